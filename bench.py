@@ -2,18 +2,26 @@
 """Headline benchmark: full Gibbs sweeps/sec (SparseBernoulliGLM.resample_model) at N=1024, T=100k, B=5 on synthetic spike trains,
 neurons sharded over --gpus MI355X, one process per GPU over RCCL.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 With N > 1 and no launcher around it (WORLD_SIZE unset) the script starts its N ranks itself, as fresh processes, before anything has
 touched a GPU; under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` it is one of the ranks.
 
-One JSON line on rank 0 (contract in the task statement): `value` = sweeps/s of the WHOLE model (max over ranks of the timed region),
-`roofline` for the dominant kernel (the integer-MFMA Gram) from HIP events recorded on the launch stream, `hbm_stage` for the streaming
-kernel next to it (residue-plane conversion), `per_rank` timings incl. the time inside collectives and the host-only share, `collective` =
-backend, world size and every rank's device, `fixed_state` = the stage table of the sweep after the timed region, run twice from the same chain
-state (`value` follows a chain that is still thinning out; this is one point of it),
-`int8_vs_fp64` = one sweep from the same state on both Gram paths, `fp64_gram_path` = the same sampler with the Gram on the fp64 kernel,
-`cpu_baseline` = the oracle timed on this box's host cores on a bounded sample (rank 0, N = 1 only).
+One JSON line on rank 0: `value` = sweeps/s of the WHOLE model (max over ranks of the timed region), `ms_per_step` = milliseconds per timed
+sweep, `roofline` for the dominant kernel (the integer-MFMA Gram) from HIP events recorded on the launch stream inside the timed region,
+`hbm_stage` for the streaming kernel next to it (residue-plane conversion), `per_rank` timings incl. the time inside collectives and the
+host-only share, `collective` = backend, world size and every rank's device.
+
+A plain run sets up, warms up, times --steps sweeps, writes --dump-outputs and prints the line.  Everything else runs only with --full
+(keys left null otherwise): `roofline.clock_power` and `roofline.box_ubench*` (amdsmi sampling, register-only MFMA loops), `roofline.hbm_side`,
+`log_likelihood_after`, `fixed_state` = the stage table of the sweep after the timed region, run twice from the same chain state (`value`
+follows a chain that is still thinning out; this is one point of it), `scaling_proxy`, `int8_vs_fp64` = one sweep from the same state on
+both Gram paths, `fp64_gram_path` = the same sampler with the Gram on the fp64 kernel, `cpu_baseline` = the oracle timed on this box's host
+cores on a bounded sample (rank 0, N = 1 only).  The --no-* options switch single parts of --full off.
+
+--dump-outputs DIR: rank 0 writes the chain state the last timed sweep left -- adjacency (float32), weights and biases (float64), what
+`model.adjacency / weights / biases` return -- as DIR/<name>.npy, at most 64 MB; a model too large for that is written for a fixed, seeded
+sample of its rows (postsynaptic neurons), whose indices go to DIR/rows.npy.  The inputs are seeded: the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -54,6 +62,26 @@ def synth(N, B, T, L, seed=0):
     basis = cosine_basis(B, L=L) / L
     Y = (rng.random((T, N)) < 0.08).astype(np.float64)
     return basis, Y
+
+
+DUMP_BYTES = 60 * 2 ** 20      # what --dump-outputs may write, .npy headers aside (the limit is 64 MB)
+
+
+def dump_outputs(path, A, W, b, rows=None, max_bytes=DUMP_BYTES):
+    """Writes the state a caller of resample_model() receives (A: N x N, W: N x N x B, b: N) as path/{adjacency,weights,biases}.npy.
+    rows: the rows that can have changed (a shard); all N by default.  When they do not fit in max_bytes, a fixed, seeded sample of
+    them is written instead, sorted, and its indices go to path/rows.npy.  Returns the names written."""
+    rows = np.arange(A.shape[0]) if rows is None else np.asarray(rows)
+    per_row = A[0].size * 4 + W[0].size * 8 + 8
+    out = {}
+    if rows.size * per_row > max_bytes:
+        rows = np.sort(np.random.default_rng(0).choice(rows, max(1, int(max_bytes // per_row)), replace=False))
+        out["rows"] = rows.astype(np.float64)
+    out.update(adjacency=A[rows].astype(np.float32), weights=W[rows].astype(np.float64), biases=np.asarray(b)[rows].astype(np.float64))
+    os.makedirs(path, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(path, name + ".npy"), v)
+    return sorted(out)
 
 
 def cpu_baseline(model, cfg, neurons=2, proposals=32, budget_s=150.0):
@@ -384,8 +412,13 @@ def self_launch(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=1)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=1, help="timed sweeps")
+    ap.add_argument("--warmup", type=int, default=1, help="sweeps before the timed ones")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need (clock / power sampling, the box's MFMA loops, HBM-side probe, "
+                         "log-likelihood, fixed_state, scaling_proxy, the fp64 Gram path, the CPU baseline); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the chain state the last timed sweep left as DIR/<name>.npy (rank 0; at most 64 MB)")
     ap.add_argument("--config", default="cfg3", choices=sorted(CONFIGS))
     ap.add_argument("--N", type=int)
     ap.add_argument("--T", type=int)
@@ -414,6 +447,8 @@ def main():
     ap.add_argument("--no-scaling-proxy", action="store_true",
                     help="skip scaling_proxy (one rank's shard of a 2 / 4 / 8-GPU run, timed on this GPU; N = 1 only)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     cfg = dict(CONFIGS[args.config])
     for k in ("N", "T", "B"):
         if getattr(args, k):
@@ -502,7 +537,7 @@ def main():
 
     props = torch.cuda.get_device_properties(local)
     pci = "%04x:%02x:%02x.0" % (getattr(props, "pci_domain_id", 0), getattr(props, "pci_bus_id", 0), getattr(props, "pci_device_id", 0))
-    watch = PowerWatch(pci, index=local) if rank == 0 else None
+    watch = PowerWatch(pci, index=local) if rank == 0 and args.full else None
     # who took part in the collectives: backend, world size and every rank's device (what a multi-GPU record is checked against)
     me = {"rank": rank, "device": "cuda:%d" % local, "name": props.name, "pci": pci}
     ranks_info = [me]
@@ -542,8 +577,11 @@ def main():
 
     for _ in range(args.warmup):
         model.resample_model()
-    ubench = box_ubench() if rank == 0 and not args.no_box_ubench else None
+    ubench = box_ubench() if rank == 0 and args.full and not args.no_box_ubench else None
     dt, dt_mine, stages, comm_s, power = timed(args.steps, watched=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model.adjacency, model.weights, model.biases,
+                     rows=np.arange(model.n0, model.n1) if model._shard_override else None)
     host_busy, launch_s = timed.host_busy, timed.launch
     stages = {k_: dict(v_, ms=v_["ms"] / args.steps, calls=v_["calls"] / args.steps, work=v_["work"] / args.steps) for k_, v_ in stages.items()}
 
@@ -561,11 +599,13 @@ def main():
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
 
-    barrier()
-    t_ll = time.perf_counter()
-    ll = model.log_likelihood()                # the chain state right after the timed region (warmup + steps sweeps from the initial state)
-    barrier()
-    t_ll = time.perf_counter() - t_ll          # log_likelihood() on its own: activation + fused reduction (+ scalar all-reduce)
+    ll = t_ll = None
+    if args.full:
+        barrier()
+        t_ll = time.perf_counter()
+        ll = model.log_likelihood()                # the chain state right after the timed region (warmup + steps sweeps from the initial state)
+        barrier()
+        t_ll = time.perf_counter() - t_ll          # log_likelihood() on its own: activation + fused reduction (+ scalar all-reduce)
 
     # ---- two more sweeps from ONE chain state (not part of `value`): the state the timed region ended in, restored in between.  `value`
     # follows the chain, whose adjacency is still thinning out during the timed sweeps (the flip and weight stages follow its density); this
@@ -573,7 +613,7 @@ def main():
     # so the two agree on what they measure, and with the driver's fixed --warmup / --steps it is the same point of the same seeded chain
     # from round to round
     fixed, stages_full = None, {}
-    if not args.no_fixed_state and not model._shard_override:
+    if args.full and not args.no_fixed_state and not model._shard_override:
         keep_state = model.get_state()
         dens0 = float(model.adjacency.mean())
         d_a, _, st_a, _, _ = timed(1)
@@ -591,12 +631,12 @@ def main():
                  "stages_ms_note": "flips.init / flips.decide / flips.apply are the pieces of `flips`"}
 
     # ---- HBM-side traffic of the product kernel from the SMU's memory-controller counter (rank 0; not part of `value`)
-    hbm_side = hbm_side_probe(eng, watch) if rank == 0 and not args.no_hbm_probe else None
+    hbm_side = hbm_side_probe(eng, watch) if rank == 0 and args.full and not args.no_hbm_probe else None
 
     # ---- what ONE rank of a 2 / 4 / 8-GPU run does, timed here (the driver's multi-GPU run is the measurement; this is the stand-in a
     # one-GPU box can give): the sweep of the first N/G neurons of this model from its current state (not advanced), twice each
     scaling = None
-    if world == 1 and not args.no_scaling_proxy and not model._shard_override and cfg.get("obs") is None and N % 8 == 0 and N >= 64:
+    if args.full and world == 1 and not args.no_scaling_proxy and not model._shard_override and cfg.get("obs") is None and N % 8 == 0 and N >= 64:
         scaling = scaling_proxy(model, eng, N, B, T)
         if fixed:
             # the proxy sweeps start from the chain state fixed_state was measured at (sweep warmup + steps), which is sparser than the states
@@ -605,7 +645,7 @@ def main():
 
     # ---- the two Gram paths from the same state (consistency), then the fp64 path timed on its own
     cmp64 = consistency = None
-    took_i8 = bool(allmax(float(any(ds.int8 for ds in eng.datasets))))      # every rank runs the extra sweeps, or none
+    took_i8 = args.full and bool(allmax(float(any(ds.int8 for ds in eng.datasets))))      # every rank runs the extra sweeps, or none
     if took_i8 and not args.no_fp64_compare and not model._shard_override:
         state = model.get_state()
         model.resample_model()
@@ -675,7 +715,8 @@ def main():
                            % ("the top-level stages" if timed_stages is TIMED_STAGES else "the dominant kernel's only at this size", args.steps),
             "fixed_state": fixed, "collective": collective,
             "per_rank": per_rank,
-            "setup_s": round(t_setup, 2), "log_likelihood_after": ll, "log_likelihood_ms": round(t_ll * 1e3, 2),
+            "setup_s": round(t_setup, 2), "log_likelihood_after": ll, "log_likelihood_ms": round(t_ll * 1e3, 2) if args.full else None,
+            "full": args.full,
         }
         gi = stage("gram.int8")
         if gi["ms"] > g["ms"]:
@@ -746,7 +787,7 @@ def main():
             out["roofline"] = {"bound": "hbm", "kernel": "scaled_gram_kernel (J[n] = X'X / eta_n, lower triangle)", "achieved": ach,
                                "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": ach / PEAK_HBM_GBS if ach else None, "traffic": None,
                                "launches": gs["calls"], "avg_launch_ms": gs["ms"] / gs["calls"] if gs["calls"] else None}
-        if not args.no_cpu_baseline and world == 1 and cfg.get("obs") is None and not model._shard_override:
+        if args.full and not args.no_cpu_baseline and world == 1 and cfg.get("obs") is None and not model._shard_override:
             out["cpu_baseline"] = cpu_baseline(model, cfg)
         else:
             out["cpu_baseline"] = None

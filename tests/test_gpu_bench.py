@@ -18,7 +18,7 @@ def _bench(gpus, *extra, **envkw):
     env.update(envkw)
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--config", "cfg2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--config", "cfg2", "--steps", "2", "--warmup", "1", "--full",
            "--no-cpu-baseline", "--no-fp64-compare", "--no-scaling-proxy"] + list(extra)
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -77,8 +77,8 @@ def test_scaling_proxy_times_every_shard():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "PGL_BENCH_DEVICE", "PGL_DIST_BACKEND"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-fp64-compare",
-           "--no-box-ubench", "--no-hbm-probe"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg2", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline",
+           "--no-fp64-compare", "--no-box-ubench", "--no-hbm-probe"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
@@ -108,3 +108,38 @@ def test_ubench_entry_point():
     with pytest.raises(PglError):
         call("pgl_ubench_mfma", 2, 0.2, ctypes.byref(r), None, None)
     assert b"argument check" in load().pgl_last_error()
+
+
+def test_plain_run_times_its_steps_and_dumps_the_state(tmp_path):
+    """a plain run (no --full) times --steps sweeps and measures nothing else; --dump-outputs writes the state the last timed sweep left,
+    and the same arguments give the same inputs, hence (the chain being bit-reproducible) the same arrays"""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "PGL_BENCH_DEVICE", "PGL_DIST_BACKEND"):
+        env.pop(k, None)
+    dumps = []
+    for k in range(2):
+        out = str(tmp_path / str(k))
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg2", "--steps", "3", "--warmup", "1", "--dump-outputs", out]
+        p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["full"] is False and d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "sweeps/s" and d["higher_is_better"] is True
+        assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-9 * d["value"]
+        assert d["roofline"]["achieved"] > 0 and d["dtype"].startswith("f64")
+        for key in ("fixed_state", "log_likelihood_after", "cpu_baseline", "scaling_proxy", "int8_vs_fp64", "fp64_gram_path"):
+            assert d.get(key) is None, key
+        r = d["roofline"]
+        assert r["clock_power"] is None and r["box_ubench_tops"] is None and r["hbm_side"] is None
+        assert sorted(os.listdir(out)) == ["adjacency.npy", "biases.npy", "weights.npy"]
+        arrs = {n: np.load(os.path.join(out, n + ".npy")) for n in ("adjacency", "weights", "biases")}
+        assert arrs["adjacency"].shape == (128, 128) and arrs["adjacency"].dtype == np.float32
+        assert set(np.unique(arrs["adjacency"])) <= {0.0, 1.0} and 0 < arrs["adjacency"].mean() < 1
+        assert arrs["weights"].shape == (128, 128, 5) and arrs["weights"].dtype == np.float64 and np.isfinite(arrs["weights"]).all()
+        assert arrs["biases"].shape == (128,) and arrs["biases"].dtype == np.float64
+        assert sum(os.path.getsize(os.path.join(out, f)) for f in os.listdir(out)) <= 64 * 10 ** 6
+        dumps.append(arrs)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
