@@ -310,6 +310,23 @@ int pgl_get_state(const pgl_sweep_t* s, int* a_host, double* W_host, double* b_h
 const char* pgl_stage_name(int i);
 int pgl_stage_times_collect(pgl_stage_times_t* t);    /* waits for the recorded events and adds them to ms / calls / work */
 
+/* ---- forward simulation ------------------------------------------------------------------------------------------ */
+/* Bins [t0, t0 + Tc) of the population model's forward simulation (pyglm/models.py:98-151, generate: the loop at :129-144), serial in t,
+ * in ONE cooperative launch.  Per bin t, for every neuron n:
+ *   x_t[m][:] = sum_{l < L} Y[t-1-l][m] basis[l][:]            (:134, X[t] = Y[t-L:t].T.dot(flipud(basis)); bins before 0 are zero)
+ *   psi       = sum_{d < N*B} Wm[n][d] x_t[d] + bias[n]        (:137; Wm [N][N*B] is the stored W, not a*W, as the reference)
+ *   obs 0 (Bernoulli, regression.py rvs):  y = U[t-t0][n] < 1 / (1 + exp(-psi))  ? 1 : 0   (U: the bin's uniforms, npr.rand(N))
+ *   obs 1 (Gaussian):                       y = psi + noise_scale * U[t-t0][n]   without contraction (U: npr.randn(N); noise_scale =
+ *                                                                                sqrt(eta), formed by the caller)
+ * U [Tc][N] holds the caller's draws; Y [Tc][N] receives y.  ring [L][N] (row t mod L = Y[t]) carries the history from one call to the next:
+ * zero it before the call with t0 = 0, then pass it on untouched; calls on consecutive chunks compose to the whole trajectory.
+ * work: device scratch of pgl_generate_work_bytes(N, B) bytes, 16-byte aligned (exchange buffers and barrier words; the call zeroes what it
+ * needs).  status [2] (device int): the caller zeroes it; a grid barrier that does not complete within 2 s writes {1, bin} and the
+ * launch ends early (Y from that bin on is not valid).  N*B <= 2^30. */
+size_t pgl_generate_work_bytes(int N, int B);
+int pgl_generate(const double* Wm, const double* bias, const double* basis, int N, int B, int L, int obs, double noise_scale, const double* U,
+                 double* ring, double* Y, long t0, int Tc, void* work, int* status, void* hip_stream);
+
 /* ---- box calibration (diagnostic; nothing on the sampling path calls it) ------------------------------------------------------- */
 /* What the matrix cores of the current device sustain right now: a register-only MFMA loop on every CU for ~`seconds` (a quarter of it
  * untimed first, so that clocks and the package power limiter settle), timed with HIP events on `stream`; WAITS for the stream.

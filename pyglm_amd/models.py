@@ -377,8 +377,32 @@ class NonlinearAutoregressiveModel(object):
             mus.append(self._gather_rows(np.ascontiguousarray(mu.T)).T)
         return mus
 
-    def generate(self, keep=True, T=100, verbose=False, intvl=10):
-        """(models.py:98-151) forward simulation, serial in t (host; not on the Gibbs hot path)."""
+    def _generate_obs(self, gpu):
+        """which device path generate(gpu=...) takes: simulate.OBS_BERNOULLI / OBS_GAUSSIAN, or None for the host loop.  The device draws
+        exactly what the built-in Bernoulli and Gaussian rvs draw; any other rvs (negative binomial: npr.negative_binomial uses the stream
+        according to the values it draws; a user's override) keeps the host loop, and so does a model with an engine_factory"""
+        if gpu is False:
+            return None
+        from . import simulate
+        reg = self.regressions[0]
+        kinds = {_regression.SparseBernoulliRegression.rvs: simulate.OBS_BERNOULLI, _regression.SparseGaussianRegression.rvs: simulate.OBS_GAUSSIAN}
+        obs = None if "rvs" in vars(reg) else kinds.get(type(reg).rvs)
+        if obs is None or self._engine_factory is not None:
+            if gpu:
+                raise ValueError("generate(gpu=True): the device path simulates the built-in Bernoulli and Gaussian observations of a model "
+                                 "without an engine_factory; %s.rvs%s keeps the host loop (gpu=None or False)"
+                                 % (type(reg).__name__, "" if self._engine_factory is None else " with an engine_factory"))
+            return None
+        if not gpu:
+            import torch
+            if not torch.cuda.is_available():
+                return None
+        return obs
+
+    def generate(self, keep=True, T=100, verbose=False, intvl=10, gpu=None):
+        """(models.py:98-151) forward simulation, serial in t.  gpu=None: on the GPU (pyglm_amd/simulate.py, pgl_generate) whenever one is
+        available and the observation model is the built-in Bernoulli or Gaussian one, else the host loop; gpu=True: on the GPU or an
+        error; gpu=False: the host loop.  Both paths draw NumPy's global generator in the same order and return the same (X, Y)."""
         if T == 0:
             return np.zeros((0, self.N))
         assert isinstance(T, int), "Size must be an integer number of time bins"
@@ -388,6 +412,15 @@ class NonlinearAutoregressiveModel(object):
         assert not np.allclose(flipped, self.basis)
         Wm = self.weights.reshape(N, N * B)               # as the reference: the stored W, not a*W
         bias = self.biases
+        obs = self._generate_obs(gpu) if T > 0 else None
+        if obs is not None:
+            from . import simulate
+            # (only regressions[0].rvs is called, for every neuron -- the reference's quirk -- and so only its eta is the noise)
+            scale = float(np.sqrt(self.regressions[0].eta)) if obs == simulate.OBS_GAUSSIAN else 0.0
+            X, Y = simulate.generate(Wm, bias, self.basis, T, obs, scale, device=self._device, verbose=verbose, intvl=intvl)
+            if keep:
+                self.add_data(Y, X=X)
+            return X, Y
         Y = np.zeros((T + L, N))
         X = np.zeros((T + L, N, B))
         for t in range(L, T + L):
