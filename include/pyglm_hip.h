@@ -62,6 +62,17 @@ int pgl_pg_loglik(double* Psi, long ldpsi, const double* bias, const double* Y, 
                   double* llpart, double* ll_out, int accumulate, int T, int nloc, int obs, double xi, uint64_t seed, uint64_t sweep,
                   uint64_t neuron0, uint64_t elem0, void* hip_stream);
 int pgl_pg_loglik_partials(int T);
+/* pgl_pg_loglik for every Polya-gamma observation model (the hooks of _SparsePGRegressionBase, regression.py:479-489):
+ *   obs 0 Bernoulli (:514-522)          a = y, b = 1, c = 1
+ *   obs 1 negative binomial             a = y, b = y + xi, log c = lgamma(y + xi) - lgamma(y + 1) - lgamma(xi)
+ *   obs 3 binomial (named at :463-466)  a = y, b = n,      log c = lgamma(n + 1) - lgamma(y + 1) - lgamma(n - y + 1)   (0 <= y <= n)
+ *   obs 4 hooks: a, b, log c read per cell from hooks[t * 3 ldh + n], [.. + ldh + n], [.. + 2 ldh + n] (a | b | log c, b >= 0): any
+ *         subclass of the base class; the terms go through the same arithmetic, in the same order, as obs 0, 1 and 3
+ * param: optional [nloc] per-neuron xi (obs 1, > 0) or n (obs 3, >= 0); NULL: the scalar xi for every neuron.  hooks: obs 4 only
+ * (ldh >= nloc).  With param = hooks = NULL and obs 0 / 1 this is pgl_pg_loglik, bit for bit. */
+int pgl_pg_loglik_ex(double* Psi, long ldpsi, const double* bias, const double* Y, long ldy, double* Omega, long ldo, double* Kappa, long ldk,
+                     double* llpart, double* ll_out, int accumulate, int T, int nloc, int obs, double xi, const double* param, const double* hooks,
+                     long ldh, uint64_t seed, uint64_t sweep, uint64_t neuron0, uint64_t elem0, void* hip_stream);
 
 /* Gaussian observations (SparseGaussianRegression, pyglm/regression.py:380-446): Psi[t][n] += bias[n] (mean, :430-431); when Omega is
  * non-NULL Omega[t][n] = inv_eta[n] (:421-423) and Kappa[t][n] = Y[t][n] * inv_eta[n] (:425-426); sse_out[n] (+)= sum_t (y - psi)^2, the
@@ -228,6 +239,8 @@ typedef struct {
     const double* omega_override;  /* optional [T][nloc]: replaces the PG draws (test hook: the reference fixtures inject omega) */
     const double* xmax;            /* optional [D]: max_t |X[t][d]| (the column maxima pgl_i8_colstats gives for Om = NULL).  With it and
                                     * pgl_sweep_t.i8_norm the scales of omega_n X are taken for a whole batch of neurons at once (see there) */
+    const double* hooks;           /* [T][3 ldn] a | b | log c of the local neurons (pgl_pg_loglik_ex, obs 4); required with pgl_sweep_t.obs = 4,
+                                    * NULL otherwise */
 } pgl_dataset_t;
 
 #define PGL_I8_MAX_GROUP 64
@@ -243,7 +256,8 @@ typedef struct {                   /* host; zero-initialise.  Per stage (pgl_sta
 
 typedef struct {
     int N, B, n0, nloc, nb;        /* neurons, basis functions, first local neuron (global index), local neurons, neurons per batch */
-    int obs; double xi;            /* 0 Bernoulli, 1 negative binomial (b = y + xi), 2 Gaussian */
+    int obs; double xi;            /* 0 Bernoulli, 1 negative binomial (b = y + xi), 2 Gaussian, 3 binomial (b = xi = n trials), 4 hooks
+                                    * (pgl_dataset_t.hooks): the models of pgl_pg_loglik_ex; obs_param overrides xi per neuron */
     int visit_order;               /* 1: sweep tableau in proposal order (see pgl_flip_t) */
     int planes, i8_group;          /* integer Gram: moduli in use where a data set does not say, neurons per launch (<= PGL_I8_MAX_GROUP; 8 at large D,
                                     * more where a plane has only a few tiles: multiples of 8 fill the per-XCD work lists) */
@@ -294,6 +308,8 @@ typedef struct {
     int flip_single_pass;          /* 1: one pass over the trailing tableau per proposal window instead of one per pair of windows -- the same
                                     * multiply-adds in the same order, the same bits (tests/test_gpu_parity.py compares the two) */
     pgl_stage_times_t* times;      /* optional (host): stage timing */
+    const double* obs_param;       /* optional [nloc]: xi per neuron (obs 1, every entry > 0) or n per neuron (obs 3, >= 0); NULL: the scalar xi.
+                                    * Device memory, not read by the argument check: the caller guarantees the signs */
 } pgl_sweep_t;
 
 int pgl_sweep_dims(int N, int B, int nloc, int* Dp, int* ldn, int* ldj);

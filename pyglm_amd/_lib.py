@@ -24,7 +24,8 @@ class CholState(ctypes.Structure):   # pgl_chol_t
 
 class Dataset(ctypes.Structure):     # pgl_dataset_t
     _fields_ = [("T", c_i), ("Tp", c_i), ("X", c_p), ("Xt", c_p), ("Y", c_p), ("Psi", c_p), ("OK", c_p), ("llpart", c_p), ("elem0", c_u64),
-                ("int8", c_i), ("planes", c_i), ("sA", c_p), ("PA", c_p), ("omega_override", c_p), ("xmax", c_p)]
+                ("int8", c_i), ("planes", c_i), ("sA", c_p), ("PA", c_p), ("omega_override", c_p), ("xmax", c_p),
+                ("hooks", c_p)]
 
 
 NSTAGES = 16
@@ -44,7 +45,7 @@ class Sweep(ctypes.Structure):       # pgl_sweep_t
                 ("d_idx", c_p), ("d_sign", c_p), ("d_cnt", c_p), ("batch_k", c_p), ("act", c_p), ("na", c_p),
                 ("i8_PB", c_p), ("i8_R", c_p), ("i8_stat", c_p), ("i8_slice", c_i), ("i8_PAs", c_p), ("i8_Rx", c_p), ("i8_norm", c_p), ("nrun", c_i), ("nfirst", c_i),
                 ("all_deterministic", c_i), ("init_rows_bound", c_i), ("active_rows_bound", c_i), ("flip_single_pass", c_i),
-                ("times", ctypes.POINTER(StageTimes))]
+                ("times", ctypes.POINTER(StageTimes)), ("obs_param", c_p)]
 
 
 # symbol -> argument types; every function returns int status unless noted. Mirrors include/pyglm_hip.h 1:1.
@@ -58,6 +59,7 @@ SIGNATURES = {
     "pgl_activation": [c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_i, c_i, c_p],
     "pgl_pg_loglik": [c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_p, c_i, c_i, c_i, c_i, c_d, c_u64, c_u64, c_u64, c_u64, c_p],
     "pgl_pg_loglik_partials": [c_i],
+    "pgl_pg_loglik_ex": [c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_p, c_i, c_i, c_i, c_i, c_d, c_p, c_p, c_l, c_u64, c_u64, c_u64, c_u64, c_p],
     "pgl_gaussian_stats": [c_p, c_l, c_p, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p, c_p, c_i, c_i, c_i, c_p],
     "pgl_scaled_gram": [c_p, c_l, c_p, c_p, c_l, c_l, c_i, c_i, c_p],
     "pgl_weighted_gram": [c_p, c_l, c_i, c_p, c_l, c_i, c_i, c_i, c_p, c_l, c_l, c_i, c_p],

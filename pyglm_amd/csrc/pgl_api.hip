@@ -99,8 +99,17 @@ int pgl_pg_loglik(double* Psi, long ldpsi, const double* bias, const double* Y, 
                   uint64_t neuron0, uint64_t elem0, void* st) {
     PGL_CHECK_ARG(Psi && Y && llpart && ll_out && T > 0 && nloc > 0 && (obs == 0 || obs == 1));
     PGL_CHECK_ARG(obs == 0 || xi > 0);
-    return pgl_k_pg_loglik(Psi, ldpsi, bias, Y, ldy, Omega, ldo, Kappa, ldk, llpart, ll_out, accumulate, T, nloc, obs, xi, seed, sweep, neuron0,
-                           elem0, ST(st));
+    return pgl_k_pg_loglik(Psi, ldpsi, bias, Y, ldy, Omega, ldo, Kappa, ldk, llpart, ll_out, accumulate, T, nloc, obs, xi, nullptr, nullptr, 0, seed,
+                           sweep, neuron0, elem0, ST(st));
+}
+int pgl_pg_loglik_ex(double* Psi, long ldpsi, const double* bias, const double* Y, long ldy, double* Omega, long ldo, double* Kappa, long ldk,
+                     double* llpart, double* ll_out, int accumulate, int T, int nloc, int obs, double xi, const double* param, const double* hooks,
+                     long ldh, uint64_t seed, uint64_t sweep, uint64_t neuron0, uint64_t elem0, void* st) {
+    PGL_CHECK_ARG(Psi && Y && llpart && ll_out && T > 0 && nloc > 0 && obs >= 0 && obs <= 4 && obs != 2);
+    PGL_CHECK_ARG(param != nullptr || obs == 0 || obs == 4 || (obs == 1 ? xi > 0 : xi >= 0));
+    PGL_CHECK_ARG(obs != 4 || (hooks != nullptr && ldh >= nloc));
+    return pgl_k_pg_loglik(Psi, ldpsi, bias, Y, ldy, Omega, ldo, Kappa, ldk, llpart, ll_out, accumulate, T, nloc, obs, xi, param, obs == 4 ? hooks : nullptr,
+                           ldh, seed, sweep, neuron0, elem0, ST(st));
 }
 int pgl_pg_loglik_partials(int T) { return pgl_k_pg_loglik_nblk(T); }
 

@@ -42,10 +42,28 @@ struct PgLlArgs {
     int T, nloc;
     int obs;                            // 0 Bernoulli (a=y,b=1,c=1)  1 negative binomial (a=y, b=y+xi, c=C(y+xi-1,y))
                                         // 2 Gaussian (regression.py:380-446): omega = 1/eta, kappa = y/eta, "ll" = sum of squared residuals
-    double xi;
+                                        // 3 binomial (a=y, b=n, c=C(n,y))  4 hooks: a, b, log c read from `hooks`
+    double xi;                          // xi (obs 1) or n (obs 3) where param is null
     const double* inv_eta;              // [nloc] 1/eta per neuron (obs == 2 only)
     uint64_t seed, sweep, neuron0, elem0;
+    const double* param;                // optional [nloc]: xi (obs 1) or n (obs 3) per neuron
+    const double* hooks; long ldh;      // obs 4: [T][3 ldh] = a | b | log c of the local neurons
 };
+
+// a(y), b(y), log c(y) of one cell (regression.py:479-489) for the PG observation models; (a, b, logc) = (y, 1, 0) for Bernoulli
+__device__ __forceinline__ void pg_abc(const PgLlArgs& g, int n, long t, double y, double& a, double& b, double& logc) {
+    a = y; b = 1.0; logc = 0.0;
+    if (g.obs == 1) {
+        const double xi = g.param ? g.param[n] : g.xi;
+        b = y + xi; logc = lgamma(y + xi) - lgamma(y + 1.0) - lgamma(xi);
+    } else if (g.obs == 3) {
+        const double m = g.param ? g.param[n] : g.xi;
+        b = m; logc = lgamma(m + 1.0) - lgamma(y + 1.0) - lgamma(m - y + 1.0);
+    } else if (g.obs == 4) {
+        const double* h = g.hooks + t * 3 * g.ldh + n;
+        a = h[0]; b = h[g.ldh]; logc = h[2 * g.ldh];
+    }
+}
 
 // one time bin's term of the log-likelihood (regression.py:491-494); one function for both kernels below, so that they round alike
 __device__ __forceinline__ double pg_ll_term(double logc, double a, double b, double psi) { return logc + a * psi - b * log1p(exp(psi)); }
@@ -72,8 +90,8 @@ __global__ __launch_bounds__(256) void pg_loglik_kernel(PgLlArgs g) {
                 if (g.Omega) g.Omega[(long)t * g.ldo + n] = ie;
                 continue;
             }
-            double a = y, b = 1.0, logc = 0.0;
-            if (g.obs == 1) { b = y + g.xi; logc = lgamma(y + g.xi) - lgamma(y + 1.0) - lgamma(g.xi); }
+            double a, b, logc;
+            pg_abc(g, n, t, y, a, b, logc);
             ll += pg_ll_term(logc, a, b, psi);
             if (g.Kappa) g.Kappa[(long)t * g.ldk + n] = a - 0.5 * b;
             if (g.Omega) g.Omega[(long)t * g.ldo + n] = pgl_pg_draw(b, psi, g.seed, stream, g.elem0 + (uint64_t)t);
@@ -103,8 +121,8 @@ __global__ __launch_bounds__(256) void pg_loglik_narrow_kernel(PgLlArgs g) {
             const double psi = g.Psi[(long)t * g.ldpsi + n] + bn;
             g.Psi[(long)t * g.ldpsi + n] = psi;
             const double y = g.Y[(long)t * g.ldy + n];
-            double a = y, b = 1.0, logc = 0.0;
-            if (g.obs == 1) { b = y + g.xi; logc = lgamma(y + g.xi) - lgamma(y + 1.0) - lgamma(g.xi); }
+            double a, b, logc;
+            pg_abc(g, n, t, y, a, b, logc);
             v = pg_ll_term(logc, a, b, psi);
             if (g.Kappa) g.Kappa[(long)t * g.ldk + n] = a - 0.5 * b;
             if (g.Omega) g.Omega[(long)t * g.ldo + n] = pgl_pg_draw(b, psi, g.seed, stream, g.elem0 + (uint64_t)t);
@@ -313,9 +331,9 @@ int pgl_k_row_stats(const int* a, const double* W, double* out, int N, int B, in
 }
 
 int pgl_k_pg_loglik(double* Psi, long ldpsi, const double* bias, const double* Y, long ldy, double* Omega, long ldo, double* Kappa, long ldk,
-                    double* llpart, double* ll_out, int accumulate, int T, int nloc, int obs, double xi, uint64_t seed, uint64_t sweep,
-                    uint64_t neuron0, uint64_t elem0, hipStream_t st) {
-    PgLlArgs a{Psi, ldpsi, bias, Y, ldy, Omega, ldo, Kappa, ldk, llpart, T, nloc, obs, xi, nullptr, seed, sweep, neuron0, elem0};
+                    double* llpart, double* ll_out, int accumulate, int T, int nloc, int obs, double xi, const double* param, const double* hooks,
+                    long ldh, uint64_t seed, uint64_t sweep, uint64_t neuron0, uint64_t elem0, hipStream_t st) {
+    PgLlArgs a{Psi, ldpsi, bias, Y, ldy, Omega, ldo, Kappa, ldk, llpart, T, nloc, obs, xi, nullptr, seed, sweep, neuron0, elem0, param, hooks, ldh};
     const int nblk = (T + PGLL_ROWS - 1) / PGLL_ROWS;
     if (nloc < 64 && obs != 2) hipLaunchKernelGGL(pg_loglik_narrow_kernel, dim3(nblk), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(pg_loglik_kernel, dim3(nblk, (nloc + 63) / 64), dim3(256), 0, st, a);
@@ -327,7 +345,7 @@ int pgl_k_pg_loglik(double* Psi, long ldpsi, const double* bias, const double* Y
 
 int pgl_k_gaussian_stats(double* Psi, long ldpsi, const double* bias, const double* Y, long ldy, const double* inv_eta, double* Omega, long ldo,
                          double* Kappa, long ldk, double* part, double* sse_out, int accumulate, int T, int nloc, hipStream_t st) {
-    PgLlArgs a{Psi, ldpsi, bias, Y, ldy, Omega, ldo, Kappa, ldk, part, T, nloc, 2, 1.0, inv_eta, 0, 0, 0, 0};
+    PgLlArgs a{Psi, ldpsi, bias, Y, ldy, Omega, ldo, Kappa, ldk, part, T, nloc, 2, 1.0, inv_eta, 0, 0, 0, 0, nullptr, nullptr, 0};
     const int nblk = (T + PGLL_ROWS - 1) / PGLL_ROWS;
     hipLaunchKernelGGL(pg_loglik_kernel, dim3(nblk, (nloc + 63) / 64), dim3(256), 0, st, a);
     PGL_CHECK_LAUNCH();

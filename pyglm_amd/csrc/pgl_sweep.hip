@@ -134,7 +134,7 @@ int pgl_stage_times_collect(pgl_stage_times_t* t) {
 int pgl_sweep(const pgl_sweep_t* s, uint64_t seed, uint64_t sweep, void* hip_stream) {
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     PGL_CHECK_ARG(s && s->N > 0 && s->B > 0 && s->B <= 32 && s->nloc > 0 && s->nb > 0 && s->n0 >= 0 && s->ndatasets > 0 && s->datasets);
-    PGL_CHECK_ARG(s->obs >= 0 && s->obs <= 2 && (s->obs != 1 || s->xi > 0));
+    PGL_CHECK_ARG(s->obs >= 0 && s->obs <= 4 && (s->obs_param != nullptr || s->obs != 1 || s->xi > 0) && (s->obs_param != nullptr || s->obs != 3 || s->xi >= 0));
     PGL_CHECK_ARG(s->a && s->W && s->b && s->rho && s->Jw && s->hw && s->Jb && s->hb && s->c0 && s->perm && s->u && s->z && s->ll && s->status);
     PGL_CHECK_ARG(s->Wt && s->bias && s->border && s->skip && s->Jbuf && s->Mtab && s->Ac && s->hc && s->Tinv && s->G && s->Lws && s->Ut && s->Wt_ws);
     PGL_CHECK_ARG(s->d_idx && s->d_sign && s->d_cnt && s->batch_k && s->act && s->na && (s->label == nullptr || s->c0_dense != nullptr));
@@ -155,6 +155,7 @@ int pgl_sweep(const pgl_sweep_t* s, uint64_t seed, uint64_t sweep, void* hip_str
     for (int i = 0; i < s->ndatasets; ++i) {
         const pgl_dataset_t& d = s->datasets[i];
         PGL_CHECK_ARG(d.T > 0 && d.Tp >= d.T && d.Tp % 16 == 0 && d.X && d.Xt && d.Y && d.Psi && d.OK && d.llpart);
+        PGL_CHECK_ARG(s->obs != 4 || d.hooks);
         PGL_CHECK_ARG(!d.int8 || (d.sA && (d.PA || s->i8_PAs) && (d.planes > 0 || s->planes > 0)));      // (no resident X planes: converted per slice -- or once per group for the whole data set -- into i8_PAs)
         any_i8 = any_i8 || d.int8;
     }
@@ -185,7 +186,8 @@ int pgl_sweep(const pgl_sweep_t* s, uint64_t seed, uint64_t sweep, void* hip_str
         if (s->obs == 2) RC(pgl_k_gaussian_stats(d.Psi + nf, ldn, s->bias + nf, d.Y + nf, ldn, s->inv_eta + nf, d.OK + nf, 2 * ldn, d.OK + ldn + nf, 2 * ldn, d.llpart,
                                                  s->ll + nf, i > 0, d.T, nrun, st));
         else RC(pgl_k_pg_loglik(d.Psi + nf, ldn, s->bias + nf, d.Y + nf, ldn, d.OK + nf, 2 * ldn, d.OK + ldn + nf, 2 * ldn, d.llpart, s->ll + nf, i > 0, d.T, nrun,
-                                s->obs, s->xi, seed, sweep, (uint64_t)(s->n0 + nf), d.elem0, st));
+                                s->obs, s->xi, s->obs_param ? s->obs_param + nf : nullptr, s->obs == 4 ? d.hooks + nf : nullptr, ldn, seed, sweep,
+                                (uint64_t)(s->n0 + nf), d.elem0, st));
         clk.toc(m);
         if (d.omega_override) {       // test hook: the reference fixtures inject omega
             if (hipMemcpy2DAsync(d.OK, (size_t)2 * ldn * sizeof(double), d.omega_override, (size_t)nloc * sizeof(double), (size_t)nloc * sizeof(double),

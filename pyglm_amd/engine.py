@@ -92,7 +92,9 @@ class _Dataset(object):
 
 
 class GibbsEngine(object):
-    OBS = {"bernoulli": 0, "negbin": 1, "gaussian": 2}
+    # observation models (include/pyglm_hip.h, pgl_pg_loglik_ex): the built-in Bernoulli, negative-binomial, Gaussian and binomial regressions,
+    # and "hooks" -- any other Polya-gamma model, its a(y), b(y), log c(y) evaluated on the host and kept next to the data (add_data obs_terms)
+    OBS = {"bernoulli": 0, "negbin": 1, "gaussian": 2, "binomial": 3, "hooks": 4}
 
     def __init__(self, N, B, n0=0, n1=None, device=None, obs="bernoulli", xi=1.0, batch=None, mem_budget_bytes=None,
                  design_only=False, visit_order=True, gram=None, likelihood_only=False, planes=None, i8_group=None, i8_slice=None,
@@ -101,7 +103,9 @@ class GibbsEngine(object):
         convolution).  likelihood_only: activation / log-likelihood / means only -- no sweep buffers, no residue planes (a held-out data
         set costs X', Y and Psi, nothing else).  i8_group / i8_slice / i8_resident: override the integer Gram's plan (_i8_plan) -- neurons
         per product launch, time bins per slice, X's planes kept (True) or converted per slice (False); tests and probes.  device_share: number of
-        engines (ranks) that share this GPU -- each then stays inside an equal share of its memory (bench.py's one-GPU dry run of N ranks)."""
+        engines (ranks) that share this GPU -- each then stays inside an equal share of its memory (bench.py's one-GPU dry run of N ranks).
+        xi: the negative-binomial xi (obs "negbin") or the binomial number of trials n (obs "binomial"): a scalar, or one value per neuron
+        of the model (N) or of this shard (n1 - n0)."""
         if not torch.cuda.is_available():
             raise _lib.PglError("pyglm_amd needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU fallback")
         _lib.load()
@@ -118,7 +122,8 @@ class GibbsEngine(object):
             self._init(N, B, obs, xi, batch, mem_budget_bytes, design_only, visit_order, gram, likelihood_only, planes)
 
     def _init(self, N, B, obs, xi, batch, mem_budget_bytes, design_only, visit_order, gram, likelihood_only, planes):
-        self.obs, self.xi = self.OBS[obs], float(xi)
+        self.obs = self.OBS[obs]
+        self.xi, self.obs_param = self._obs_param(xi)
         self.Dp = _r(self.D + 1, 16)
         self.ldn = _r(self.nloc, 2)
         self.ldj = _r(self.D + 2, 16)
@@ -168,6 +173,24 @@ class GibbsEngine(object):
         self.wait_seconds = 0.0
         self.overlap_seconds = 0.0
         self.launch_seconds = 0.0      # inside the pgl_sweep call itself: ~3 000 launches at the headline size (and, when the queue is full, waiting)
+
+    def _obs_param(self, xi):
+        """-> (scalar xi, None) or (1.0, [nloc] device array of the shard's per-neuron values), checked: > 0 (negative binomial), >= 0 (binomial)"""
+        v = np.asarray(xi, dtype=np.float64)
+        if v.ndim == 0:
+            vals, out = v.reshape(1), (float(v), None)
+        else:
+            v = v.reshape(-1)
+            if v.size == self.N:
+                v = v[self.n0:self.n1]
+            elif v.size != self.nloc:
+                raise ValueError("xi: %d values for a model of %d neurons (shard of %d)" % (v.size, self.N, self.nloc))
+            vals, out = v, (1.0, torch.from_numpy(np.ascontiguousarray(v)).to(self.dev))
+        if self.obs == 1 and not np.all(vals > 0):
+            raise ValueError("negative binomial: xi must be > 0")
+        if self.obs == 3 and not np.all((vals >= 0) & (vals == np.floor(vals))):
+            raise ValueError("binomial: the number of trials n must be an integer >= 0")
+        return out
 
     # ------------------------------------------------------------------ stage timing (HIP events on the launch stream)
     def _tic(self, name, work=0.0):
@@ -315,12 +338,19 @@ class GibbsEngine(object):
 
     # ------------------------------------------------------------------ data
     @_on_device
-    def add_data(self, Y, X=None, basis=None):
+    def add_data(self, Y, X=None, basis=None, obs_terms=None):
         """models.py:66-80: Y is (T, N) counts; X (T, N, B) optional, else built on the device from `basis` (L, B)
-        by pgl_design_matrix (utils/basis.py:5-34)."""
+        by pgl_design_matrix (utils/basis.py:5-34).  obs_terms (obs "hooks" only, and required there): (A, Bv, logC), the host arrays
+        a(y), b(y), log c(y) of the LOCAL neurons, each (T, n1 - n0) -- kept on the device next to the data set (3 T ldn doubles)."""
         Y = np.ascontiguousarray(Y, dtype=np.float64)
         T = Y.shape[0]
         assert Y.shape == (T, self.N)
+        if (obs_terms is not None) != (self.obs == 4) and not self.design_only:
+            raise ValueError("obs_terms are the data of the hooks observation model: required with obs='hooks', and only there")
+        if obs_terms is not None:
+            terms = [np.broadcast_to(np.asarray(v, dtype=np.float64), (T, self.nloc)) for v in obs_terms]
+            if len(terms) != 3 or not all(np.all(np.isfinite(v)) for v in terms) or not np.all(terms[1] >= 0):
+                raise ValueError("obs_terms: a(y), b(y), log c(y) must be finite, with b(y) >= 0")
         ds = _Dataset()
         ds.T, ds.Tp = T, _r(T, 16)
         ds.X = self._z(ds.Tp, self.Dp)
@@ -347,6 +377,13 @@ class GibbsEngine(object):
             return ds
         ds.Y = self._z(T, self.ldn)
         ds.Y[:, :self.nloc] = torch.from_numpy(np.ascontiguousarray(Y[:, self.n0:self.n1])).to(self.dev)
+        ds.hooks = None
+        if obs_terms is not None:
+            # [T][3 ldn] = a | b | log c (pgl_pg_loglik_ex), allocated before the batch size and the integer Gram's plan are chosen from the
+            # memory left: 2.5 GB per data set at N = 1024, T = 1e5
+            ds.hooks = self._z(T, 3, self.ldn)
+            for k in range(3):
+                ds.hooks[:, k, :self.nloc] = torch.from_numpy(np.require(terms[k], requirements=["C", "W"])).to(self.dev)
         self._ensure_batch()
         ds.Psi = self._z(T, self.ldn)
         if not self.likelihood_only:
@@ -572,8 +609,13 @@ class GibbsEngine(object):
                      kp, 2 * self.ldn, ptr(ds.llpart), ptr(self.ll), int(i > 0), ds.T, self.nloc, st)
                 self._toc(h)
                 continue
-            call("pgl_pg_loglik", ptr(ds.Psi), self.ldn, ptr(self.bias), ptr(ds.Y), self.ldn, ptr(om), 2 * self.ldn, kp, 2 * self.ldn,
-                 ptr(ds.llpart), ptr(self.ll), int(i > 0), ds.T, self.nloc, self.obs, self.xi, int(seed), int(sweep), self.n0, ds.elem0, st)
+            if self.obs in (0, 1) and self.obs_param is None:
+                call("pgl_pg_loglik", ptr(ds.Psi), self.ldn, ptr(self.bias), ptr(ds.Y), self.ldn, ptr(om), 2 * self.ldn, kp, 2 * self.ldn,
+                     ptr(ds.llpart), ptr(self.ll), int(i > 0), ds.T, self.nloc, self.obs, self.xi, int(seed), int(sweep), self.n0, ds.elem0, st)
+            else:
+                call("pgl_pg_loglik_ex", ptr(ds.Psi), self.ldn, ptr(self.bias), ptr(ds.Y), self.ldn, ptr(om), 2 * self.ldn, kp, 2 * self.ldn,
+                     ptr(ds.llpart), ptr(self.ll), int(i > 0), ds.T, self.nloc, self.obs, self.xi, ptr(self.obs_param), ptr(ds.hooks), self.ldn,
+                     int(seed), int(sweep), self.n0, ds.elem0, st)
             self._toc(h)
         return self.ll
 
@@ -685,7 +727,7 @@ class GibbsEngine(object):
             for i, ds in enumerate(self.datasets):
                 dsets[i] = _lib.Dataset(ds.T, ds.Tp, ptr(ds.X), ptr(ds.Xt), ptr(ds.Y), ptr(ds.Psi), ptr(ds.OK), ptr(ds.llpart), ds.elem0, int(ds.int8),
                                         int(getattr(ds, "planes", 0) or 0), ptr(getattr(ds, "sA", None)), ptr(getattr(ds, "PA", None)),
-                                        ptr(ovs[i]) if ovs else None, ptr(getattr(ds, "xmax", None)))
+                                        ptr(ovs[i]) if ovs else None, ptr(getattr(ds, "xmax", None)), ptr(getattr(ds, "hooks", None)))
             sw = _lib.Sweep(N, B, self.n0, nloc, self.nb, self.obs, self.xi, int(self.visit_order), self.planes or 0, i8[2] if i8 else 0,
                             dsets, len(self.datasets), ptr(self.a_dev), ptr(self.W_dev), ptr(self.b_dev),
                             None, None, None, None, None, None, None, None, None, None,
@@ -695,7 +737,8 @@ class GibbsEngine(object):
                             ptr(self.Jbuf), ptr(self.Mtab), ptr(self.Ac), ptr(self.hc), ptr(self.Tinv), ptr(self.G), ptr(self.Lws), ptr(self.Ut),
                             ptr(self.Wt_ws), ptr(self.d_idx), ptr(self.d_sign), ptr(self.d_cnt), ptr(self.batch_k), ptr(self.act), ptr(self.na),
                             ptr(i8[3]) if i8 else None, ptr(i8[4]) if i8 else None, ptr(i8[5]) if i8 else None,
-                            int(i8[6]) if i8 else 0, ptr(i8[7]) if i8 else None, ptr(i8[8]) if i8 else None, None, 0, 0, 0, 0, 0, 0, None)
+                            int(i8[6]) if i8 else 0, ptr(i8[7]) if i8 else None, ptr(i8[8]) if i8 else None, None, 0, 0, 0, 0, 0, 0, None,
+                            ptr(self.obs_param))
             self._sweep_cache = (sig, sw, dsets)
         sw = self._sweep_cache[1]
         if ovs:

@@ -121,8 +121,11 @@ class NonlinearAutoregressiveModel(object):
     @property
     def engine(self):
         if self._engine is None:
-            reg = self.regressions[0]
-            kw = dict(obs=getattr(reg, "_obs", "bernoulli") or "bernoulli", xi=getattr(reg, "xi", 1.0))
+            # the observation model of ALL the regressions (regression.device_obs), kept: a regression of another kind swapped in later
+            # is an error at the next sweep (_check_obs), not a silent run of the old model
+            self._engine_mode = _regression.device_obs(self.regressions)
+            obs, xi = self._engine_mode
+            kw = dict(obs=obs, xi=xi)
             kw.update(self._engine_kwargs)
             if self._engine_factory is not None:
                 self._engine = self._engine_factory(self.N, self.B, self.n0, self.n1, **kw)
@@ -168,7 +171,8 @@ class NonlinearAutoregressiveModel(object):
         T = data.shape[0]
         if X is not None:
             assert X.shape == (T, N, B)
-        ds = self.engine.add_data(data, X=X, basis=self.basis)
+        _regression.check_counts(self.regressions, data)
+        ds = self.engine.add_data(data, X=X, basis=self.basis, **self._obs_terms_kw(data))
         dist = _dist()
         if dist is not None and hasattr(self.engine, "drop_int8"):
             # gram="auto" looks at the free memory of ITS GPU: make the choice collective (integer path only if every rank can take it), so
@@ -181,6 +185,21 @@ class NonlinearAutoregressiveModel(object):
             if not int(t.item()):
                 self.engine.drop_int8(len(self.engine.datasets) - 1)
         self.data_list.append((_LazyX(self.engine, len(self.engine.datasets) - 1) if X is None else X, data))
+
+    def _obs_terms_kw(self, Y):
+        """engine.add_data's obs_terms for data Y (T, N) in hooks mode -- a(y), b(y), log c(y) of this rank's neurons -- else nothing"""
+        if self.engine_obs() != "hooks":
+            return {}
+        return dict(obs_terms=_regression.obs_terms(self.regressions[self.n0:self.n1], np.asarray(Y)[:, self.n0:self.n1]))
+
+    def _check_obs(self):
+        """the engine was built for one observation model: a regression swapped in since (model.regressions[n] = other) must not change it"""
+        if self._engine is None:
+            return
+        mode = _regression.device_obs(self.regressions)
+        if not _regression.same_obs(mode, self._engine_mode):
+            raise ValueError("the regressions now call for the device observation model %r (param %r), but this model's engine was built for %r "
+                             "(param %r): build a new model for the new regressions" % (mode[0], mode[1], self._engine_mode[0], self._engine_mode[1]))
 
     # ---- local <-> global state
     def _local_state(self):
@@ -352,28 +371,57 @@ class NonlinearAutoregressiveModel(object):
         cache = getattr(self, "_heldout_cache", None)
         if cache is None or cache[0] != key:
             self._heldout_cache = None
-            kw = dict(obs=self.engine_obs() or "bernoulli", xi=getattr(self.regressions[0], "xi", 1.0), likelihood_only=True)
+            obs, xi = self._engine_mode if self._engine is not None else _regression.device_obs(self.regressions)
+            kw = dict(obs=obs, xi=xi, likelihood_only=True)
             if self._engine_factory is not None:
                 eng = self._engine_factory(self.N, self.B, self.n0, self.n1, **kw)
             else:
                 eng = GibbsEngine(self.N, self.B, self.n0, self.n1, device=self.engine.dev, **kw)
             for X, Y in items:
-                eng.add_data(Y, X=X, basis=self.basis)
+                _regression.check_counts(self.regressions, Y)
+                eng.add_data(Y, X=X, basis=self.basis, **self._obs_terms_kw(Y))
             cache = self._heldout_cache = (key, eng)
         return cache[1]
 
     def engine_obs(self):
-        return getattr(self.regressions[0], "_obs", "bernoulli")
+        """the device observation model of the whole list of regressions (regression.device_obs): "bernoulli", "negbin", "gaussian",
+        "binomial" or "hooks" -- the one the engine was built with, once it is"""
+        mode = self._engine_mode if self._engine is not None else _regression.device_obs(self.regressions)
+        return mode[0]
 
     @property
     def means(self):
-        """(models.py:153-163) E[y | X] per dataset, (T, N)"""
+        """(models.py:153-163) E[y | X] per dataset, (T, N): per neuron, from its own observation model"""
         a, W, b = self._local_state()
+        mode = self._engine_mode if self._engine is not None else _regression.device_obs(self.regressions)
+        obs, par = mode
+        regs = self.regressions[self.n0:self.n1]
+        par_loc = np.asarray(par, dtype=np.float64)
+        if par_loc.ndim:
+            par_loc = par_loc[self.n0:self.n1]
         mus = []
         for i in range(len(self.data_list)):
             psi = self.engine.psi(a, W, b, i)
-            obs = self.engine_obs()
-            mu = logistic(psi) if obs == "bernoulli" else psi if obs == "gaussian" else self.regressions[0].xi * np.exp(psi)
+            if obs == "bernoulli":
+                mu = logistic(psi)
+            elif obs == "gaussian":
+                mu = psi
+            elif obs == "negbin":
+                mu = (par if par_loc.ndim == 0 else par_loc) * np.exp(psi)
+            elif obs == "binomial":
+                mu = par_loc * logistic(psi)
+            else:
+                # hooks: each regression's own mean -- from psi where it is a built-in one, else its mean(X) on the data set's design matrix
+                mu = np.empty_like(psi)
+                Xi = None
+                for j, r in enumerate(regs):
+                    f = None if "mean" in vars(r) else _MEAN_OF_PSI.get(type(r).mean)
+                    if f is not None:
+                        mu[:, j] = f(r, psi[:, j])
+                    else:
+                        if Xi is None:
+                            Xi = np.asarray(self.data_list[i][0])
+                        mu[:, j] = r.mean(Xi)
             mus.append(self._gather_rows(np.ascontiguousarray(mu.T)).T)
         return mus
 
@@ -471,6 +519,7 @@ class NonlinearAutoregressiveModel(object):
         """(models.py:169-171) all local neurons through the GPU engine, then ONE all_gather of the new rows (packed on the device and
         launched behind the sweep on its stream; the host draws the next sweep's random inputs meanwhile)."""
         from .engine import make_draws
+        self._check_obs()
         regs = self.regressions[self.n0:self.n1]
         a, W, b, rho, Jw, hw, Jb, hb, c0, perm, u, z = self._sweep_inputs()
         self._draws_ahead = None
@@ -589,6 +638,12 @@ class NonlinearAutoregressiveModel(object):
 
     def plot(self, *args, **kwargs):
         raise NotImplementedError("plotting is outside the scope of the MI355X hot path (SURVEY.md section 2, row 8)")
+
+
+# E[y | psi] of the built-in Polya-gamma regressions, for means() in hooks mode (a regression whose `mean` is one of these)
+_MEAN_OF_PSI = {_regression.SparseBernoulliRegression.mean: lambda r, psi: logistic(psi),
+                _regression.SparseNegativeBinomialRegression.mean: lambda r, psi: r.xi * np.exp(psi),
+                _regression.SparseBinomialRegression.mean: lambda r, psi: r.n * logistic(psi)}
 
 
 class _LazyX(object):
@@ -785,3 +840,13 @@ class NegativeBinomialGLM(_DefaultMixin, NetworkGLM):
 class SparseNegativeBinomialGLM(_DefaultMixin, NetworkGLM):
     _network_class = _networks.NIWSparseNetwork
     _regression_class = _regression.SparseNegativeBinomialRegression
+
+
+class BinomialGLM(_DefaultMixin, NetworkGLM):
+    _network_class = _networks.NIWDenseNetwork
+    _regression_class = _regression.BinomialRegression
+
+
+class SparseBinomialGLM(_DefaultMixin, NetworkGLM):
+    _network_class = _networks.NIWSparseNetwork
+    _regression_class = _regression.SparseBinomialRegression

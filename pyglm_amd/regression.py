@@ -193,17 +193,27 @@ class _SparseScalarRegressionBase(object):
         Activation / mean / log-likelihood calls use a likelihood-only engine keyed by X alone (no sweep buffers, y irrelevant)."""
         from .engine import GibbsEngine
         flat = [self.extract_data((X, y)) for X, y in datas]
+        # the regression's own observation model (device_obs of a one-element list); an activation-only engine reads psi alone, so a
+        # hooks model takes the Bernoulli pass there (no hook arrays to keep)
+        obs, xi = device_obs([self])
+        if likelihood_only and obs == "hooks":
+            obs, xi = "bernoulli", 1.0
         key = (bool(likelihood_only),) + tuple((fingerprint(X), None if likelihood_only else fingerprint(y)) for X, y in flat)
         slot = "_lik_engine_cache" if likelihood_only else "_engine_cache"
         cache = getattr(self, slot, None)
         if cache is None or cache[0] != key:
             setattr(self, slot, None)              # release the previous engine's device memory before allocating the next
-            eng = GibbsEngine(self.N, self.B, 0, 1, obs=self._obs, xi=getattr(self, "xi", 1.0), batch=1, likelihood_only=likelihood_only)
+            Ys, terms = [], []
             for X, y in flat:
                 Y = np.zeros((X.shape[0], self.N))
                 if not likelihood_only:
                     Y[:, 0] = np.asarray(y, dtype=float).ravel()
-                eng.add_data(Y, X=np.asarray(X, dtype=float).reshape(-1, self.N, self.B))
+                    check_counts([self], Y[:, :1])
+                Ys.append(Y)
+                terms.append(dict(obs_terms=obs_terms([self], Y[:, :1])) if obs == "hooks" else {})
+            eng = GibbsEngine(self.N, self.B, 0, 1, obs=obs, xi=xi, batch=1, likelihood_only=likelihood_only)
+            for (X, _), Y, kw in zip(flat, Ys, terms):
+                eng.add_data(Y, X=np.asarray(X, dtype=float).reshape(-1, self.N, self.B), **kw)
             cache = (key, eng)
             setattr(self, slot, cache)
         return cache[1]
@@ -403,3 +413,134 @@ class NegativeBinomialRegression(SparseNegativeBinomialRegression):
     def __init__(self, N, B, **kwargs):
         kwargs["rho"] = np.ones(N)
         super(NegativeBinomialRegression, self).__init__(N, B, **kwargs)
+
+
+class SparseBinomialRegression(_SparsePGRegressionBase):
+    """named in the reference docstring (:463-466) but not implemented there; defined through the hooks (:479-489):
+    y ~ Binomial(n, sigma(psi)):  a = y, b = n, c = C(n, y)."""
+    _obs = "binomial"
+
+    def __init__(self, N, B, n=1, **kwargs):
+        if not (np.isscalar(n) and n >= 0 and float(n) == int(n)):
+            raise ValueError("binomial: the number of trials n must be an integer >= 0, got %r" % (n,))
+        self.n = int(n)
+        super(SparseBinomialRegression, self).__init__(N, B, **kwargs)
+
+    def a_func(self, data):
+        return data
+
+    def b_func(self, data):
+        return self.n * np.ones_like(data, dtype=float)
+
+    def c_func(self, data):
+        from scipy.special import gammaln
+        return np.exp(gammaln(self.n + 1) - gammaln(data + 1) - gammaln(self.n - data + 1))
+
+    def check_data(self, y):
+        """counts must be integers in [0, n]: anything else has zero probability, and the log-likelihood would be -inf or NaN"""
+        y = np.asarray(y, dtype=float)
+        if not np.all((y >= 0) & (y <= self.n) & (y == np.floor(y))):
+            raise ValueError("binomial observations must be integers in [0, n = %d]" % self.n)
+
+    def mean(self, X):
+        return self.n * logistic(self.activation(X))
+
+    def rvs(self, X=None, size=[], psi=None):
+        if psi is None:
+            if X is None:
+                assert isinstance(size, int)
+                X = npr.randn(size, self.N * self.B)
+            psi = self.activation(self._flatten_X(X))
+        return npr.binomial(self.n, logistic(psi)).astype(float)
+
+
+class BinomialRegression(SparseBinomialRegression):
+    """dense weights: rho = 1"""
+
+    def __init__(self, N, B, **kwargs):
+        kwargs["rho"] = np.ones(N)
+        super(BinomialRegression, self).__init__(N, B, **kwargs)
+
+
+# ---------------------------------------------------------------------------------------------------- the device's observation model
+_HOOKS = ("a_func", "b_func", "c_func")
+_BUILTIN = {"bernoulli": (SparseBernoulliRegression, None), "negbin": (SparseNegativeBinomialRegression, "xi"),
+            "binomial": (SparseBinomialRegression, "n")}
+_class_kind = {}
+
+
+def _kind(reg):
+    """"gaussian", a built-in PG model's name, or "hooks" for any other Polya-gamma regression; raises for a type the device cannot run"""
+    cls = type(reg)
+    kind = _class_kind.get(cls)
+    if kind is None:
+        if issubclass(cls, SparseGaussianRegression):
+            kind = "gaussian"
+        elif issubclass(cls, _SparsePGRegressionBase):
+            kind = "hooks"
+            b = _BUILTIN.get(getattr(cls, "_obs", None))
+            # built in: an instance of the class that defines the model, with every hook the one that class defines (the same test as
+            # _generate_obs makes for rvs)
+            if b is not None and issubclass(cls, b[0]) and all(getattr(cls, h, None) is getattr(b[0], h) for h in _HOOKS):
+                kind = cls._obs
+        else:
+            raise TypeError("%s: the device runs Gaussian regressions and subclasses of _SparsePGRegressionBase (a_func / b_func / c_func)"
+                            % cls.__name__)
+        _class_kind[cls] = kind
+    if kind not in ("gaussian", "hooks"):
+        d = reg.__dict__
+        if "a_func" in d or "b_func" in d or "c_func" in d:       # a hook set on the instance
+            return "hooks"
+    return kind
+
+
+def device_obs(regressions):
+    """-> (obs, param): the observation model the device runs for ALL of `regressions` (a model's list, or [reg] for a stand-alone one).
+    Built-in Bernoulli: ("bernoulli", 1.0).  Built-in negative binomial: ("negbin", xi) -- a scalar when every xi is equal, else one per
+    regression.  Built-in binomial: ("binomial", n), likewise.  Gaussian: ("gaussian", 1.0).  Any other mix of Polya-gamma regressions, or a
+    hook overridden in a class or on an instance: ("hooks", 1.0) -- their a/b/c are evaluated on the host (obs_terms).  Gaussian mixed with
+    a Polya-gamma model raises ValueError; a regression type the device cannot run raises TypeError."""
+    kinds = set(_kind(r) for r in regressions)
+    if "gaussian" in kinds:
+        if len(kinds) > 1:
+            raise ValueError("a Gaussian regression cannot share a model with Polya-gamma regressions (%s)" % sorted(kinds))
+        return "gaussian", 1.0
+    if len(kinds) != 1 or "hooks" in kinds:
+        return "hooks", 1.0
+    kind = kinds.pop()
+    attr = _BUILTIN[kind][1]
+    if attr is None:
+        return kind, 1.0
+    vals = np.array([float(getattr(r, attr)) for r in regressions])
+    return kind, (float(vals[0]) if np.all(vals == vals[0]) else vals)
+
+
+def same_obs(m1, m2):
+    """two device_obs results describe the same device model"""
+    p1, p2 = np.asarray(m1[1], dtype=float), np.asarray(m2[1], dtype=float)
+    return m1[0] == m2[0] and (p1.ndim == 0 or p2.ndim == 0 or p1.shape == p2.shape) and bool(np.all(p1 == p2))
+
+
+def check_counts(regressions, Y):
+    """ValueError unless every column of Y (T, len(regressions)) is a valid observation for its regression (those with check_data)"""
+    for j, r in enumerate(regressions):
+        chk = getattr(r, "check_data", None)
+        if chk is not None:
+            chk(Y[:, j])
+
+
+def obs_terms(regressions, Y):
+    """(A, Bv, logC): a(y), b(y), log c(y) of each regression on its column of Y (T, len(regressions)), broadcast to (T, len) -- the hooks
+    mode's data, the same expressions as the reference's log_likelihood (regression.py:491-494).  Raises unless all are finite and b >= 0."""
+    Y = np.asarray(Y, dtype=np.float64)
+    T, n = Y.shape
+    out = [np.empty((T, n)) for _ in range(3)]
+    for j, r in enumerate(regressions):
+        y = Y[:, j]
+        out[0][:, j] = np.broadcast_to(np.asarray(r.a_func(y), dtype=np.float64), (T,))
+        out[1][:, j] = np.broadcast_to(np.asarray(r.b_func(y), dtype=np.float64), (T,))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out[2][:, j] = np.broadcast_to(np.log(np.asarray(r.c_func(y), dtype=np.float64)), (T,))
+        if not all(np.all(np.isfinite(v[:, j])) for v in out) or not np.all(out[1][:, j] >= 0):
+            raise ValueError("regression %d (%s): a(y), b(y) and log c(y) must be finite and b(y) >= 0 on its data" % (j, type(r).__name__))
+    return tuple(out)
