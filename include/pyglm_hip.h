@@ -320,6 +320,12 @@ int pgl_sweep_dims(int N, int B, int nloc, int* Dp, int* ldn, int* ldj);
  * exchange these 1 + B + B^2 doubles per neuron with their rows, so that no rank walks the N^2 B doubles of the gathered state. */
 int pgl_row_stats(const int* a, const double* W, double* out, int N, int B, int nloc, int n0, void* hip_stream);
 int pgl_sweep(const pgl_sweep_t* s, uint64_t seed, uint64_t sweep, void* hip_stream);
+/* The likelihood Gram stage of pgl_sweep on its own (tests, probes): X' diag(omega_n) X of the local neurons [first, first + count) into
+ * Jbuf[0 .. count), by the same launches as a sweep's batch that starts at `first` (the Gaussian model's scaled X'X; the fp64 MFMA kernel,
+ * split in time at D <= 512; or the integer Gram with its scales, time slices, planes, products and CRT), from the omega in each data set's OK
+ * -- a sweep's, or written there by the caller.  Checks only the fields the Gram reads; count <= nb, first + count <= nloc.  Stage timing
+ * through s->times as in a sweep. */
+int pgl_sweep_gram(const pgl_sweep_t* s, int first, int count, void* hip_stream);
 /* copies the shard's state to host buffers (any may be NULL) and waits for the stream: a [nloc][N], W [nloc][D], b, ll, status [nloc].
  * The read-backs of pyglm/models.py:54-64 (weights / adjacency / biases) for a non-Python binder. */
 int pgl_get_state(const pgl_sweep_t* s, int* a_host, double* W_host, double* b_host, double* ll_host, int* status_host, void* hip_stream);

@@ -90,6 +90,7 @@ SIGNATURES = {
     "pgl_row_stats": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
     "pgl_sweep_dims": [c_i, c_i, c_i, ctypes.POINTER(c_i), ctypes.POINTER(c_i), ctypes.POINTER(c_i)],
     "pgl_sweep": [ctypes.POINTER(Sweep), c_u64, c_u64, c_p],
+    "pgl_sweep_gram": [ctypes.POINTER(Sweep), c_i, c_i, c_p],
     "pgl_get_state": [ctypes.POINTER(Sweep), c_p, c_p, c_p, c_p, c_p, c_p],
     "pgl_stage_name": [c_i],
     "pgl_stage_times_collect": [ctypes.POINTER(StageTimes)],

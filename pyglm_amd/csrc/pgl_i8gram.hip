@@ -859,7 +859,6 @@ int pgl_k_i8_colstats(const double* X, long ldx, const double* Om, long ldo, int
 // chunks), so the scales do not depend on launch timing; they can differ from pgl_k_i8_colstats + pgl_k_i8_scales in the last bit of a norm,
 // i.e. only for a column whose norm sits on a power-of-two boundary.
 constexpr int CS_NCH = 4;
-size_t pgl_k_i8_stats_scratch_doubles(int D, int G) { return (size_t)2 * CS_NCH * G * D; }
 int pgl_k_i8_colstats_scales(const double* X, long ldx, const double* Om, long ldo, int T, int D, int G, int nplanes, double* scratch, double* scale,
                              hipStream_t st) {
     if (G > CS_G || G < 1 || !Om) { pgl_set_error("i8 colstats+scales: %d weight columns per call (max %d)", G, CS_G); return PGL_ERR_ARG; }

@@ -98,6 +98,139 @@ inline int r_up(long x, int m) { return (int)((x + m - 1) / m * m); }
 
 #define RC(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
 
+// the fields the likelihood Gram reads (G: the scratch of the split fp64 kernel); pgl_sweep checks these and the rest
+int check_gram_args(const pgl_sweep_t* s) {
+    PGL_CHECK_ARG(s && s->N > 0 && s->B > 0 && s->nloc > 0 && s->nb > 0 && s->ndatasets > 0 && s->datasets && s->Jbuf && s->G);
+    PGL_CHECK_ARG(s->obs >= 0 && s->obs <= 4 && (s->obs != 2 || (s->inv_eta && s->G0)) && s->i8_slice >= 0 && s->i8_slice % 64 == 0);
+    bool any_i8 = false;
+    for (int i = 0; i < s->ndatasets; ++i) {
+        const pgl_dataset_t& d = s->datasets[i];
+        PGL_CHECK_ARG(d.T > 0 && d.Tp >= d.T && d.Tp % 16 == 0 && d.X && d.Xt && d.OK);
+        PGL_CHECK_ARG(!d.int8 || (d.sA && (d.PA || s->i8_PAs) && (d.planes > 0 || s->planes > 0)));      // (no resident X planes: converted per slice -- or once per group for the whole data set -- into i8_PAs)
+        any_i8 = any_i8 || d.int8;
+    }
+    PGL_CHECK_ARG(!any_i8 || (s->i8_PB && s->i8_R && s->i8_stat && s->i8_group >= 1 && s->i8_group <= PGL_I8_MAX_GROUP && s->obs != 2));
+    return PGL_OK;
+}
+
+// A long sum over time as S partial sums: q.K rows cut into S slices of a multiple of 16 rows, one batch of the contraction each, whose sums go
+// to `scratch` (q.strideC doubles apart); the last rem < 16 S rows go onto the first slice's sums, and sum_slices_kernel adds the slices up in
+// slice order into out (q.N columns of q.ldc).  The order of the additions follows from q.K and S alone
+int sliced_sum(PglGemmKind kind, PglGemmArgs q, long S, double* scratch, double* out, int accumulate, hipStream_t st) {
+    const int chunk = (int)(q.K / 16 / S) * 16, rem = q.K - (int)S * chunk;
+    q.strideA = (long)chunk * q.lda; q.strideB = (long)chunk * q.ldb; q.C = scratch; q.K = chunk; q.nbatch = (int)S;
+    RC(pgl_launch_gemm(kind, q, st));
+    if (rem > 0) {
+        q.A += (long)S * chunk * q.lda; q.B += (long)S * chunk * q.ldb; q.K = rem; q.nbatch = 1; q.beta = 1.0;
+        RC(pgl_launch_gemm(kind, q, st));
+    }
+    hipLaunchKernelGGL(sum_slices_kernel, dim3((unsigned)((q.strideC + 255) / 256)), dim3(256), 0, st, scratch, q.strideC, (int)S, out, accumulate,
+                       (int)q.ldc, q.N);
+    PGL_CHECK_LAUNCH();
+    return PGL_OK;
+}
+
+// ---- likelihood Gram of the neurons [s0, s0 + nbb) into Jbuf[0, nbb)  (regression.py:251-252): a batch of pgl_sweep, or pgl_sweep_gram
+int gram_batch(const pgl_sweep_t& s, int s0, int nbb, Clock& clk, hipStream_t st) {
+    const long D = (long)s.N * s.B;
+    const int Dp = r_up(D + 1, 16), ldn = r_up(s.nloc, 2), ldj = r_up(D + 2, 16);
+    const long strideJ = (long)ldj * ldj;
+    const int kmax = pgl_k_flip_kmax();
+    if (s.obs == 2) {
+        auto m = clk.tic(ST_GSCALE, 8.0 * nbb * D * (D + 1) / 2);
+        RC(pgl_k_scaled_gram(s.G0, ldj, s.inv_eta + s0, s.Jbuf, ldj, strideJ, (int)D, nbb, st));
+        clk.toc(m);
+        return PGL_OK;
+    }
+    for (int i = 0; i < s.ndatasets; ++i) {
+        const pgl_dataset_t& d = s.datasets[i];
+        if (!d.int8) {
+            auto m = clk.tic(ST_GRAM, (double)nbb * d.T * D * (D + 1));
+            // A small model (a few 128 x 128 tiles per neuron) with a long recording is a handful of workgroups each walking all of T --
+            // BASELINE configs[0]: 4 items, 1.2 of the sweep's 2 ms.  Then T is cut into up to 64 slices of >= 256 bins, one work item
+            // each, whose sums land in the flips' (idle) pivot-block buffer G ([nb][kmax][kmax]: kmax^2 / ldj^2 slices per neuron --
+            // 1024 at D = 4, 12 at D = 128, 1 from D = 350) and are added in slice order.  The number of slices follows from T and D
+            // alone -- not from the number of neurons -- so a shard gets the bits of the whole.
+            long S = d.Tp / 256;
+            if (S > (long)kmax * kmax / ((long)ldj * ldj)) S = (long)kmax * kmax / ((long)ldj * ldj);
+            if (S > 64) S = 64;
+            if (D <= 512 && S >= 2) {
+                const long ks = r_up((d.Tp + S - 1) / S, 16);
+                RC(pgl_gram_split(d.X, Dp, Dp, d.OK + s0, 2 * ldn, d.Tp, (int)D, nbb, s.Jbuf, ldj, strideJ, i > 0, ks, s.G, (long)kmax * kmax, st));
+            } else RC(pgl_weighted_gram(d.X, Dp, Dp, d.OK + s0, 2 * ldn, d.Tp, (int)D, nbb, s.Jbuf, ldj, strideJ, i > 0, st));
+            clk.toc(m);
+            continue;
+        }
+        const int G = s.i8_group, np = d.planes > 0 ? d.planes : s.planes;
+        double* sB = s.i8_stat + 2L * G * D;               // [G][D] scales of omega_g X (the last third of i8_stat)
+        // The scales of omega_n X need the norm of each of its columns.  With d.xmax and s.i8_norm those come for the WHOLE batch from one
+        // fp64 MFMA contraction of the squared operands, ss[n][j] = sum_t omega_nt^2 x_tj^2 -- X is read once per batch instead of once
+        // per group of 8 neurons (215 ms of column-statistics passes per sweep at BASELINE configs[2]) --, T cut into slices whose partial
+        // sums borrow the (idle) residue buffer and are added in slice order, like the border sums.
+        const bool batch_norms = d.xmax && s.i8_norm && s0 % 2 == 0;
+        const long part = (long)r_up(s.nb, 2) * Dp;
+        double* ssb = s.i8_norm;                           // [nb rounded up to even][Dp] sums of squares of this batch's columns
+        double* ommax = s.i8_norm + part;                  // [nloc] largest omega of every local neuron
+        if (batch_norms) {
+            auto m = clk.tic(ST_STATS, 8.0 * d.T * D);
+            RC(pgl_k_i8_colmax(d.OK + s0, 2 * ldn, d.T, nbb, ommax + s0, st));
+            const int Mp = r_up(nbb, 2);
+            const size_t r_bytes = (size_t)(G < nbb ? G : nbb) * np * pgl_k_i8_padded_rows((int)D) * pgl_k_i8_padded_rows((int)D);
+            long S = 64;                                   // (from T alone, like the border sums: the same norms -- hence scales -- whatever the shard)
+            if (S > d.Tp / 256) S = d.Tp / 256;
+            if (S > (long)(r_bytes / sizeof(double)) / part) S = (long)(r_bytes / sizeof(double)) / part;
+            PglGemmArgs q{};
+            q.A = d.OK + s0; q.lda = 2 * ldn; q.a_cols = Mp;
+            q.B = d.X; q.ldb = Dp; q.b_cols = Dp;
+            q.M = Mp; q.N = (int)D; q.K = d.Tp; q.alpha = 1.0; q.beta = 0.0; q.tri = 0; q.ldc = Dp;
+            if (S >= 2) {
+                q.strideC = part;
+                RC(sliced_sum(PGL_GEMM_SQUARES, q, S, reinterpret_cast<double*>(s.i8_R), ssb, 0, st));
+            } else {
+                q.C = ssb; q.nbatch = 1;
+                RC(pgl_launch_gemm(PGL_GEMM_SQUARES, q, st));
+            }
+            clk.toc(m);
+        }
+        for (int g0 = 0; g0 < nbb; g0 += G) {
+            const int gz = G < nbb - g0 ? G : nbb - g0;
+            const double* om = d.OK + s0 + g0;
+            auto m = clk.tic(ST_STATS, batch_norms ? 0.0 : 8.0 * d.T * D);
+            if (batch_norms) {
+                RC(pgl_k_i8_scales_bound(ssb + (long)g0 * Dp, Dp, ommax + s0 + g0, d.xmax, (int)D, gz, d.T, np, sB, st));
+            } else {
+                // one pass over X per 8 neurons, whose per-chunk partials borrow the residue buffer (the previous group's CRT has read it, this
+                // group's products have not written it yet): their 64 cz D bytes always fit in its gz np Dq^2 (cz <= gz, np >= 1, Dq >= max(D, 320))
+                for (int c0 = 0; c0 < gz; c0 += 8) {
+                    const int cz = 8 < gz - c0 ? 8 : gz - c0;
+                    RC(pgl_k_i8_colstats_scales(d.X, Dp, om + c0, 2 * ldn, d.T, (int)D, cz, np, reinterpret_cast<double*>(s.i8_R), sB + (long)c0 * D, st));
+                }
+            }
+            clk.toc(m);
+            // time slices (BASELINE configs[4]: one neuron's planes are 86 GB): the integer Gram is a sum over time, so the
+            // slices' products add up in the residues; a data set without resident X planes converts those per slice too
+            const int slice = s.i8_slice > 0 && s.i8_slice < d.T ? s.i8_slice : d.T;
+            for (int t0 = 0; t0 < d.T; t0 += slice) {
+                const int ts = slice < d.T - t0 ? slice : d.T - t0;
+                m = clk.tic(ST_PLANES, (double)np * (gz + (d.PA ? 0 : 1)) * ts * D);
+                if (!d.PA) RC(pgl_k_i8_planes(d.Xt + t0, d.Tp, 1, nullptr, 0, d.sA, static_cast<int8_t*>(s.i8_PAs), ts, (int)D, 1, np, t0, st));
+                RC(pgl_k_i8_planes(d.Xt + t0, d.Tp, 1, om + (long)t0 * 2 * ldn, 2 * ldn, sB, static_cast<int8_t*>(s.i8_PB), ts, (int)D, gz, np, t0, st));   // (coalesced rows of Xt)
+                clk.toc(m);
+                m = clk.tic(ST_I8, (double)gz * ts * D * (D + 1));
+                if (d.PA) RC(pgl_k_i8_gram(static_cast<const int8_t*>(d.PA), pgl_k_i8_kp(d.T), t0 / 64, static_cast<const int8_t*>(s.i8_PB),
+                                           static_cast<int8_t*>(s.i8_R), static_cast<int8_t*>(s.i8_Rx), ts, (int)D, gz, np, t0 > 0, st));
+                else RC(pgl_k_i8_gram(static_cast<const int8_t*>(s.i8_PAs), 0, 0, static_cast<const int8_t*>(s.i8_PB), static_cast<int8_t*>(s.i8_R),
+                                      static_cast<int8_t*>(s.i8_Rx), ts, (int)D, gz, np, t0 > 0, st));
+                clk.toc(m);
+            }
+            m = clk.tic(ST_CRT, (double)np * gz * D * (D + 1) / 2);
+            RC(pgl_k_i8_crt(static_cast<const int8_t*>(s.i8_R), static_cast<const int8_t*>(s.i8_Rx), d.sA, sB, s.Jbuf + (long)g0 * strideJ, ldj, strideJ, (int)D, gz, np, i > 0, st));
+            clk.toc(m);
+        }
+    }
+    return PGL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -133,14 +266,16 @@ int pgl_stage_times_collect(pgl_stage_times_t* t) {
 
 int pgl_sweep(const pgl_sweep_t* s, uint64_t seed, uint64_t sweep, void* hip_stream) {
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    PGL_CHECK_ARG(s && s->N > 0 && s->B > 0 && s->B <= 32 && s->nloc > 0 && s->nb > 0 && s->n0 >= 0 && s->ndatasets > 0 && s->datasets);
-    PGL_CHECK_ARG(s->obs >= 0 && s->obs <= 4 && (s->obs_param != nullptr || s->obs != 1 || s->xi > 0) && (s->obs_param != nullptr || s->obs != 3 || s->xi >= 0));
+    RC(check_gram_args(s));
+    PGL_CHECK_ARG(s->B <= 32 && s->n0 >= 0 && (s->obs_param != nullptr || s->obs != 1 || s->xi > 0) && (s->obs_param != nullptr || s->obs != 3 || s->xi >= 0));
     PGL_CHECK_ARG(s->a && s->W && s->b && s->rho && s->Jw && s->hw && s->Jb && s->hb && s->c0 && s->perm && s->u && s->z && s->ll && s->status);
-    PGL_CHECK_ARG(s->Wt && s->bias && s->border && s->skip && s->Jbuf && s->Mtab && s->Ac && s->hc && s->Tinv && s->G && s->Lws && s->Ut && s->Wt_ws);
+    PGL_CHECK_ARG(s->Wt && s->bias && s->border && s->skip && s->Mtab && s->Ac && s->hc && s->Tinv && s->Lws && s->Ut && s->Wt_ws);
     PGL_CHECK_ARG(s->d_idx && s->d_sign && s->d_cnt && s->batch_k && s->act && s->na && (s->label == nullptr || s->c0_dense != nullptr));
-    PGL_CHECK_ARG(s->obs != 2 || (s->inv_eta && s->G0));
     PGL_CHECK_ARG(s->nrun >= 0 && s->nfirst >= 0 && s->nfirst % 2 == 0 && s->nfirst + s->nrun <= s->nloc && (s->nrun > 0 || s->nfirst == 0));
-    PGL_CHECK_ARG(s->i8_slice >= 0 && s->i8_slice % 64 == 0);
+    for (int i = 0; i < s->ndatasets; ++i) {
+        const pgl_dataset_t& d = s->datasets[i];
+        PGL_CHECK_ARG(d.Y && d.Psi && d.llpart && (s->obs != 4 || d.hooks));
+    }
     const int N = s->N, B = s->B, nloc = s->nloc;
     const int nrun = s->nrun > 0 ? s->nrun : nloc;        // neurons actually swept: [nf, nf + nrun) of the shard (the array layouts stay the shard's)
     const int nf = s->nfirst;
@@ -151,15 +286,6 @@ int pgl_sweep(const pgl_sweep_t* s, uint64_t seed, uint64_t sweep, void* hip_str
     const int R = pgl_k_flip_window_blocks(B);
     const int kmax = pgl_k_flip_kmax();
     if (R < 1) { pgl_set_error("B=%d too large for the proposal window", B); return PGL_ERR_ARG; }
-    bool any_i8 = false;
-    for (int i = 0; i < s->ndatasets; ++i) {
-        const pgl_dataset_t& d = s->datasets[i];
-        PGL_CHECK_ARG(d.T > 0 && d.Tp >= d.T && d.Tp % 16 == 0 && d.X && d.Xt && d.Y && d.Psi && d.OK && d.llpart);
-        PGL_CHECK_ARG(s->obs != 4 || d.hooks);
-        PGL_CHECK_ARG(!d.int8 || (d.sA && (d.PA || s->i8_PAs) && (d.planes > 0 || s->planes > 0)));      // (no resident X planes: converted per slice -- or once per group for the whole data set -- into i8_PAs)
-        any_i8 = any_i8 || d.int8;
-    }
-    PGL_CHECK_ARG(!any_i8 || (s->i8_PB && s->i8_R && s->i8_stat && s->i8_group >= 1 && s->i8_group <= PGL_I8_MAX_GROUP && s->obs != 2));
     Clock clk{s->times, st};
 
     // ---- activation of the whole shard, PG draw / kappa / log-likelihood (regression.py:195-201, 491-511)
@@ -225,7 +351,6 @@ int pgl_sweep(const pgl_sweep_t* s, uint64_t seed, uint64_t sweep, void* hip_str
         // (cap_any) --, each neuron's sums still added in the same slice order (S used to be clamped by this shard's capacity, which
         // made the last bits depend on the batch size)
         if (S >= 2) {
-            const int chunk = (int)(d.Tp / 16 / S) * 16, rem = d.Tp - (int)S * chunk;
             long cols_fit = scratch_doubles / (S * Dp) / 2 * 2;                  // border rows (neuron columns of Omega or of Kappa) whose S slices fit
             const bool whole = npieces == 1 && cols_fit >= 2L * ldn;            // the usual case: [Omega | Kappa] of the whole shard as one product
             const int cols = nrun < nloc ? r_up(nrun, 2) : ldn;                 // columns of Omega (and of Kappa) to contract
@@ -234,22 +359,13 @@ int pgl_sweep(const pgl_sweep_t* s, uint64_t seed, uint64_t sweep, void* hip_str
                 const int first = whole ? 0 : nf, count = whole ? 2 * ldn : cols;
                 for (int c0 = 0; c0 < count; c0 += ngroups_cols) {
                     const int mcols = ngroups_cols < count - c0 ? ngroups_cols : count - c0;
-                    const double* Ap = d.OK + (long)piece * ldn + first + c0;                    // columns of Omega, then of Kappa
-                    const long crow = ((long)piece * ldn + first + c0) * Dp;                     // rows of the border: omega sums, then kappa sums
-                    const long partg = (long)mcols * Dp;
                     PglGemmArgs a{};
-                    a.A = Ap; a.lda = 2 * ldn; a.strideA = (long)chunk * a.lda; a.a_cols = mcols;
-                    a.B = d.X; a.ldb = Dp; a.strideB = (long)chunk * Dp; a.b_cols = Dp;
-                    a.C = scratch; a.ldc = Dp; a.strideC = partg;
-                    a.M = mcols; a.N = (int)D + 1; a.K = chunk; a.nbatch = (int)S; a.alpha = 1.0; a.beta = 0.0; a.tri = 0;
-                    RC(pgl_launch_gemm(PGL_GEMM_PLAIN, a, st));
-                    if (rem > 0) {           // the last rem < 16 S rows: onto the first slice's sums
-                        a.A = Ap + (long)S * chunk * a.lda; a.B = d.X + (long)S * chunk * Dp; a.K = rem; a.nbatch = 1; a.beta = 1.0;
-                        RC(pgl_launch_gemm(PGL_GEMM_PLAIN, a, st));
-                    }
-                    hipLaunchKernelGGL(sum_slices_kernel, dim3((unsigned)((partg + 255) / 256)), dim3(256), 0, st, scratch, partg, (int)S, s->border + crow, i > 0, Dp,
-                                       (int)D + 1);
-                    PGL_CHECK_LAUNCH();
+                    a.A = d.OK + (long)piece * ldn + first + c0; a.lda = 2 * ldn; a.a_cols = mcols;          // columns of Omega, then of Kappa
+                    a.B = d.X; a.ldb = Dp; a.b_cols = Dp;
+                    a.ldc = Dp; a.strideC = (long)mcols * Dp;
+                    a.M = mcols; a.N = (int)D + 1; a.K = d.Tp; a.alpha = 1.0; a.beta = 0.0; a.tri = 0;
+                    // (rows of the border: omega sums, then kappa sums)
+                    RC(sliced_sum(PGL_GEMM_PLAIN, a, S, scratch, s->border + ((long)piece * ldn + first + c0) * Dp, i > 0, st));
                 }
             }
         } else {
@@ -279,114 +395,7 @@ int pgl_sweep(const pgl_sweep_t* s, uint64_t seed, uint64_t sweep, void* hip_str
     for (int s0 = nf; s0 < nf + nrun; s0 += nb) {
         const int nbb = nb < nf + nrun - s0 ? nb : nf + nrun - s0;
         // ---- likelihood Gram of neurons [s0, s0 + nbb)  (regression.py:251-252)
-        if (s->obs == 2) {
-            auto m = clk.tic(ST_GSCALE, 8.0 * nbb * D * (D + 1) / 2);
-            RC(pgl_k_scaled_gram(s->G0, ldj, s->inv_eta + s0, s->Jbuf, ldj, strideJ, (int)D, nbb, st));
-            clk.toc(m);
-        } else {
-            for (int i = 0; i < s->ndatasets; ++i) {
-                const pgl_dataset_t& d = s->datasets[i];
-                if (!d.int8) {
-                    auto m = clk.tic(ST_GRAM, (double)nbb * d.T * D * (D + 1));
-                    // A small model (a few 128 x 128 tiles per neuron) with a long recording is a handful of workgroups each walking all of T --
-                    // BASELINE configs[0]: 4 items, 1.2 of the sweep's 2 ms.  Then T is cut into up to 64 slices of >= 256 bins, one work item
-                    // each, whose sums land in the flips' (idle) pivot-block buffer G ([nb][kmax][kmax]: kmax^2 / ldj^2 slices per neuron --
-                    // 1024 at D = 4, 12 at D = 128, 1 from D = 350) and are added in slice order.  The number of slices follows from T and D
-                    // alone -- not from the number of neurons -- so a shard gets the bits of the whole.
-                    long S = d.Tp / 256;
-                    if (S > (long)kmax * kmax / ((long)ldj * ldj)) S = (long)kmax * kmax / ((long)ldj * ldj);
-                    if (S > 64) S = 64;
-                    if (D <= 512 && S >= 2) {
-                        const long ks = r_up((d.Tp + S - 1) / S, 16);
-                        RC(pgl_gram_split(d.X, Dp, Dp, d.OK + s0, 2 * ldn, d.Tp, (int)D, nbb, s->Jbuf, ldj, strideJ, i > 0, ks, s->G, (long)kmax * kmax, st));
-                    } else RC(pgl_weighted_gram(d.X, Dp, Dp, d.OK + s0, 2 * ldn, d.Tp, (int)D, nbb, s->Jbuf, ldj, strideJ, i > 0, st));
-                    clk.toc(m);
-                    continue;
-                }
-                const int G = s->i8_group, np = d.planes > 0 ? d.planes : s->planes;
-                double* amax = s->i8_stat;
-                double* ss = s->i8_stat + (long)G * D;
-                double* sB = s->i8_stat + 2L * G * D;
-                // The scales of omega_n X need the norm of each of its columns.  With d.xmax and s->i8_norm those come for the WHOLE batch from one
-                // fp64 MFMA contraction of the squared operands, ss[n][j] = sum_t omega_nt^2 x_tj^2 -- X is read once per batch instead of once
-                // per group of 8 neurons (215 ms of column-statistics passes per sweep at BASELINE configs[2]) --, T cut into slices whose partial
-                // sums borrow the (idle) residue buffer and are added in slice order, like the border sums above.
-                const bool batch_norms = d.xmax && s->i8_norm && s0 % 2 == 0;
-                const long part = (long)r_up(s->nb, 2) * Dp;
-                double* ssb = s->i8_norm;                          // [nb rounded up to even][Dp] sums of squares of this batch's columns
-                double* ommax = s->i8_norm + part;                 // [nloc] largest omega of every local neuron
-                if (batch_norms) {
-                    auto m = clk.tic(ST_STATS, 8.0 * d.T * D);
-                    RC(pgl_k_i8_colmax(d.OK + s0, 2 * ldn, d.T, nbb, ommax + s0, st));
-                    const int Mp = r_up(nbb, 2);
-                    const size_t r_bytes = (size_t)(G < nbb ? G : nbb) * np * pgl_k_i8_padded_rows((int)D) * pgl_k_i8_padded_rows((int)D);
-                    long S = 64;                                   // (from T alone, like the border sums: the same norms -- hence scales -- whatever the shard)
-                    if (S > d.Tp / 256) S = d.Tp / 256;
-                    if (S > (long)(r_bytes / sizeof(double)) / part) S = (long)(r_bytes / sizeof(double)) / part;
-                    PglGemmArgs q{};
-                    q.A = d.OK + s0; q.lda = 2 * ldn; q.a_cols = Mp;
-                    q.B = d.X; q.ldb = Dp; q.b_cols = Dp;
-                    q.M = Mp; q.N = (int)D; q.alpha = 1.0; q.beta = 0.0; q.tri = 0; q.ldc = Dp;
-                    if (S >= 2) {
-                        const int chunk = (int)(d.Tp / 16 / S) * 16, rem = d.Tp - (int)S * chunk;
-                        double* partial = reinterpret_cast<double*>(s->i8_R);
-                        q.strideA = (long)chunk * q.lda; q.strideB = (long)chunk * Dp; q.C = partial; q.strideC = part; q.K = chunk; q.nbatch = (int)S;
-                        RC(pgl_launch_gemm(PGL_GEMM_SQUARES, q, st));
-                        if (rem > 0) {           // the last rem < 16 S rows: onto the first slice's sums
-                            q.A += (long)S * chunk * q.lda; q.B += (long)S * chunk * Dp; q.K = rem; q.nbatch = 1; q.beta = 1.0;
-                            RC(pgl_launch_gemm(PGL_GEMM_SQUARES, q, st));
-                        }
-                        hipLaunchKernelGGL(sum_slices_kernel, dim3((unsigned)((part + 255) / 256)), dim3(256), 0, st, partial, part, (int)S, ssb, 0, Dp, (int)D);
-                        PGL_CHECK_LAUNCH();
-                    } else {
-                        q.C = ssb; q.K = d.Tp; q.nbatch = 1;
-                        RC(pgl_launch_gemm(PGL_GEMM_SQUARES, q, st));
-                    }
-                    clk.toc(m);
-                }
-                for (int g0 = 0; g0 < nbb; g0 += G) {
-                    const int gz = G < nbb - g0 ? G : nbb - g0;
-                    const double* om = d.OK + s0 + g0;
-                    auto m = clk.tic(ST_STATS, batch_norms ? 0.0 : 8.0 * d.T * D);
-                    if (batch_norms) {
-                        RC(pgl_k_i8_scales_bound(ssb + (long)g0 * Dp, Dp, ommax + s0 + g0, d.xmax, (int)D, gz, d.T, np, sB, st));
-                    } else {
-                        // one pass over X per 8 neurons (the statistics pass borrows the residue buffer for its per-chunk partials: the previous
-                        // group's CRT has read it, this group's products have not written it yet)
-                        const size_t r_bytes = (size_t)gz * np * pgl_k_i8_padded_rows((int)D) * pgl_k_i8_padded_rows((int)D);
-                        for (int c0 = 0; c0 < gz; c0 += 8) {
-                            const int cz = 8 < gz - c0 ? 8 : gz - c0;
-                            if (pgl_k_i8_stats_scratch_doubles((int)D, cz) * sizeof(double) <= r_bytes)
-                                RC(pgl_k_i8_colstats_scales(d.X, Dp, om + c0, 2 * ldn, d.T, (int)D, cz, np, reinterpret_cast<double*>(s->i8_R), sB + (long)c0 * D, st));
-                            else {
-                                RC(pgl_k_i8_colstats(d.X, Dp, om + c0, 2 * ldn, d.T, (int)D, cz, amax, ss, st));
-                                RC(pgl_k_i8_scales(amax, ss, (long)cz * D, d.T, np, sB + (long)c0 * D, st));
-                            }
-                        }
-                    }
-                    clk.toc(m);
-                    // time slices (BASELINE configs[4]: one neuron's planes are 86 GB): the integer Gram is a sum over time, so the
-                    // slices' products add up in the residues; a data set without resident X planes converts those per slice too
-                    const int slice = s->i8_slice > 0 && s->i8_slice < d.T ? s->i8_slice : d.T;
-                    for (int t0 = 0; t0 < d.T; t0 += slice) {
-                        const int ts = slice < d.T - t0 ? slice : d.T - t0;
-                        m = clk.tic(ST_PLANES, (double)np * (gz + (d.PA ? 0 : 1)) * ts * D);
-                        if (!d.PA) RC(pgl_k_i8_planes(d.Xt + t0, d.Tp, 1, nullptr, 0, d.sA, static_cast<int8_t*>(s->i8_PAs), ts, (int)D, 1, np, t0, st));
-                        RC(pgl_k_i8_planes(d.Xt + t0, d.Tp, 1, om + (long)t0 * 2 * ldn, 2 * ldn, sB, static_cast<int8_t*>(s->i8_PB), ts, (int)D, gz, np, t0, st));   // (coalesced rows of Xt)
-                        clk.toc(m);
-                        m = clk.tic(ST_I8, (double)gz * ts * D * (D + 1));
-                        if (d.PA) RC(pgl_k_i8_gram(static_cast<const int8_t*>(d.PA), pgl_k_i8_kp(d.T), t0 / 64, static_cast<const int8_t*>(s->i8_PB),
-                                                   static_cast<int8_t*>(s->i8_R), static_cast<int8_t*>(s->i8_Rx), ts, (int)D, gz, np, t0 > 0, st));
-                        else RC(pgl_k_i8_gram(static_cast<const int8_t*>(s->i8_PAs), 0, 0, static_cast<const int8_t*>(s->i8_PB), static_cast<int8_t*>(s->i8_R),
-                                              static_cast<int8_t*>(s->i8_Rx), ts, (int)D, gz, np, t0 > 0, st));
-                        clk.toc(m);
-                    }
-                    m = clk.tic(ST_CRT, (double)np * gz * D * (D + 1) / 2);
-                    RC(pgl_k_i8_crt(static_cast<const int8_t*>(s->i8_R), static_cast<const int8_t*>(s->i8_Rx), d.sA, sB, s->Jbuf + (long)g0 * strideJ, ldj, strideJ, (int)D, gz, np, i > 0, st));
-                    clk.toc(m);
-                }
-            }
-        }
+        RC(gram_batch(*s, s0, nbb, clk, st));
         // ---- posterior assembly (regression.py:210-223, 253-260, 270-271)
         {
             auto m = clk.tic(ST_ASM);
@@ -455,6 +464,14 @@ int pgl_sweep(const pgl_sweep_t* s, uint64_t seed, uint64_t sweep, void* hip_str
         clk.toc(mw);
     }
     return PGL_OK;
+}
+
+int pgl_sweep_gram(const pgl_sweep_t* s, int first, int count, void* hip_stream) {
+    RC(check_gram_args(s));
+    PGL_CHECK_ARG(first >= 0 && count > 0 && count <= s->nb && first + count <= s->nloc);
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    Clock clk{s->times, st};
+    return gram_batch(*s, first, count, clk, st);
 }
 
 int pgl_get_state(const pgl_sweep_t* s, int* a_host, double* W_host, double* b_host, double* ll_host, int* status_host, void* hip_stream) {

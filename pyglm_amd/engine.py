@@ -8,12 +8,13 @@ PyTorch is used for device memory and streams only; all arithmetic is in libpygl
 import ctypes
 import functools
 import time
+import typing
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import FlipState, CholState, call, ptr
+from ._lib import call, ptr
 
 F64 = torch.float64
 I32 = torch.int32
@@ -88,7 +89,22 @@ class BlockPrior(object):
 
 
 class _Dataset(object):
-    pass
+    # what add_data leaves unset on a data set without the integer Gram or without hooks
+    int8, planes, sA, PA, xmax, hooks = False, 0, None, None, None, None
+
+
+class _I8Scratch(typing.NamedTuple):
+    """the integer Gram's scratch (GibbsEngine._i8_reserve)"""
+    bytes: int                           # held by the buffers below
+    T: int                               # the longest data set it is sized for
+    G: int                               # neurons per product launch (pgl_sweep_t.i8_group)
+    PB: torch.Tensor                     # planes of omega_g X (of one time slice)
+    R: torch.Tensor                      # residues of a group
+    stat: torch.Tensor                   # (3, G, D) per group: column maxima, sums of squares, scales of omega_g X
+    slice: int                           # time bins per slice (pgl_sweep_t.i8_slice; 0: the whole data set at once)
+    PAs: typing.Optional[torch.Tensor]   # planes of one slice of X where X's own are not resident
+    Rx: typing.Optional[torch.Tensor]    # the three extra residue slots per neuron of the K-quarter split of the last plane (groups that
+    #                                      fill the per-XCD lists: multiples of 8)
 
 
 class GibbsEngine(object):
@@ -258,8 +274,7 @@ class GibbsEngine(object):
 
     def _alloc_batch(self):
         nb, ldj, N, D, kmax = self.nb, self.ldj, self.N, self.D, self.kmax
-        self.Jslots = self._z(1, nb, ldj, ldj)
-        self.Jbuf = self.Jslots[0]
+        self.Jbuf = self._z(nb, ldj, ldj)
         self.Mtab = self._z(nb, ldj, ldj)
         self.Ac = self.Mtab if self.share_tableau else self._z(nb, ldj, ldj)
         self.hc = self._z(2, nb, ldj)
@@ -377,7 +392,6 @@ class GibbsEngine(object):
             return ds
         ds.Y = self._z(T, self.ldn)
         ds.Y[:, :self.nloc] = torch.from_numpy(np.ascontiguousarray(Y[:, self.n0:self.n1])).to(self.dev)
-        ds.hooks = None
         if obs_terms is not None:
             # [T][3 ldn] = a | b | log c (pgl_pg_loglik_ex), allocated before the batch size and the integer Gram's plan are chosen from the
             # memory left: 2.5 GB per data set at N = 1024, T = 1e5
@@ -392,7 +406,6 @@ class GibbsEngine(object):
         if self.likelihood_only:
             torch.cuda.synchronize(self.dev)
             ds.X = ds.OK = None                   # the activation contraction reads X' only
-            ds.int8 = False
             return ds
         plan = self._i8_plan(T)
         ds.int8 = plan is not None
@@ -485,7 +498,7 @@ class GibbsEngine(object):
         per_bin = planes * Dq                                    # bytes of one time bin in one set of planes
         r1 = lib.pgl_i8_residue_bytes(self.D) // mp * planes
         free = self._free_bytes()
-        have = self._i8_scratch[0] if self._i8_scratch else 0
+        have = self._i8_scratch.bytes if self._i8_scratch else 0
         budget = int(0.85 * free) + have
         gmax = int(max(1, min(over["group"] or self.I8_GROUPS[0], self.nb or self.nloc)))
         groups = [G for G in self.I8_GROUPS if G <= gmax] or [1]
@@ -535,29 +548,26 @@ class GibbsEngine(object):
         lib = _lib.load()
         mp, planes = lib.pgl_i8_max_planes(), plan["planes"]
         S, G, T0 = plan["slice"], plan["G"], 0
-        if self._i8_scratch:
-            S0 = self._i8_scratch[6]
-            if S0 and (not S or S0 < S):
-                S = S0
+        old = self._i8_scratch
+        if old and old.slice and (not S or old.slice < S):
+            S = old.slice
         Ts = min(S, T) if S else T
         pb1, r1 = lib.pgl_i8_plane_bytes(self.D, Ts) // mp * planes, lib.pgl_i8_residue_bytes(self.D) // mp * planes
         pas = 0 if plan["resident"] else pb1
-        if self._i8_scratch:
-            _, T0, G0, PB, R, _, S0, PAs = self._i8_scratch[:8]
-            if G0 == G and S0 == S and T0 >= T and PB.numel() >= G * pb1 and R.numel() >= G * r1 and (PAs.numel() if PAs is not None else 0) >= pas:
+        if old:
+            old_pas = old.PAs.numel() if old.PAs is not None else 0
+            if old.G == G and old.slice == S and old.T >= T and old.PB.numel() >= G * pb1 and old.R.numel() >= G * r1 and old_pas >= pas:
                 return
-            pb1, r1 = max(pb1, PB.numel() // G0), max(r1, R.numel() // G0)      # keep what earlier data sets need
-            pas = max(pas, PAs.numel() if PAs is not None else 0)
-            G = min(G, G0)
-        self._i8_scratch = None
+            pb1, r1 = max(pb1, old.PB.numel() // old.G), max(r1, old.R.numel() // old.G)      # keep what earlier data sets need
+            pas = max(pas, old_pas)
+            G, T0 = min(G, old.G), old.T
+        self._i8_scratch = old = None
         torch.cuda.empty_cache()
         Dq = lib.pgl_i8_padded_rows(self.D)
-        self._i8_scratch = (G * (pb1 + r1) + pas, max(T, T0), G, torch.empty(G * pb1, dtype=torch.int8, device=self.dev),
-                            torch.empty(G * r1, dtype=torch.int8, device=self.dev),
-                            self._z(3, G, self.D),          # per group: column maxima, sums of squares, scales of omega_g X
-                            S, torch.empty(pas, dtype=torch.int8, device=self.dev) if pas else None,
-                            # the three extra residue slots per neuron of the K-quarter split of the last plane (groups that fill the per-XCD lists)
-                            torch.empty(3 * G * Dq * Dq, dtype=torch.int8, device=self.dev) if G % 8 == 0 else None)
+        self._i8_scratch = _I8Scratch(bytes=G * (pb1 + r1) + pas, T=max(T, T0), G=G, PB=torch.empty(G * pb1, dtype=torch.int8, device=self.dev),
+                                      R=torch.empty(G * r1, dtype=torch.int8, device=self.dev), stat=self._z(3, G, self.D), slice=S,
+                                      PAs=torch.empty(pas, dtype=torch.int8, device=self.dev) if pas else None,
+                                      Rx=torch.empty(3 * G * Dq * Dq, dtype=torch.int8, device=self.dev) if G % 8 == 0 else None)
 
     @_on_device
     def drop_int8(self, i):
@@ -567,7 +577,7 @@ class GibbsEngine(object):
         if ds.int8:
             ds.int8 = False
             ds.PA = ds.sA = ds.xmax = None
-            if not any(getattr(d, "int8", False) for d in self.datasets):
+            if not any(d.int8 for d in self.datasets):
                 self._i8_norm = None
                 self._i8_scratch = None             # nobody multiplies planes any more: the group buffers (56 GB at cfg3) go back too
             torch.cuda.empty_cache()
@@ -607,11 +617,6 @@ class GibbsEngine(object):
             if self.obs == 2:      # self.ll then holds the sums of squared residuals
                 call("pgl_gaussian_stats", ptr(ds.Psi), self.ldn, ptr(self.bias), ptr(ds.Y), self.ldn, ptr(self.inv_eta), ptr(om), 2 * self.ldn,
                      kp, 2 * self.ldn, ptr(ds.llpart), ptr(self.ll), int(i > 0), ds.T, self.nloc, st)
-                self._toc(h)
-                continue
-            if self.obs in (0, 1) and self.obs_param is None:
-                call("pgl_pg_loglik", ptr(ds.Psi), self.ldn, ptr(self.bias), ptr(ds.Y), self.ldn, ptr(om), 2 * self.ldn, kp, 2 * self.ldn,
-                     ptr(ds.llpart), ptr(self.ll), int(i > 0), ds.T, self.nloc, self.obs, self.xi, int(seed), int(sweep), self.n0, ds.elem0, st)
             else:
                 call("pgl_pg_loglik_ex", ptr(ds.Psi), self.ldn, ptr(self.bias), ptr(ds.Y), self.ldn, ptr(om), 2 * self.ldn, kp, 2 * self.ldn,
                      ptr(ds.llpart), ptr(self.ll), int(i > 0), ds.T, self.nloc, self.obs, self.xi, ptr(self.obs_param), ptr(ds.hooks), self.ldn,
@@ -649,6 +654,41 @@ class GibbsEngine(object):
         return ds.Psi[:, :self.nloc].cpu().numpy()
 
     # ------------------------------------------------------------------ one Gibbs sweep of the shard's regressions
+    def _sweep_args(self, ovs=None):
+        """the argument block of pgl_sweep and pgl_sweep_gram.  Every buffer is persistent, so the struct is built once -- again when the I/O
+        buffer, the data sets, the batch or the integer Gram's scratch change, and for a call with omega overrides (ovs: one (T, nloc) device
+        array per data set, kept alive by the caller) -- and the caller assigns what changes from sweep to sweep (the inputs, the hints, the
+        optional outputs)"""
+        i8 = self._i8_scratch
+        sig = (self._din.data_ptr(), len(self.datasets), id(i8), self.nb, tuple(ds.int8 for ds in self.datasets))
+        if ovs or self._sweep_cache is None or self._sweep_cache[0] != sig:
+            dsets = (_lib.Dataset * len(self.datasets))()
+            for i, ds in enumerate(self.datasets):
+                dsets[i] = _lib.Dataset(T=ds.T, Tp=ds.Tp, X=ptr(ds.X), Xt=ptr(ds.Xt), Y=ptr(ds.Y), Psi=ptr(ds.Psi), OK=ptr(ds.OK), llpart=ptr(ds.llpart),
+                                        elem0=ds.elem0, int8=int(ds.int8), planes=ds.planes, sA=ptr(ds.sA), PA=ptr(ds.PA),
+                                        omega_override=ptr(ovs[i]) if ovs else None, xmax=ptr(ds.xmax), hooks=ptr(ds.hooks))
+            i8_args = dict(i8_group=i8.G, i8_PB=ptr(i8.PB), i8_R=ptr(i8.R), i8_stat=ptr(i8.stat), i8_slice=i8.slice, i8_PAs=ptr(i8.PAs),
+                           i8_Rx=ptr(i8.Rx)) if i8 else {}
+            sw = _lib.Sweep(N=self.N, B=self.B, n0=self.n0, nloc=self.nloc, nb=self.nb, obs=self.obs, xi=self.xi, visit_order=int(self.visit_order),
+                            planes=self.planes or 0, datasets=dsets, ndatasets=len(self.datasets), a=ptr(self.a_dev), W=ptr(self.W_dev),
+                            b=ptr(self.b_dev), inv_eta=ptr(getattr(self, "inv_eta", None)), G0=ptr(getattr(self, "G0", None)), ll=ptr(self.ll),
+                            status=ptr(self.status), Wt=ptr(self.Wt), bias=ptr(self.bias), border=ptr(self.border), skip=ptr(self.skip),
+                            Jbuf=ptr(self.Jbuf), Mtab=ptr(self.Mtab), Ac=ptr(self.Ac), hc=ptr(self.hc), Tinv=ptr(self.Tinv), G=ptr(self.G),
+                            Lws=ptr(self.Lws), Ut=ptr(self.Ut), Wt_ws=ptr(self.Wt_ws), d_idx=ptr(self.d_idx), d_sign=ptr(self.d_sign),
+                            d_cnt=ptr(self.d_cnt), batch_k=ptr(self.batch_k), act=ptr(self.act), na=ptr(self.na), obs_param=ptr(self.obs_param),
+                            **i8_args)
+            self._sweep_cache = None if ovs else (sig, sw, dsets)       # (the override tensors die with the caller's call)
+        else:
+            sw = self._sweep_cache[1]
+        sw.i8_norm = ptr(self._i8_norm) if i8 else None
+        if self.profile and self._times is None:
+            self._times = _lib.StageTimes()
+            if self.profile is not True:
+                names = [_lib.load().pgl_stage_name(i).decode() for i in range(_lib.NSTAGES)]
+                self._times.mask = sum(1 << names.index(n) for n in self.profile)
+        sw.times = ctypes.pointer(self._times) if self.profile else None
+        return sw
+
     @_on_device
     def sweep(self, a, W, b, rho, Jw, hw, Jb, hb, c0, perm, u, z, seed, sweep, omega_override=None, host_overlap=None, nrun=0,
               after_queue=None, readback=True, nfirst=0, copy=True, want_stats=False):
@@ -705,54 +745,19 @@ class GibbsEngine(object):
         self.logodds = torch.empty((nloc, N), dtype=F64, device=self.dev) if self.keep_logodds else None
         if label is not None and (self._c0_dense is None):
             self._c0_dense = self._z(nloc, N)
-        keep = []
-        ovs = []
+        ovs = None
         if omega_override is not None:
-            for i, ds in enumerate(self.datasets):
-                ov = torch.from_numpy(np.ascontiguousarray(omega_override[i], dtype=np.float64).reshape(ds.T, nloc)).to(self.dev)
-                keep.append(ov)
-                ovs.append(ov)
-        if self.profile and self._times is None:
-            self._times = _lib.StageTimes()
-            if self.profile is not True:
-                lib = _lib.load()
-                names = [lib.pgl_stage_name(i).decode() for i in range(_lib.NSTAGES)]
-                self._times.mask = sum(1 << names.index(n) for n in self.profile)
-        i8 = self._i8_scratch
-        # the argument block of pgl_sweep: every buffer is persistent, so the struct is built once and only what changes from sweep to sweep
-        # is assigned (the I/O pointers, the hints, the optional outputs)
-        sig = (base, len(self.datasets), id(i8), self.nb, bool(ovs), tuple(int(ds.int8) for ds in self.datasets))
-        if self._sweep_cache is None or self._sweep_cache[0] != sig or ovs:
-            dsets = (_lib.Dataset * len(self.datasets))()
-            for i, ds in enumerate(self.datasets):
-                dsets[i] = _lib.Dataset(ds.T, ds.Tp, ptr(ds.X), ptr(ds.Xt), ptr(ds.Y), ptr(ds.Psi), ptr(ds.OK), ptr(ds.llpart), ds.elem0, int(ds.int8),
-                                        int(getattr(ds, "planes", 0) or 0), ptr(getattr(ds, "sA", None)), ptr(getattr(ds, "PA", None)),
-                                        ptr(ovs[i]) if ovs else None, ptr(getattr(ds, "xmax", None)), ptr(getattr(ds, "hooks", None)))
-            sw = _lib.Sweep(N, B, self.n0, nloc, self.nb, self.obs, self.xi, int(self.visit_order), self.planes or 0, i8[2] if i8 else 0,
-                            dsets, len(self.datasets), ptr(self.a_dev), ptr(self.W_dev), ptr(self.b_dev),
-                            None, None, None, None, None, None, None, None, None, None,
-                            ptr(getattr(self, "inv_eta", None)), ptr(getattr(self, "G0", None)),
-                            ptr(self.ll), ptr(self.status), None,
-                            ptr(self.Wt), ptr(self.bias), ptr(self.border), ptr(self.skip), None,
-                            ptr(self.Jbuf), ptr(self.Mtab), ptr(self.Ac), ptr(self.hc), ptr(self.Tinv), ptr(self.G), ptr(self.Lws), ptr(self.Ut),
-                            ptr(self.Wt_ws), ptr(self.d_idx), ptr(self.d_sign), ptr(self.d_cnt), ptr(self.batch_k), ptr(self.act), ptr(self.na),
-                            ptr(i8[3]) if i8 else None, ptr(i8[4]) if i8 else None, ptr(i8[5]) if i8 else None,
-                            int(i8[6]) if i8 else 0, ptr(i8[7]) if i8 else None, ptr(i8[8]) if i8 else None, None, 0, 0, 0, 0, 0, 0, None,
-                            ptr(self.obs_param))
-            self._sweep_cache = (sig, sw, dsets)
-        sw = self._sweep_cache[1]
-        if ovs:
-            self._sweep_cache = None             # (the override tensors die with this call)
+            ovs = [torch.from_numpy(np.ascontiguousarray(omega_override[i], dtype=np.float64).reshape(ds.T, nloc)).to(self.dev)
+                   for i, ds in enumerate(self.datasets)]
+        sw = self._sweep_args(ovs)
         sw.rho, sw.Jw, sw.hw, sw.label, sw.Jb, sw.hb, sw.c0 = dp["rho"], dp["Jw"], dp["hw"], dp["label"], dp["Jb"], dp["hb"], dp["c0"]
         sw.perm, sw.u, sw.z = dp["perm"], dp["u"], dp["z"]
         sw.logodds, sw.c0_dense = ptr(self.logodds), ptr(self._c0_dense)
-        sw.i8_norm = ptr(self._i8_norm) if i8 else None
         n_act = int(a.sum(axis=1).max()) if a.size else 0
         sw.nrun, sw.nfirst, sw.all_deterministic = int(nrun), int(nfirst), int(det.all())
         sw.init_rows_bound = 1 + B * n_act
         sw.active_rows_bound = (1 + B * int(np.round(rho).sum(axis=1).max())) if det.all() else 0
         sw.flip_single_pass = int(self.flip_single_pass)
-        sw.times = ctypes.pointer(self._times) if self.profile else None
         t_launch = time.perf_counter()
         call("pgl_sweep", ctypes.byref(sw), int(seed), int(sweep), st)
         self.launch_seconds += time.perf_counter() - t_launch
@@ -785,7 +790,7 @@ class GibbsEngine(object):
         status = hout[off_st:off_st + 4 * nloc].view(np.int32).copy()
         if want_stats:
             self.last_row_stats = self._stats_host.numpy()
-        del keep
+        del ovs
         self.last_status = status
         if status.any() and readback:
             # the reference's np.linalg.cholesky raises at the first such neuron (regression.py:369-370), with the neurons before it already
@@ -829,55 +834,15 @@ class GibbsEngine(object):
         p[:, oa:oa + self.N] = self.a_dev.to(torch.uint8)
         return p
 
-    def _gram(self, s, nbb, slot):
-        """omega-weighted Gram of local neurons [s, s+nbb) into the batch's J (regression.py:251-252): the stage on its own (probes, tests;
-        a sweep runs the same kernels from pgl_sweep)"""
-        D, ldn, Dp, ldj = self.D, self.ldn, self.Dp, self.ldj
-        st = self._st()
-        J = self.Jslots[slot]
-        if self.obs == 2:
-            call("pgl_scaled_gram", ptr(self.G0), ldj, ctypes.c_void_p(self.inv_eta.data_ptr() + 8 * s), ptr(J), ldj, ldj * ldj, D, nbb, st)
-            return
-        for i, ds in enumerate(self.datasets):
-            if ds.int8:
-                G = self._i8_scratch[2]
-                for g0 in range(0, nbb, G):
-                    gz = min(G, nbb - g0)
-                    self._i8_group(ds, ctypes.c_void_p(ds.OK.data_ptr() + 8 * (s + g0)), 2 * self.ldn, gz,
-                                   ctypes.c_void_p(J.data_ptr() + 8 * g0 * self.ldj * self.ldj), int(i > 0))
-                continue
-            call("pgl_weighted_gram", ptr(ds.X), Dp, Dp, ctypes.c_void_p(ds.OK.data_ptr() + 8 * s), 2 * ldn, ds.Tp, D, nbb, ptr(J), ldj,
-                 ldj * ldj, int(i > 0), st)
-
-    def _i8_group(self, ds, om, ldo, gz, Jp, accumulate):
-        """J[g] (+)= X' diag(om[:, g]) X for gz <= group size weight columns at `om` (device pointer, leading dimension ldo): column
-        statistics -> scales -> per time slice: residue planes -> int8 products mod p (added up in the residues) -> CRT"""
-        D, Dp, ldj = self.D, self.Dp, self.ldj
-        st = self._st()
-        _, _, G, PB, R, stat, S, PAs = self._i8_scratch[:8]
-        assert gz <= G
-        npl = ds.planes
-        for c0 in range(0, gz, 8):          # (the statistics pass takes at most 8 weight columns)
-            cz = min(8, gz - c0)
-            call("pgl_i8_colstats", ptr(ds.X), Dp, ctypes.c_void_p(om.value + 8 * c0), ldo, ds.T, D, cz, ptr(stat[0][c0:]), ptr(stat[1][c0:]), st)
-        call("pgl_i8_scales", ptr(stat[0]), ptr(stat[1]), gz * D, ds.T, npl, ptr(stat[2]), st)
-        if not S and ds.PA is not None:
-            call("pgl_i8_planes_t", ptr(ds.Xt), ds.Tp, om, ldo, ptr(stat[2]), ptr(PB), ds.T, D, gz, npl, 0, st)
-            call("pgl_i8_gram", ptr(ds.PA), ptr(PB), ptr(R), ds.T, D, gz, npl, st)
-        else:
-            S = S or ds.T
-            for t0 in range(0, ds.T, S):
-                ts = min(S, ds.T - t0)
-                xt = ctypes.c_void_p(ds.Xt.data_ptr() + 8 * t0)
-                omt = ctypes.c_void_p(om.value + 8 * t0 * ldo)
-                if ds.PA is None:
-                    call("pgl_i8_planes_t", xt, ds.Tp, None, 0, ptr(ds.sA), ptr(PAs), ts, D, 1, npl, t0, st)
-                call("pgl_i8_planes_t", xt, ds.Tp, omt, ldo, ptr(stat[2]), ptr(PB), ts, D, gz, npl, t0, st)
-                call("pgl_i8_gram_slice", ptr(ds.PA) if ds.PA is not None else ptr(PAs), ds.T if ds.PA is not None else 0, t0, ptr(PB), ptr(R), ts, ds.T,
-                     D, gz, npl, int(t0 > 0), st)
-        call("pgl_i8_crt", ptr(R), ptr(ds.sA), ptr(stat[2]), Jp, ldj, ldj * ldj, ds.T, D, gz, npl, accumulate, st)
-
     # test hooks --------------------------------------------------------------------------------------------------
+    @_on_device
+    def sweep_gram(self, first, count):
+        """the likelihood Gram (regression.py:251-252) of local neurons [first, first + count) into Jbuf[:count], formed as a sweep forms it
+        for a batch that starts at `first` (pgl_sweep_gram) from the omega in each data set's OK: a sweep's, or the caller's own written into
+        ds.OK[:T, first:first + count].  Queued on the current stream"""
+        self._ensure_batch()
+        call("pgl_sweep_gram", ctypes.byref(self._sweep_args()), int(first), int(count), self._st())
+
     @_on_device
     def posterior(self, i):
         """assembled (J_post (D+1,D+1), h_post (D+1,)) of batch slot i as dense symmetric host arrays"""

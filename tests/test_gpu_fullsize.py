@@ -36,7 +36,7 @@ def test_gram_identities_at_cfg3_shape():
     W[:T, 1] = torch.rand(T, generator=g, device="cuda", dtype=torch.float64) * 0.25
     W[:T, 2] = W[:T, 0] + 2 * W[:T, 1]
     W[:T, 3] = 1.0
-    J = eng.Jslots[0]
+    J = torch.zeros(4, ldj, ldj, dtype=torch.float64, device="cuda")
     call("pgl_weighted_gram", ptr(ds.X), Dp, Dp, ptr(W), 4, ds.Tp, D, 4, ptr(J), ldj, ldj * ldj, 0, None)
     torch.cuda.synchronize()
     L = [torch.tril(J[k, :D, :D]) for k in range(4)]
@@ -54,10 +54,12 @@ def test_gram_identities_at_cfg3_shape():
     assert ((got - ref)[mask]).abs().max().item() <= 1e-11 * ref.abs().max().item()
     blk = J[3, 1280:1408, 1280:1408]                                                             # a diagonal tile is written in full
     assert (blk - blk.t()).abs().max().item() <= 1e-12 * blk.abs().max().item()
-    # the same four Grams through the integer matrix cores (what gram='auto' runs at this shape): residue planes, int8 GEMM mod p, CRT
-    assert ds.int8 and eng._i8_scratch is not None and eng._i8_scratch[2] >= 4
-    J8 = torch.zeros(4, ldj, ldj, dtype=torch.float64, device="cuda")
-    eng._i8_group(ds, ptr(W), 4, 4, ptr(J8), 0)
+    # the same four Grams through the sweep's own Gram stage, on the integer matrix cores (what gram='auto' runs at this shape): column
+    # norms, residue planes, int8 GEMM mod p, CRT
+    assert ds.int8 and eng._i8_scratch is not None and eng._i8_scratch.G >= 4
+    ds.OK[:T, :4] = W[:T]
+    eng.sweep_gram(0, 4)
+    J8 = eng.Jbuf
     torch.cuda.synchronize()
     L8 = [torch.tril(J8[k, :D, :D]) for k in range(4)]
     for k in range(4):
@@ -183,7 +185,7 @@ def test_cfg5_shape_sweep_with_flips():
     # J: regression.py:251-252 restricted to 64 rows x 32 columns (the whole J is 8.6 GB per neuron and X 52 GB: blocks are what the host can
     # take; a float64 dgemm over 200 000 bins is itself off by 1e-14 |x_i||omega x_j|, hence long double), with the GPU's own omega
     ds = eng.datasets[0]
-    assert ds.int8 and eng._i8_scratch[6] > 0                       # in time slices
+    assert ds.int8 and eng._i8_scratch.slice > 0                    # in time slices
     for r0, c0 in ((20000, 5000), (32768 - 64, 32768 - 64 - 32), (64, 0)):
         rows, cols = slice(r0, r0 + 64), slice(c0, c0 + 32)
         Xr, Xc = ds.X[:T, rows].cpu().numpy(), ds.X[:T, cols].cpu().numpy()
@@ -423,7 +425,7 @@ def test_cfg3_whole_model_in_batches_equals_the_oracle_checked_shards():
     perm, u, z = make_draws(31, 2, range(N), N, D)
     eng = GibbsEngine(N, B)
     ds = eng.add_data(Y, basis=basis)
-    assert ds.int8 and eng.nb == 256 and eng._i8_scratch[2] == 8
+    assert ds.int8 and eng.nb == 256 and eng._i8_scratch.G == 8
     eng.keep_logodds = True
     a1, W1, b1, ll1 = eng.sweep(a, W, b, rho, *hyp, perm, u, z, seed=31, sweep=2)
     lo1 = eng.logodds.cpu().numpy()

@@ -322,10 +322,12 @@ def test_time_slices_of_x_hold_the_integers_of_the_whole(T, S):
                 assert (_planes(other.cpu().numpy(), k, Dq, Ks)[:, :, :ts] != whole[:, :, t0:t0 + ts]).any()
 
 
-def test_heavy_tailed_columns_keep_the_error_at_the_fp64_level():
+@pytest.mark.parametrize("route", ["batch_norms", "per_group"])
+def test_heavy_tailed_columns_keep_the_error_at_the_fp64_level(route):
     """the guard of gram='auto' is structural: scales come from column NORMS, so a column with one element 1e8 x its rms, or a neuron
     whose omega has a spike, costs no precision relative to |a_i||b_j| -- checked against an extended-precision reference, next to the
-    fp64 kernel, through the engine's own group path (the default number of planes)"""
+    fp64 kernel, through the sweep's own Gram stage (pgl_sweep_gram, the default number of planes), with the column norms of the whole
+    batch (the default) and from a statistics pass per group (pgl_sweep_t.i8_norm = NULL)"""
     import torch
     from pyglm_amd.engine import GibbsEngine
     from pyglm_amd._lib import call, ptr
@@ -341,11 +343,14 @@ def test_heavy_tailed_columns_keep_the_error_at_the_fp64_level():
     eng = GibbsEngine(N, B, 0, 4, batch=4, gram="int8")
     ds = eng.add_data((rng.random((T, N)) < 0.1).astype(float), X=X)
     assert eng.planes is None and ds.planes == 13
+    if route == "per_group":
+        eng._i8_norm = None
     W = torch.zeros(ds.Tp, 4, dtype=torch.float64, device="cuda")
     W[:T] = torch.from_numpy(Om).cuda()
-    J8 = torch.zeros(4, eng.ldj, eng.ldj, dtype=torch.float64, device="cuda")
     J64 = torch.zeros(4, eng.ldj, eng.ldj, dtype=torch.float64, device="cuda")
-    eng._i8_group(ds, ptr(W), 4, 4, ptr(J8), 0)
+    ds.OK[:T, :4] = W[:T]
+    eng.sweep_gram(0, 4)
+    J8 = eng.Jbuf
     call("pgl_weighted_gram", ptr(ds.X), eng.Dp, eng.Dp, ptr(W), 4, ds.Tp, D, 4, ptr(J64), eng.ldj, eng.ldj * eng.ldj, 0, None)
     torch.cuda.synchronize()
     Xf = X.reshape(T, D)
@@ -381,10 +386,10 @@ def test_default_planes_against_the_fp64_kernels_own_error_on_bench_data(T):
         eng._upload_weights(np.ones((nl, N), bool), W, np.full(nl, -2.0))
         with torch.cuda.device(eng.dev):
             eng._psi_pass(True, 3, 0)
-            eng._gram(0, nl, 0)
+            eng.sweep_gram(0, nl)
             torch.cuda.synchronize()
         D = N * B
-        res[name] = eng.Jslots[0][:nl, :D, :D].cpu().numpy()
+        res[name] = eng.Jbuf[:nl, :D, :D].cpu().numpy()
         X, Om = ds.X[:T, :D].cpu().numpy(), ds.OK[:T, :nl].cpu().numpy()
         del eng, ds
         torch.cuda.empty_cache()
@@ -402,24 +407,26 @@ def test_default_planes_against_the_fp64_kernels_own_error_on_bench_data(T):
         assert r_int <= r_f64 and m_int <= m_f64, out
 
 
-def test_dyadic_data_is_exact():
+@pytest.mark.parametrize("route", ["batch_norms", "per_group"])
+def test_dyadic_data_is_exact(route):
     """spike counts through an identity basis (the reference's default basis, models.py:14-17) are small integers: with power-of-two
     scales the integer operands are exact -- no operand rounding at all for dyadic weights -- and every entry of the Gram comes back to
     the last few ulp of ITS OWN value (1e-15 relative: the fp64 Horner evaluation of the ~100-bit mixed-radix integer), where the
-    operand-rounding model only promises 2e-16 |a_i||b_j| -- orders of magnitude more for these nearly orthogonal columns"""
+    operand-rounding model only promises 2e-16 |a_i||b_j| -- orders of magnitude more for these nearly orthogonal columns.  Through the
+    sweep's own Gram stage, with the column norms of the whole batch (the default) and from a statistics pass per group"""
     import torch
     from pyglm_amd.engine import GibbsEngine
-    from pyglm_amd._lib import ptr
     rng = np.random.default_rng(8)
     N, B, T = 64, 5, 4000
     X = (rng.random((T, N, B)) < 0.1).astype(float) * rng.integers(1, 4, size=(T, N, B))       # counts 0..3
     eng = GibbsEngine(N, B, 0, 2, batch=2, gram="int8")
     ds = eng.add_data((rng.random((T, N)) < 0.1).astype(float), X=X)
-    W = torch.zeros(ds.Tp, 2, dtype=torch.float64, device="cuda")
-    W[:T, 0] = 1.0
-    W[:T, 1] = 0.25
-    J = torch.zeros(2, eng.ldj, eng.ldj, dtype=torch.float64, device="cuda")
-    eng._i8_group(ds, ptr(W), 2, 2, ptr(J), 0)
+    if route == "per_group":
+        eng._i8_norm = None
+    ds.OK[:T, 0] = 1.0
+    ds.OK[:T, 1] = 0.25
+    eng.sweep_gram(0, 2)
+    J = eng.Jbuf
     torch.cuda.synchronize()
     Xf = X.reshape(T, -1)
     G = Xf.T @ Xf                                       # integers below 2^53: exact in fp64
@@ -487,8 +494,8 @@ def test_time_slices_add_up_to_the_same_bits(resident):
         kw = {} if slc is None else dict(i8_slice=slc or None, i8_resident=resident)
         eng = GibbsEngine(N, B, gram="int8", batch=N, **kw)
         ds = eng.add_data(Y, X=X)
-        assert ds.int8 and (eng._i8_scratch[6] == (slc or 0)) and ((ds.PA is None) == (slc is not None and not resident))
-        assert (eng._i8_scratch[7] is not None) == (ds.PA is None)
+        assert ds.int8 and (eng._i8_scratch.slice == (slc or 0)) and ((ds.PA is None) == (slc is not None and not resident))
+        assert (eng._i8_scratch.PAs is not None) == (ds.PA is None)
         out = eng.sweep(a, W, b, rho, *hyp, perm, u, z, seed=5, sweep=0)
         res.append((eng.Jbuf[:, :D + 2, :D + 2].cpu().numpy().copy(), out))
         del eng
@@ -523,7 +530,7 @@ def test_group_sizes_give_the_same_bits(N, B, T):
     for G in (8, 16, 32, 64, 5):
         eng = GibbsEngine(N, B, gram="int8", batch=N, i8_group=G)
         ds = eng.add_data(Y, X=X)
-        assert ds.int8 and eng._i8_scratch[2] == G and (eng._i8_scratch[8] is not None) == (G % 8 == 0)
+        assert ds.int8 and eng._i8_scratch.G == G and (eng._i8_scratch.Rx is not None) == (G % 8 == 0)
         out = eng.sweep(*args, seed=5, sweep=0)
         res.append((eng.Jbuf[:, :D + 2, :D + 2].cpu().numpy().copy(), out))
         del eng
@@ -544,7 +551,7 @@ def test_group_size_follows_the_item_count():
         T = 17000
         eng = GibbsEngine(N, B)
         ds = eng.add_data((rng.random((T, N)) < 0.1).astype(float), X=rng.random((T, N, B)) * 0.1)
-        assert ds.int8 and eng._i8_scratch[2] == want, (N, eng._i8_scratch[2])
+        assert ds.int8 and eng._i8_scratch.G == want, (N, eng._i8_scratch.G)
         del eng
 
 
@@ -560,10 +567,10 @@ def test_data_sets_planned_with_different_slicing_share_the_shorter_slice():
     for second_slice in (None, 640):
         eng = GibbsEngine(N, B, gram="int8", batch=N)
         d0 = eng.add_data(Y[:1500], X=X[:1500])
-        assert d0.int8 and eng._i8_scratch[6] == 0
+        assert d0.int8 and eng._i8_scratch.slice == 0
         eng._i8_over["slice"] = second_slice             # the second data set is planned as if its planes only fitted 640 bins at a time
         d1 = eng.add_data(Y[1500:], X=X[1500:])
-        assert d1.int8 and eng._i8_scratch[6] == (second_slice or 0)
+        assert d1.int8 and eng._i8_scratch.slice == (second_slice or 0)
         out = eng.sweep(*args, seed=5, sweep=0)
         res.append((eng.Jbuf[:, :D + 2, :D + 2].cpu().numpy().copy(), out))
         del eng

@@ -1,6 +1,7 @@
-"""Measurement (GPU): error of the fp64-MFMA Gram kernel relative to |a_i||b_j|, with the integer path as the reference, on the
-bench's own kind of data (basis-filtered Bernoulli(0.08) spikes, omega ~ PG(1, psi)).  Decides how many residue planes the integer
-path needs to stay at or below the fp64 kernel's own error.   python tools/probe_f64err.py [T] [N]"""
+"""Measurement (GPU): error of the sweep's fp64 Gram route (GibbsEngine.sweep_gram: the fp64-MFMA kernel, split in time at D <= 512) relative to
+|a_i||b_j|, with the integer path as the reference, on the bench's own kind of data (basis-filtered Bernoulli(0.08) spikes, omega ~ PG(1,
+psi)).  Decides how many residue planes the integer path needs to stay at or below the fp64 kernel's own error.
+python tools/probe_f64err.py [T] [N]"""
 import os
 import sys
 
@@ -27,10 +28,10 @@ for gram in ("int8", "fp64"):
     eng._upload_weights(a, W, b)
     with torch.cuda.device(eng.dev):
         eng._psi_pass(True, 3, 0)
-        eng._gram(0, nl, 0)
+        eng.sweep_gram(0, nl)
         torch.cuda.synchronize()
     D = N * B
-    res[gram] = eng.Jslots[0][:nl, :D, :D].cpu().numpy()
+    res[gram] = eng.Jbuf[:nl, :D, :D].cpu().numpy()
     X = ds.X[:T, :D].cpu().numpy()
     Om = ds.OK[:T, :nl].cpu().numpy()
     del eng

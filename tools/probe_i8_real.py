@@ -30,10 +30,10 @@ eng._upload_weights(np.ones((nl, N), bool), rng.standard_normal((nl, N, B)) * 0.
 with torch.cuda.device(eng.dev):
     eng._psi_pass(True, 3, 0)
     D, Dp, ldj = eng.D, eng.Dp, eng.ldj
-    _, _, G, PB, R, stat = eng._i8_scratch[:6]
+    PB, R, stat = eng._i8_scratch.PB, eng._i8_scratch.R, eng._i8_scratch.stat
     om = ctypes.c_void_p(ds.OK.data_ptr())
     ldo = 2 * eng.ldn
-    J = eng.Jslots[0]
+    J = eng.Jbuf
     def stats():
         for c0 in range(0, nl, 8):          # (the statistics pass takes at most 8 weight columns)
             call("pgl_i8_colstats", ptr(ds.X), Dp, ctypes.c_void_p(om.value + 8 * c0), ldo, T, D, min(8, nl - c0), ptr(stat[0][c0:]), ptr(stat[1][c0:]), None)

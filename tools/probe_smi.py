@@ -140,7 +140,7 @@ eng._upload_weights(np.ones((nl, N), bool), rng.standard_normal((nl, N, B)) * 0.
 with torch.cuda.device(eng.dev):
     eng._psi_pass(True, 3, 0)
     D, Dp, ldj = eng.D, eng.Dp, eng.ldj
-    _, _, G, PB, R, stat = eng._i8_scratch[:6]
+    PB, R, stat = eng._i8_scratch.PB, eng._i8_scratch.R, eng._i8_scratch.stat
     om = ctypes.c_void_p(ds.OK.data_ptr())
     ldo = 2 * eng.ldn
     for c0 in range(0, nl, 8):
