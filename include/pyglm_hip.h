@@ -332,6 +332,37 @@ int pgl_get_state(const pgl_sweep_t* s, int* a_host, double* W_host, double* b_h
 const char* pgl_stage_name(int i);
 int pgl_stage_times_collect(pgl_stage_times_t* t);    /* waits for the recorded events and adds them to ms / calls / work */
 
+/* ---- posterior accumulators ---------------------------------------------------------------------------------------- */
+/* Running posterior summaries kept on the device and fed once per collected sample, instead of the reference's stacks of host samples
+ * (examples/synthetic.py:51-84: log_likelihood(), weights, adjacency, biases, means[0] appended per sweep, then .mean(0) / .std(0)).
+ *
+ * pgl_summary_fold: ONE pass over a data set's Psi [T][ldn] as pgl_activation left it (X.w, bias not added; Psi is not written).  Per cell
+ * (t, n), with psi = Psi + bias[n]:
+ *   - the log-likelihood term l of pgl_pg_loglik_ex (obs 0, 1, 3, 4; regression.py:491-494) or, obs 2, the squared residual of
+ *     pgl_gaussian_stats, summed per neuron into ll_out (+= with accumulate) through llpart [pgl_pg_loglik_partials(T)][nloc] with the block
+ *     shape and the order of addition of those two entry points: ll_out equals theirs bit for bit (models.py:82-96);
+ *   - rate_mean / rate_M2 (optional, [T][ldn]): Welford step k of E[y | psi] (models.py:153-163, means): d = x - mean; mean += d / k;
+ *     M2 += d (x - mean), with x by the neuron's link code -- link [nloc] or, NULL, link0 for all: 0 1 / (1 + exp(-psi)), 1 psi,
+ *     2 par exp(psi), 3 par / (1 + exp(-psi)); par = link_par[n] or, NULL, link_par0;
+ *   - l_mean / l_M2 / lse_m / lse_s (optional, all four or none, [T][ldn]): the same Welford step of l and a streaming log-sum-exp:
+ *     m' = max(m, l), s = s exp(m - m') + exp(l - m') (k = 1: m = l, s = 1).  For obs 2, l = -log(2 pi eta) / 2 - (y - psi)^2 / (2 eta),
+ *     eta = 1 / inv_eta[n] (regression.py:399-403).
+ * k: 1-based index of the sample (the caller counts; nothing is read back).  Y, the hooks' rows (ldh) and every accumulator share ldn.
+ * Accumulators are zeroed by the caller before k = 1.  No atomics; every cell has one owner. */
+int pgl_summary_fold(const double* Psi, long ldn, const double* bias, const double* Y, double* llpart, double* ll_out, int accumulate, int T,
+                     int nloc, int obs, double xi, const double* param, const double* hooks, long ldh, const double* inv_eta, double* rate_mean,
+                     double* rate_M2, const int* link, int link0, const double* link_par, double link_par0, double* l_mean, double* l_M2,
+                     double* lse_m, double* lse_s, int k, void* hip_stream);
+/* Step k of the chain state's moments (the stacked weights / adjacency / biases of examples/synthetic.py:51-84): edge [nloc][N] += a != 0;
+ * Welford (as above) of the effective weights a * W into w_mean / w_M2 [nloc][N*B] -- read from Wt [N*B ..][ldw], the k-major copy
+ * pgl_activation contracts with (Wt[d][n] = a[n][d / B] * W[n][d]) -- and of bias [nloc] into b_mean / b_M2.  a [nloc][N] int (0 / 1). */
+int pgl_summary_state(const int* a, const double* Wt, long ldw, const double* bias, double* edge, double* w_mean, double* w_M2, double* b_mean,
+                      double* b_M2, int N, int B, int nloc, int k, void* hip_stream);
+/* out[n] (+= with accumulate) = sum_t V[t][n] of V [T][ldv], n < nloc, through part [pgl_pg_loglik_partials(T)][nloc] in the block shape and the
+ * fixed order of the log-likelihood's reduction: a column's sum does not depend on the width of the array (the per-neuron sums of the
+ * pointwise predictive density; the stacked per-bin vectors of regression.py:491-494 summed as at models.py:93-94). */
+int pgl_summary_colsum(const double* V, long ldv, int T, int nloc, double* part, double* out, int accumulate, void* hip_stream);
+
 /* ---- forward simulation ------------------------------------------------------------------------------------------ */
 /* Bins [t0, t0 + Tc) of the population model's forward simulation (pyglm/models.py:98-151, generate: the loop at :129-144), serial in t,
  * in ONE cooperative launch.  Per bin t, for every neuron n:

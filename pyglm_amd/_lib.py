@@ -98,6 +98,9 @@ SIGNATURES = {
     "pgl_sample_weights": [ctypes.POINTER(CholState), c_i, c_p],
     "pgl_ubench_mfma": [c_i, c_d, ctypes.POINTER(c_d), ctypes.POINTER(c_d), c_p],
     "pgl_generate_work_bytes": [c_i, c_i],
+    "pgl_summary_fold": [c_p, c_l, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_d, c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_i, c_p, c_d, c_p, c_p, c_p, c_p, c_i, c_p],
+    "pgl_summary_state": [c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
+    "pgl_summary_colsum": [c_p, c_l, c_i, c_i, c_p, c_p, c_i, c_p],
     "pgl_generate": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_d, c_p, c_p, c_p, c_l, c_i, c_p, c_p, c_p],
 }
 

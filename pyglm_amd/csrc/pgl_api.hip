@@ -221,6 +221,30 @@ int pgl_i8_crt(const void* residues, const double* scale_x, const double* scale_
     return pgl_k_i8_crt(static_cast<const int8_t*>(residues), nullptr, scale_x, scale_wx, J, ldj, strideJ, D, G, nplanes, accumulate, ST(st));
 }
 
+int pgl_summary_fold(const double* Psi, long ldn, const double* bias, const double* Y, double* llpart, double* ll_out, int accumulate, int T,
+                     int nloc, int obs, double xi, const double* param, const double* hooks, long ldh, const double* inv_eta, double* rate_mean,
+                     double* rate_M2, const int* link, int link0, const double* link_par, double link_par0, double* l_mean, double* l_M2,
+                     double* lse_m, double* lse_s, int k, void* st) {
+    PGL_CHECK_ARG(Psi && Y && llpart && ll_out && T > 0 && nloc > 0 && ldn >= nloc && obs >= 0 && obs <= 4 && k >= 1);
+    PGL_CHECK_ARG(obs != 2 || inv_eta != nullptr);
+    PGL_CHECK_ARG(obs == 2 || param != nullptr || obs == 0 || obs == 4 || (obs == 1 ? xi > 0 : xi >= 0));
+    PGL_CHECK_ARG(obs != 4 || (hooks != nullptr && ldh >= nloc));
+    PGL_CHECK_ARG((rate_mean == nullptr) == (rate_M2 == nullptr) && (link != nullptr || (link0 >= 0 && link0 <= 3)));
+    PGL_CHECK_ARG((l_mean != nullptr) == (l_M2 != nullptr) && (l_mean != nullptr) == (lse_m != nullptr) && (l_mean != nullptr) == (lse_s != nullptr));
+    PglSummaryFold f{Psi, ldn, bias, Y, llpart, ll_out, accumulate, T, nloc, obs, xi, param, obs == 4 ? hooks : nullptr, ldh, inv_eta, rate_mean, rate_M2,
+                     link, link0, link_par, link_par0, l_mean, l_M2, lse_m, lse_s, k};
+    return pgl_k_summary_fold(f, ST(st));
+}
+int pgl_summary_state(const int* a, const double* Wt, long ldw, const double* bias, double* edge, double* w_mean, double* w_M2, double* b_mean,
+                      double* b_M2, int N, int B, int nloc, int k, void* st) {
+    PGL_CHECK_ARG(a && Wt && bias && edge && w_mean && w_M2 && b_mean && b_M2 && N > 0 && B > 0 && nloc > 0 && ldw >= nloc && k >= 1);
+    return pgl_k_summary_state(a, Wt, ldw, bias, edge, w_mean, w_M2, b_mean, b_M2, N, B, nloc, k, ST(st));
+}
+int pgl_summary_colsum(const double* V, long ldv, int T, int nloc, double* part, double* out, int accumulate, void* st) {
+    PGL_CHECK_ARG(V && part && out && T > 0 && nloc > 0 && ldv >= nloc);
+    return pgl_k_summary_colsum(V, ldv, T, nloc, part, out, accumulate, ST(st));
+}
+
 static PglFlipState to_state(const pgl_flip_t* s) {
     return PglFlipState{s->M, s->ldj, s->strideM, s->nb, s->N, s->B, s->perm, s->u, s->rho, s->c0, s->a, s->skip,
                         s->d_idx, s->d_sign, s->d_cnt, s->batch_k, s->G, s->Lws, s->Ut, s->Wt, s->ldu, s->status, s->visit_order, s->logodds};

@@ -111,6 +111,23 @@ int pgl_k_row_stats(const int* a, const double* W, double* out, int N, int B, in
 int pgl_k_pg_loglik(double*, long, const double*, const double*, long, double*, long, double*, long, double*, double*, int, int, int, int, double,
                     const double* param, const double* hooks, long ldh, uint64_t, uint64_t, uint64_t, uint64_t, hipStream_t);
 int pgl_k_pg_loglik_nblk(int);
+int pgl_k_colsum_partials(const double* part, int nblk, int ncol, double* out, int accumulate, hipStream_t st);   // out[n] (+)= sum_b part[b][n], b ascending
+// posterior accumulators (pgl_summary.hip)
+struct PglSummaryFold {
+    const double* Psi; long ld;         // [T][ld] X.w as pgl_activation left it (bias not added; not written); Y and the accumulators share ld
+    const double* bias; const double* Y;
+    double* llpart; double* ll_out; int accumulate;
+    int T, nloc, obs; double xi; const double* param; const double* hooks; long ldh; const double* inv_eta;
+    double* rmean; double* rM2;         // rates: Welford mean / M2 of E[y | psi], or null
+    const int* link; int link0;         // link code per neuron, or null: link0 for all (0 logistic, 1 identity, 2 par * exp, 3 par * logistic)
+    const double* link_par; double link_par0;
+    double* lmean; double* lM2; double* lse_m; double* lse_s;   // pointwise: Welford of the term l and its streaming log-sum-exp, or null
+    int k;                              // 1-based index of the sample being folded
+};
+int pgl_k_summary_fold(const PglSummaryFold& f, hipStream_t st);
+int pgl_k_summary_state(const int* a, const double* Wt, long ldw, const double* bias, double* edge, double* wmean, double* wM2, double* bmean,
+                        double* bM2, int N, int B, int nloc, int k, hipStream_t st);
+int pgl_k_summary_colsum(const double* V, long ldv, int T, int nloc, double* part, double* out, int accumulate, hipStream_t st);
 int pgl_k_gaussian_stats(double*, long, const double*, const double*, long, const double*, double*, long, double*, long, double*, double*, int, int,
                          int, hipStream_t);
 int pgl_k_scaled_gram(const double*, long, const double*, double*, long, long, int, int, hipStream_t);

@@ -2,6 +2,7 @@
 // log-likelihood in one pass over Psi; causal basis convolution that builds the design matrix in HBM;
 // assembly of the posterior precision from the Gram tiles, the border sums and the block-diagonal prior.
 #include "pgl_common.h"
+#include "pgl_obs.h"
 #include "pgl_rng.h"
 
 namespace {
@@ -30,43 +31,7 @@ __global__ __launch_bounds__(256) void pg_draw_kernel(const double* __restrict__
 // a wave reads/writes 64 consecutive doubles of one time bin.  Each block covers ROWS time bins of one 64-neuron
 // column group and leaves one log-likelihood partial per neuron; a second pass adds partials in a fixed order
 // (deterministic; no atomics).
-constexpr int PGLL_ROWS = 64;
-
-struct PgLlArgs {
-    double* Psi; long ldpsi;            // in: X.w   out: psi = X.w + bias   [T][ldpsi]
-    const double* bias;                 // [nloc]
-    const double* Y; long ldy;          // spikes/counts of the local neurons: Y[t*ldy + n]
-    double* Omega; long ldo;            // out [T][ldo]   (may be null: log-likelihood only)
-    double* Kappa; long ldk;            // out [T][ldk]   (may be null)
-    double* llpart;                     // [nblk_t][nloc]
-    int T, nloc;
-    int obs;                            // 0 Bernoulli (a=y,b=1,c=1)  1 negative binomial (a=y, b=y+xi, c=C(y+xi-1,y))
-                                        // 2 Gaussian (regression.py:380-446): omega = 1/eta, kappa = y/eta, "ll" = sum of squared residuals
-                                        // 3 binomial (a=y, b=n, c=C(n,y))  4 hooks: a, b, log c read from `hooks`
-    double xi;                          // xi (obs 1) or n (obs 3) where param is null
-    const double* inv_eta;              // [nloc] 1/eta per neuron (obs == 2 only)
-    uint64_t seed, sweep, neuron0, elem0;
-    const double* param;                // optional [nloc]: xi (obs 1) or n (obs 3) per neuron
-    const double* hooks; long ldh;      // obs 4: [T][3 ldh] = a | b | log c of the local neurons
-};
-
-// a(y), b(y), log c(y) of one cell (regression.py:479-489) for the PG observation models; (a, b, logc) = (y, 1, 0) for Bernoulli
-__device__ __forceinline__ void pg_abc(const PgLlArgs& g, int n, long t, double y, double& a, double& b, double& logc) {
-    a = y; b = 1.0; logc = 0.0;
-    if (g.obs == 1) {
-        const double xi = g.param ? g.param[n] : g.xi;
-        b = y + xi; logc = lgamma(y + xi) - lgamma(y + 1.0) - lgamma(xi);
-    } else if (g.obs == 3) {
-        const double m = g.param ? g.param[n] : g.xi;
-        b = m; logc = lgamma(m + 1.0) - lgamma(y + 1.0) - lgamma(m - y + 1.0);
-    } else if (g.obs == 4) {
-        const double* h = g.hooks + t * 3 * g.ldh + n;
-        a = h[0]; b = h[g.ldh]; logc = h[2 * g.ldh];
-    }
-}
-
-// one time bin's term of the log-likelihood (regression.py:491-494); one function for both kernels below, so that they round alike
-__device__ __forceinline__ double pg_ll_term(double logc, double a, double b, double psi) { return logc + a * psi - b * log1p(exp(psi)); }
+// (block shape, argument block and the per-cell terms: pgl_obs.h, shared with the posterior accumulators of pgl_summary.hip)
 
 __global__ __launch_bounds__(256) void pg_loglik_kernel(PgLlArgs g) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -362,6 +327,12 @@ int pgl_k_scaled_gram(const double* G0, long ldg, const double* inv_eta, double*
 }
 
 int pgl_k_pg_loglik_nblk(int T) { return (T + PGLL_ROWS - 1) / PGLL_ROWS; }
+
+int pgl_k_colsum_partials(const double* part, int nblk, int ncol, double* out, int accumulate, hipStream_t st) {
+    hipLaunchKernelGGL(colsum_partials_kernel, dim3((ncol + 255) / 256), dim3(256), 0, st, part, nblk, ncol, out, accumulate);
+    PGL_CHECK_LAUNCH();
+    return PGL_OK;
+}
 
 int pgl_k_basis_conv(const double* S, long lds, const double* basis, double* X, long ldx, double* Xt, long ldxt, int T, int N, int B, int R,
                      int clip, hipStream_t st) {

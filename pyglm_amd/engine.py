@@ -93,6 +93,10 @@ class _Dataset(object):
     int8, planes, sA, PA, xmax, hooks = False, 0, None, None, None, None
 
 
+class _Summary(object):
+    """device accumulators of one posterior summary (GibbsEngine.summary_alloc): rate / pw per data set, edge, w, b of the state"""
+
+
 class _I8Scratch(typing.NamedTuple):
     """the integer Gram's scratch (GibbsEngine._i8_reserve)"""
     bytes: int                           # held by the buffers below
@@ -652,6 +656,101 @@ class GibbsEngine(object):
         self._psi_pass(False, 0, 0)
         ds = self.datasets[i]
         return ds.Psi[:, :self.nloc].cpu().numpy()
+
+    # ------------------------------------------------------------------ posterior accumulators (pyglm_amd/summary.py)
+    def summary_bytes(self, rates=True, pointwise=False):
+        """device bytes summary_alloc takes: (T_i x ldn) doubles per data set x 2 (rates) + 4 (pointwise), and the state's moments"""
+        per = 2 * bool(rates) + 4 * bool(pointwise)
+        cells = sum(ds.T for ds in self.datasets) * self.ldn
+        return 8 * per * cells + 8 * (self.nloc * self.N + 2 * self.nloc * self.D + 2 * self.nloc) + 4 * self.nloc * self.N
+
+    @_on_device
+    def summary_alloc(self, rates=True, pointwise=False, link=None, link_par=None):
+        """zeroed accumulators for the data sets this engine holds now: per data set the Welford (mean, M2) of the rates and, pointwise, of
+        the log-likelihood term plus its streaming log-sum-exp (m, s); the edge counts and the moments of a * W and b.  Checked against
+        what this engine may still take on its GPU (_free_bytes) BEFORE anything is allocated: MemoryError otherwise.
+        link / link_par: per local neuron, the link code of pgl_summary_fold and its parameter -- required for the rates of the hooks mode,
+        where the engine does not know the neurons' models; the built-in modes take theirs from the observation model."""
+        need, free = self.summary_bytes(rates, pointwise), self._free_bytes()
+        if need > free:
+            raise MemoryError("posterior summary: the accumulators need %d bytes, %d are free on %s" % (need, free, self.dev))
+        s = _Summary()
+        s.ndatasets = len(self.datasets)
+        s.link0, s.link_par0, s.link, s.link_par = {0: 0, 1: 2, 2: 1, 3: 3, 4: 0}[self.obs], float(self.xi), None, self.obs_param
+        if self.obs == 4:
+            s.link_par = None
+            if rates:
+                if link is None:
+                    raise ValueError("the rates of the hooks mode need a link code per neuron")
+                s.link = torch.from_numpy(np.ascontiguousarray(link, dtype=np.int32).reshape(self.nloc)).to(self.dev)
+                s.link_par = torch.from_numpy(np.ascontiguousarray(link_par, dtype=np.float64).reshape(self.nloc)).to(self.dev)
+        s.rate = [(self._z(ds.T, self.ldn), self._z(ds.T, self.ldn)) for ds in self.datasets] if rates else None
+        s.pw = [tuple(self._z(ds.T, self.ldn) for _ in range(4)) for ds in self.datasets] if pointwise else None
+        s.a = self._z(self.nloc, self.N, dtype=I32)
+        s.edge = self._z(self.nloc, self.N)
+        s.w = (self._z(self.nloc, self.D), self._z(self.nloc, self.D))
+        s.b = (self._z(self.nloc), self._z(self.nloc))
+        return s
+
+    @_on_device
+    def summary_reset(self, s):
+        for t in [s.edge, *s.w, *s.b] + [x for grp in (s.rate or []) + (s.pw or []) for x in grp]:
+            t.zero_()
+
+    @_on_device
+    def summary_fold(self, s, a, W, b, k):
+        """sample k (1-based) of the state (a, W, b) into the accumulators s: one upload of the weights, per data set ONE activation and ONE
+        pgl_summary_fold, then pgl_summary_state.  Returns what log_likelihood(a, W, b) returns, to the last bit (the fold forms the
+        per-neuron totals as pgl_pg_loglik_ex / pgl_gaussian_stats do).  Gaussian: set_noise first, as for log_likelihood."""
+        if len(self.datasets) != s.ndatasets:
+            raise RuntimeError("data was added after the posterior summary was allocated: its accumulators cover %d data sets, the engine "
+                               "holds %d (build a new summary)" % (s.ndatasets, len(self.datasets)))
+        self._upload_weights(a, W, b)
+        s.a.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(a).reshape(self.nloc, self.N), dtype=np.int32)))
+        st = self._st()
+        none2, none4 = (None, None), (None,) * 4
+        for i, ds in enumerate(self.datasets):
+            h = self._tic("activation", 2.0 * ds.T * self.D * self.nloc)
+            call("pgl_activation", ptr(ds.Xt), ds.Tp, ptr(self.Wt), self.ldn, ptr(ds.Psi), self.ldn, ds.T, self.Dp, self.nloc, st)
+            self._toc(h)
+            h = self._tic("summary_fold", float(ds.T) * self.nloc)
+            r, p = s.rate[i] if s.rate else none2, s.pw[i] if s.pw else none4
+            call("pgl_summary_fold", ptr(ds.Psi), self.ldn, ptr(self.bias), ptr(ds.Y), ptr(ds.llpart), ptr(self.ll), int(i > 0), ds.T, self.nloc,
+                 self.obs, self.xi, ptr(self.obs_param), ptr(ds.hooks), self.ldn, ptr(self.inv_eta) if self.obs == 2 else None, ptr(r[0]), ptr(r[1]),
+                 ptr(s.link), s.link0, ptr(s.link_par), s.link_par0, ptr(p[0]), ptr(p[1]), ptr(p[2]), ptr(p[3]), int(k), st)
+            self._toc(h)
+        call("pgl_summary_state", ptr(s.a), ptr(self.Wt), self.ldn, ptr(self.bias), ptr(s.edge), ptr(s.w[0]), ptr(s.w[1]), ptr(s.b[0]), ptr(s.b[1]),
+             self.N, self.B, self.nloc, int(k), st)
+        return self._ll_host(self.ll)
+
+    @_on_device
+    def summary_state(self, s, k):
+        """-> host dict(edge_prob (nloc, N), weight_mean, weight_var (nloc, N, B), bias_mean, bias_var (nloc,)) after k samples"""
+        shp = (self.nloc, self.N, self.B)
+        host = lambda t: t.cpu().numpy()           # (the divisions on the host: a count / k there is the correctly rounded quotient)
+        return dict(edge_prob=host(s.edge) / k, weight_mean=host(s.w[0]).reshape(shp), weight_var=host(s.w[1]).reshape(shp) / k,
+                    bias_mean=host(s.b[0]), bias_var=host(s.b[1]) / k)
+
+    @_on_device
+    def summary_rates(self, s, i, k, std=False):
+        """-> host (T_i, nloc): the mean of the rates of data set i over k samples, or their standard deviation (population: M2 / k)"""
+        mean, M2 = s.rate[i]
+        out = torch.sqrt(M2[:, :self.nloc] / k) if std else mean[:, :self.nloc]
+        return out.cpu().numpy()
+
+    @_on_device
+    def summary_pointwise(self, s, k, var=False):
+        """-> host (nloc,): per neuron, the sum over all bins of log mean_s exp(l) = m + log s - log k, or (var) of the sample variance
+        M2 / (k - 1) of l.  Element-wise in torch; the sums over t through pgl_summary_colsum, in the fixed order of the log-likelihood's
+        reduction (torch.sum's order may follow the width of the array)."""
+        out = self._z(self.nloc)
+        st = self._st()
+        for i, ds in enumerate(self.datasets):
+            lmean, lM2, m, sm = s.pw[i]
+            V = lM2 / (k - 1) if var else m + torch.log(sm) - float(np.log(k))
+            call("pgl_summary_colsum", ptr(V), self.ldn, ds.T, self.nloc, ptr(ds.llpart), ptr(out), int(i > 0), st)
+            torch.cuda.current_stream(self.dev).synchronize()        # (V is released below; the launch must have read it)
+        return out.cpu().numpy()
 
     # ------------------------------------------------------------------ one Gibbs sweep of the shard's regressions
     def _sweep_args(self, ovs=None):

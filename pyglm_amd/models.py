@@ -335,26 +335,37 @@ class NonlinearAutoregressiveModel(object):
         if self.engine_obs() == "gaussian":
             eng.set_noise([r.eta for r in self.regressions[self.n0:self.n1]])
         ll_loc = np.asarray(eng.log_likelihood(a, W, b), dtype=np.float64).reshape(-1)       # one value per local neuron
+        return float(np.sum(self._all_neurons(ll_loc)))
+
+    def _all_neurons(self, loc):
+        """per-neuron values of this rank's neurons, (nloc,) or (k, nloc) -> those of ALL neurons, (N,) or (k, N), on every rank.  No process
+        group: `loc` itself.  Otherwise the only collective on the likelihood path: ONE all_reduce -- of the N per-neuron values, each rank
+        contributing its own entries and zeros elsewhere (x + 0 is exact, so the reduction's order cannot matter); the caller sums them in
+        neuron order on every rank: the total is the same to the last bit whatever the number of ranks (a scalar all_reduce of per-rank
+        sums regroups the additions; 8 N bytes instead of 8 cost nothing on xGMI)"""
         dist = _dist()
         if dist is None:
-            return float(np.sum(ll_loc))
-        # the only collective on the likelihood path: ONE all_reduce -- of the N per-neuron values, each rank contributing its own entries and
-        # zeros elsewhere (x + 0 is exact, so the reduction's order cannot matter), then summed in neuron order on every rank: the total is
-        # the same to the last bit whatever the number of ranks (a scalar all_reduce of per-rank sums regroups the additions; 8 N bytes
-        # instead of 8 cost nothing on xGMI)
+            return loc
         import time
         import torch
         t0 = time.perf_counter()
-        vec = np.zeros(self.N)
-        vec[self.n0:self.n1] = ll_loc
+        vec = np.zeros(loc.shape[:-1] + (self.N,))
+        vec[..., self.n0:self.n1] = loc
         t = torch.from_numpy(vec)
         if dist.get_backend() == "nccl":
             t = t.to(self._comm_dev())
         dist.all_reduce(t)
-        ll = float(np.sum(t.cpu().numpy()))
+        out = t.cpu().numpy()
         self.comm_seconds += time.perf_counter() - t0
         self.collectives += 1
-        return ll
+        return out
+
+    def summarize(self, rates=True, pointwise=False, datas=None):
+        """a posterior accumulator bound to this model (pyglm_amd/summary.py): call its collect() after every sweep to be kept, read
+        edge_prob / weight_mean / rate_mean / lppd() ... at the end.  Allocates its accumulators (on the device, next to the data);
+        changes nothing in the chain.  datas: as for log_likelihood -- None: the stored data; a list: held-out data."""
+        from .summary import PosteriorSummary
+        return PosteriorSummary(self, rates=rates, pointwise=pointwise, datas=datas)
 
     def _heldout_engine(self, datas):
         """likelihood-only engine (X', Y, Psi: no sweep buffers, no residue planes) for data other than the stored data, on THIS shard's
@@ -644,6 +655,11 @@ class NonlinearAutoregressiveModel(object):
 _MEAN_OF_PSI = {_regression.SparseBernoulliRegression.mean: lambda r, psi: logistic(psi),
                 _regression.SparseNegativeBinomialRegression.mean: lambda r, psi: r.xi * np.exp(psi),
                 _regression.SparseBinomialRegression.mean: lambda r, psi: r.n * logistic(psi)}
+
+
+# the same models as link codes of pgl_summary_fold: (code, attribute that holds the link's parameter)
+_LINK_OF_MEAN = {_regression.SparseBernoulliRegression.mean: (0, None), _regression.SparseNegativeBinomialRegression.mean: (2, "xi"),
+                 _regression.SparseBinomialRegression.mean: (3, "n")}
 
 
 class _LazyX(object):
