@@ -1,6 +1,6 @@
 // extern "C" entry points of libpyglm_hip.so (declared and documented in include/pyglm_hip.h).
 #include "pgl_common.h"
-#include "../../include/pyglm_hip.h"
+#include "pgl_obs.h"
 #include <cstdarg>
 #include <cstdio>
 
@@ -99,8 +99,12 @@ int pgl_pg_loglik(double* Psi, long ldpsi, const double* bias, const double* Y, 
                   uint64_t neuron0, uint64_t elem0, void* st) {
     PGL_CHECK_ARG(Psi && Y && llpart && ll_out && T > 0 && nloc > 0 && (obs == 0 || obs == 1));
     PGL_CHECK_ARG(obs == 0 || xi > 0);
-    return pgl_k_pg_loglik(Psi, ldpsi, bias, Y, ldy, Omega, ldo, Kappa, ldk, llpart, ll_out, accumulate, T, nloc, obs, xi, nullptr, nullptr, 0, seed,
-                           sweep, neuron0, elem0, ST(st));
+    PgLlArgs a{};
+    a.Psi = Psi; a.ldpsi = ldpsi; a.bias = bias; a.Y = Y; a.ldy = ldy; a.llpart = llpart; a.T = T; a.nloc = nloc;
+    a.obs = obs; a.xi = xi;
+    a.Omega = Omega; a.ldo = ldo; a.Kappa = Kappa; a.ldk = ldk;
+    a.seed = seed; a.sweep = sweep; a.neuron0 = neuron0; a.elem0 = elem0;
+    return pgl_k_pg_loglik(a, ll_out, accumulate, ST(st));
 }
 int pgl_pg_loglik_ex(double* Psi, long ldpsi, const double* bias, const double* Y, long ldy, double* Omega, long ldo, double* Kappa, long ldk,
                      double* llpart, double* ll_out, int accumulate, int T, int nloc, int obs, double xi, const double* param, const double* hooks,
@@ -108,15 +112,23 @@ int pgl_pg_loglik_ex(double* Psi, long ldpsi, const double* bias, const double* 
     PGL_CHECK_ARG(Psi && Y && llpart && ll_out && T > 0 && nloc > 0 && obs >= 0 && obs <= 4 && obs != 2);
     PGL_CHECK_ARG(param != nullptr || obs == 0 || obs == 4 || (obs == 1 ? xi > 0 : xi >= 0));
     PGL_CHECK_ARG(obs != 4 || (hooks != nullptr && ldh >= nloc));
-    return pgl_k_pg_loglik(Psi, ldpsi, bias, Y, ldy, Omega, ldo, Kappa, ldk, llpart, ll_out, accumulate, T, nloc, obs, xi, param, obs == 4 ? hooks : nullptr,
-                           ldh, seed, sweep, neuron0, elem0, ST(st));
+    PgLlArgs a{};
+    a.Psi = Psi; a.ldpsi = ldpsi; a.bias = bias; a.Y = Y; a.ldy = ldy; a.llpart = llpart; a.T = T; a.nloc = nloc;
+    a.obs = obs; a.xi = xi; a.param = param; a.hooks = obs == 4 ? hooks : nullptr; a.ldh = ldh;
+    a.Omega = Omega; a.ldo = ldo; a.Kappa = Kappa; a.ldk = ldk;
+    a.seed = seed; a.sweep = sweep; a.neuron0 = neuron0; a.elem0 = elem0;
+    return pgl_k_pg_loglik(a, ll_out, accumulate, ST(st));
 }
-int pgl_pg_loglik_partials(int T) { return pgl_k_pg_loglik_nblk(T); }
+int pgl_pg_loglik_partials(int T) { return psi_row_blocks(T); }
 
 int pgl_gaussian_stats(double* Psi, long ldpsi, const double* bias, const double* Y, long ldy, const double* inv_eta, double* Omega, long ldo,
                        double* Kappa, long ldk, double* part, double* sse_out, int accumulate, int T, int nloc, void* st) {
     PGL_CHECK_ARG(Psi && Y && inv_eta && part && sse_out && T > 0 && nloc > 0);
-    return pgl_k_gaussian_stats(Psi, ldpsi, bias, Y, ldy, inv_eta, Omega, ldo, Kappa, ldk, part, sse_out, accumulate, T, nloc, ST(st));
+    PgLlArgs a{};
+    a.Psi = Psi; a.ldpsi = ldpsi; a.bias = bias; a.Y = Y; a.ldy = ldy; a.llpart = part; a.T = T; a.nloc = nloc;
+    a.obs = 2; a.inv_eta = inv_eta;
+    a.Omega = Omega; a.ldo = ldo; a.Kappa = Kappa; a.ldk = ldk;
+    return pgl_k_pg_loglik(a, sse_out, accumulate, ST(st));
 }
 
 int pgl_scaled_gram(const double* G0, long ldg, const double* inv_eta, double* J, long ldj, long strideJ, int D, int nz, void* st) {
@@ -231,8 +243,12 @@ int pgl_summary_fold(const double* Psi, long ldn, const double* bias, const doub
     PGL_CHECK_ARG(obs != 4 || (hooks != nullptr && ldh >= nloc));
     PGL_CHECK_ARG((rate_mean == nullptr) == (rate_M2 == nullptr) && (link != nullptr || (link0 >= 0 && link0 <= 3)));
     PGL_CHECK_ARG((l_mean != nullptr) == (l_M2 != nullptr) && (l_mean != nullptr) == (lse_m != nullptr) && (l_mean != nullptr) == (lse_s != nullptr));
-    PglSummaryFold f{Psi, ldn, bias, Y, llpart, ll_out, accumulate, T, nloc, obs, xi, param, obs == 4 ? hooks : nullptr, ldh, inv_eta, rate_mean, rate_M2,
-                     link, link0, link_par, link_par0, l_mean, l_M2, lse_m, lse_s, k};
+    PglSummaryFold f{};
+    f.Psi = const_cast<double*>(Psi); f.ldpsi = ldn; f.bias = bias; f.Y = Y; f.ldy = ldn; f.llpart = llpart; f.T = T; f.nloc = nloc;   // (the fold only reads Psi)
+    f.obs = obs; f.xi = xi; f.param = param; f.hooks = obs == 4 ? hooks : nullptr; f.ldh = ldh; f.inv_eta = inv_eta;
+    f.ll_out = ll_out; f.accumulate = accumulate;
+    f.rmean = rate_mean; f.rM2 = rate_M2; f.link = link; f.link0 = link0; f.link_par = link_par; f.link_par0 = link_par0;
+    f.lmean = l_mean; f.lM2 = l_M2; f.lse_m = lse_m; f.lse_s = lse_s; f.k = k;
     return pgl_k_summary_fold(f, ST(st));
 }
 int pgl_summary_state(const int* a, const double* Wt, long ldw, const double* bias, double* edge, double* w_mean, double* w_M2, double* b_mean,
@@ -245,51 +261,43 @@ int pgl_summary_colsum(const double* V, long ldv, int T, int nloc, double* part,
     return pgl_k_summary_colsum(V, ldv, T, nloc, part, out, accumulate, ST(st));
 }
 
-static PglFlipState to_state(const pgl_flip_t* s) {
-    return PglFlipState{s->M, s->ldj, s->strideM, s->nb, s->N, s->B, s->perm, s->u, s->rho, s->c0, s->a, s->skip,
-                        s->d_idx, s->d_sign, s->d_cnt, s->batch_k, s->G, s->Lws, s->Ut, s->Wt, s->ldu, s->status, s->visit_order, s->logodds};
-}
 int pgl_flip_kmax(void) { return pgl_k_flip_kmax(); }
 int pgl_flip_window_blocks(int B) { return pgl_k_flip_window_blocks(B); }
 int pgl_flip_apply(const pgl_flip_t* s, void* st) {
     PGL_CHECK_ARG(s && s->M && s->d_idx && s->d_sign && s->d_cnt && s->batch_k && s->G && s->Ut && s->Wt && s->status);
     PGL_CHECK_ARG(s->ldu >= (long)s->N * s->B + 2 && s->ldu % 2 == 0 && s->ldj >= (long)s->N * s->B + 2 && s->nb > 0);
-    return pgl_k_flip_apply(to_state(s), 0, 128, -1, ST(st));
+    return pgl_k_flip_apply(*s, 0, 128, -1, ST(st));
 }
 int pgl_flip_apply_chunk(const pgl_flip_t* s, int max_pivots, void* st) {
     PGL_CHECK_ARG(s && s->M && s->d_idx && s->d_sign && s->d_cnt && s->batch_k && s->G && s->Lws && s->Ut && s->Wt && s->status);
     PGL_CHECK_ARG(s->ldu >= (long)s->N * s->B + 2 && s->ldu % 2 == 0 && s->ldj >= (long)s->N * s->B + 2 && s->nb > 0 && max_pivots > 0);
-    return pgl_k_flip_apply(to_state(s), 0, max_pivots, -1, ST(st));
+    return pgl_k_flip_apply(*s, 0, max_pivots, -1, ST(st));
 }
 int pgl_flip_visit_order(const pgl_flip_t* s, const double* J, long ldj_src, long strideJ, void* st) {
     PGL_CHECK_ARG(s && s->M && s->perm && J && s->visit_order && s->nb > 0 && ldj_src >= (long)s->N * s->B + 2 && s->ldj >= (long)s->N * s->B + 2);
     PGL_CHECK_ARG(s->B >= 1 && s->B <= 32);
-    return pgl_k_flip_permute(to_state(s), J, ldj_src, strideJ, ST(st));
+    return pgl_k_flip_permute(*s, J, ldj_src, strideJ, ST(st));
 }
 int pgl_flip_apply_window(const pgl_flip_t* s, int window, void* st) {
     PGL_CHECK_ARG(s && s->M && s->d_idx && s->d_sign && s->d_cnt && s->batch_k && s->G && s->Ut && s->Wt && s->status);
     PGL_CHECK_ARG(s->ldu >= (long)s->N * s->B + 2 && s->ldu % 2 == 0 && s->ldj >= (long)s->N * s->B + 2 && s->nb > 0);
     PGL_CHECK_ARG(window >= 0);
-    return pgl_k_flip_apply(to_state(s), 1, 0, window, ST(st));
+    return pgl_k_flip_apply(*s, 1, 0, window, ST(st));
 }
 int pgl_flip_decide(const pgl_flip_t* s, int window, void* st) {
     PGL_CHECK_ARG(s && s->M && s->perm && s->u && s->rho && s->c0 && s->a && s->d_idx && s->d_sign && s->d_cnt && s->status && s->Lws);
     PGL_CHECK_ARG(s->B >= 1 && s->B <= 32 && window >= 0);
-    return pgl_k_flip_decide(to_state(s), window, ST(st));
+    return pgl_k_flip_decide(*s, window, ST(st));
 }
 
-static PglCholState to_cstate(const pgl_chol_t* s) {
-    return PglCholState{s->J, s->ldj, s->strideJ, s->a, s->act, s->ldact, s->na, s->Ac, s->ldc, s->strideC, s->hc, s->Tinv, s->z, s->ldz,
-                        s->W, s->b, s->nb, s->N, s->B, s->status};
-}
 int pgl_active_index(const pgl_chol_t* s, void* st) {
     PGL_CHECK_ARG(s && s->a && s->act && s->na && s->nb > 0 && s->ldact >= (long)s->N * s->B + 1);
-    return pgl_k_chol_index(to_cstate(s), ST(st));
+    return pgl_k_chol_index(*s, ST(st));
 }
 int pgl_sample_weights(const pgl_chol_t* s, int na_max, void* st) {
     PGL_CHECK_ARG(s && s->J && s->act && s->na && s->Ac && s->hc && s->Tinv && s->z && s->W && s->b && s->status);
     PGL_CHECK_ARG(na_max >= 1 && na_max <= s->N * s->B + 1 && s->ldc >= na_max + 1 && s->ldc % 2 == 0 && s->ldz >= na_max);
-    return pgl_k_chol_sample(to_cstate(s), na_max, ST(st));
+    return pgl_k_chol_sample(*s, na_max, ST(st));
 }
 
 }  // extern "C"

@@ -272,18 +272,24 @@ __global__ __launch_bounds__(256) void scatter_active_kernel(CholArgs g, long pl
 }  // namespace
 
 
-static CholArgs mk(const PglCholState& s) {
-    return CholArgs{s.J, s.ldj, s.strideJ, s.a, s.act, s.ldact, s.na, s.Ac, s.ldc, s.strideC, s.hc, s.Tinv, s.z, s.ldz, s.W, s.b, s.N, s.B, s.status};
+static CholArgs mk(const pgl_chol_t& s) {
+    CholArgs g{};
+    g.J = s.J; g.ldj = s.ldj; g.strideJ = s.strideJ;
+    g.a = s.a; g.act = s.act; g.ldact = s.ldact; g.na = s.na;
+    g.Ac = s.Ac; g.ldc = s.ldc; g.strideC = s.strideC; g.hc = s.hc; g.Tinv = s.Tinv;
+    g.z = s.z; g.ldz = s.ldz; g.W = s.W; g.b = s.b;
+    g.N = s.N; g.B = s.B; g.status = s.status;
+    return g;
 }
 
-int pgl_k_chol_index(const PglCholState& s, hipStream_t st) {
+int pgl_k_chol_index(const pgl_chol_t& s, hipStream_t st) {
     hipLaunchKernelGGL(active_index_kernel, dim3(s.nb), dim3(64), 0, st, mk(s));
     PGL_CHECK_LAUNCH();
     return PGL_OK;
 }
 
 // na_max: host-side upper bound of the active sizes (every neuron stops at its own na[n])
-int pgl_k_chol_sample(const PglCholState& s, int na_max, hipStream_t st) {
+int pgl_k_chol_sample(const pgl_chol_t& s, int na_max, hipStream_t st) {
     CholArgs g = mk(s);
     if (na_max <= 0) return PGL_OK;
     hipLaunchKernelGGL(gather_active_kernel, dim3((na_max + 63) / 64, (na_max + 63) / 64, s.nb), dim3(256), 0, st, g);

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <atomic>
+#include "../../include/pyglm_hip.h"
 
 #define PGL_OK 0
 #define PGL_ERR_ARG 1
@@ -92,44 +93,15 @@ int pgl_launch_update_rows(const PglGemmArgs& a, int row0, int nrows, hipStream_
 // 8 zeroed per-XCD work counters for one persistent launch on stream st (a ring of slots owned by the library; pgl_gemm.hip)
 int* pgl_sched_slot(hipStream_t st);
 
-// ---- host-side views of the C-ABI structs (pgl_flip_t / pgl_chol_t of include/pyglm_hip.h), shared by the translation units
-struct PglFlipState {
-    double* M; long ldj; long strideM; int nb, N, B;
-    const int* perm; const double* u; const double* rho; const double* c0; int* a; const int* skip;
-    int* d_idx; double* d_sign; int* d_cnt; int* batch_k; double* G; double* Lws; double* Ut; double* Wt; long ldu; int* status;
-    int permuted; double* logodds;
-};
-struct PglCholState {
-    const double* J; long ldj; long strideJ; const int* a; int* act; long ldact; int* na;
-    double* Ac; long ldc; long strideC; double* hc; double* Tinv; const double* z; long ldz; double* W; double* b; int nb, N, B; int* status;
-};
-
 // kernels' host launchers (defined next to their kernels)
 int pgl_k_philox_words(uint64_t, uint32_t, uint32_t, uint64_t, uint64_t, uint32_t*, size_t, hipStream_t);
 int pgl_k_pg_draw(const double*, const double*, double*, size_t, uint64_t, uint64_t, uint64_t, hipStream_t);
 int pgl_k_row_stats(const int* a, const double* W, double* out, int N, int B, int nloc, int n0, hipStream_t st);
-int pgl_k_pg_loglik(double*, long, const double*, const double*, long, double*, long, double*, long, double*, double*, int, int, int, int, double,
-                    const double* param, const double* hooks, long ldh, uint64_t, uint64_t, uint64_t, uint64_t, hipStream_t);
-int pgl_k_pg_loglik_nblk(int);
 int pgl_k_colsum_partials(const double* part, int nblk, int ncol, double* out, int accumulate, hipStream_t st);   // out[n] (+)= sum_b part[b][n], b ascending
-// posterior accumulators (pgl_summary.hip)
-struct PglSummaryFold {
-    const double* Psi; long ld;         // [T][ld] X.w as pgl_activation left it (bias not added; not written); Y and the accumulators share ld
-    const double* bias; const double* Y;
-    double* llpart; double* ll_out; int accumulate;
-    int T, nloc, obs; double xi; const double* param; const double* hooks; long ldh; const double* inv_eta;
-    double* rmean; double* rM2;         // rates: Welford mean / M2 of E[y | psi], or null
-    const int* link; int link0;         // link code per neuron, or null: link0 for all (0 logistic, 1 identity, 2 par * exp, 3 par * logistic)
-    const double* link_par; double link_par0;
-    double* lmean; double* lM2; double* lse_m; double* lse_s;   // pointwise: Welford of the term l and its streaming log-sum-exp, or null
-    int k;                              // 1-based index of the sample being folded
-};
-int pgl_k_summary_fold(const PglSummaryFold& f, hipStream_t st);
+// posterior accumulators (pgl_summary.hip; pgl_k_summary_fold and the passes over Psi: pgl_obs.h)
 int pgl_k_summary_state(const int* a, const double* Wt, long ldw, const double* bias, double* edge, double* wmean, double* wM2, double* bmean,
                         double* bM2, int N, int B, int nloc, int k, hipStream_t st);
 int pgl_k_summary_colsum(const double* V, long ldv, int T, int nloc, double* part, double* out, int accumulate, hipStream_t st);
-int pgl_k_gaussian_stats(double*, long, const double*, const double*, long, const double*, double*, long, double*, long, double*, double*, int, int,
-                         int, hipStream_t);
 int pgl_k_scaled_gram(const double*, long, const double*, double*, long, long, int, int, hipStream_t);
 int pgl_k_basis_conv(const double*, long, const double*, double*, long, double*, long, int, int, int, int, int, hipStream_t);
 int pgl_k_transpose(const double*, long, double*, long, int, int, hipStream_t);
@@ -151,18 +123,19 @@ int pgl_k_i8_planes(const double*, long, int transposed, const double*, long, co
 int pgl_k_i8_gram(const int8_t*, long, int, const int8_t*, int8_t*, int8_t*, int, int, int, int, int, hipStream_t);
 long pgl_k_i8_kp(int);
 int pgl_k_i8_crt(const int8_t*, const int8_t*, const double*, const double*, double*, long, long, int, int, int, int, hipStream_t);
-int pgl_k_flip_apply(const PglFlipState&, int, int, int, hipStream_t);
-int pgl_k_flip_apply_pair(const PglFlipState&, int phase, int window, int* ws, hipStream_t);
-int pgl_k_flip_permute(const PglFlipState&, const double*, long, long, hipStream_t);
-int pgl_k_flip_decide(const PglFlipState&, int, hipStream_t);
-int pgl_k_flip_pivot_list(const PglFlipState&, int*, long, int*, hipStream_t);
-int pgl_k_flip_pivot_chunk(const PglFlipState&, const int*, long, const int*, int, int, hipStream_t);
+// the flips and the weight draw take the C ABI's own argument blocks (pgl_flip_t / pgl_chol_t of include/pyglm_hip.h)
+int pgl_k_flip_apply(const pgl_flip_t&, int, int, int, hipStream_t);
+int pgl_k_flip_apply_pair(const pgl_flip_t&, int phase, int window, int* ws, hipStream_t);
+int pgl_k_flip_permute(const pgl_flip_t&, const double*, long, long, hipStream_t);
+int pgl_k_flip_decide(const pgl_flip_t&, int, hipStream_t);
+int pgl_k_flip_pivot_list(const pgl_flip_t&, int*, long, int*, hipStream_t);
+int pgl_k_flip_pivot_chunk(const pgl_flip_t&, const int*, long, const int*, int, int, hipStream_t);
 int pgl_k_flip_kmax(void);
 int pgl_k_flip_window_blocks(int);
-int pgl_k_chol_index(const PglCholState&, hipStream_t);
+int pgl_k_chol_index(const pgl_chol_t&, hipStream_t);
 // flips + weight draw of a small model (D + 2 <= pgl_k_small_max_rows(), B <= 16) as one launch, one workgroup per neuron (pgl_small.hip)
 bool pgl_k_small_fits(int N, int B);
 int pgl_k_small_max_rows(void);
 int pgl_k_small_tail(const double* J, long ldj, long strideJ, int nb, int N, int B, const int* perm, const double* u, const double* rho, const double* c0,
                      int* a, const int* skip, const double* z, long ldz, double* W, double* b, int* status, double* logodds, hipStream_t st);
-int pgl_k_chol_sample(const PglCholState&, int, hipStream_t);
+int pgl_k_chol_sample(const pgl_chol_t&, int, hipStream_t);

@@ -27,83 +27,38 @@ __global__ __launch_bounds__(256) void pg_draw_kernel(const double* __restrict__
 }
 
 // ------------------------------------------------------------------ psi -> (omega, kappa, log-lik)   regression.py:491-511
-// Psi is T x nloc (time-major, from the activation GEMM, bias not yet added).  Lane = neuron column, wave = row:
-// a wave reads/writes 64 consecutive doubles of one time bin.  Each block covers ROWS time bins of one 64-neuron
-// column group and leaves one log-likelihood partial per neuron; a second pass adds partials in a fixed order
-// (deterministic; no atomics).
-// (block shape, argument block and the per-cell terms: pgl_obs.h, shared with the posterior accumulators of pgl_summary.hip)
+// Psi is T x nloc (time-major, from the activation GEMM, bias not yet added).  One pass in the shared walk of pgl_obs.h (argument block,
+// per-cell terms and order of addition: there, shared with the posterior accumulators of pgl_summary.hip): each block leaves one
+// log-likelihood partial per neuron, a second pass adds the partials in a fixed order (deterministic; no atomics).
 
-__global__ __launch_bounds__(256) void pg_loglik_kernel(PgLlArgs g) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = blockIdx.y * 64 + lane;
-    const int t0 = blockIdx.x * PGLL_ROWS;
-    __shared__ double red[4][64];
-    double ll = 0.0;
-    if (n < g.nloc) {
-        const double bn = g.bias ? g.bias[n] : 0.0;
-        const uint64_t stream = ((uint64_t)g.sweep << 32) | (uint64_t)(uint32_t)(g.neuron0 + n);
-        for (int r = wave; r < PGLL_ROWS; r += 4) {
-            const int t = t0 + r;
-            if (t >= g.T) break;
-            const double psi = g.Psi[(long)t * g.ldpsi + n] + bn;
-            g.Psi[(long)t * g.ldpsi + n] = psi;
-            const double y = g.Y[(long)t * g.ldy + n];
-            if (g.obs == 2) {
-                const double ie = g.inv_eta[n], r = y - psi;
-                ll += r * r;
-                if (g.Kappa) g.Kappa[(long)t * g.ldk + n] = y * ie;
-                if (g.Omega) g.Omega[(long)t * g.ldo + n] = ie;
-                continue;
-            }
-            double a, b, logc;
-            pg_abc(g, n, t, y, a, b, logc);
-            ll += pg_ll_term(logc, a, b, psi);
-            if (g.Kappa) g.Kappa[(long)t * g.ldk + n] = a - 0.5 * b;
-            if (g.Omega) g.Omega[(long)t * g.ldo + n] = pgl_pg_draw(b, psi, g.seed, stream, g.elem0 + (uint64_t)t);
-        }
+// one cell: psi = X.w + bias written back, its term added to ll, kappa and the omega drawn (Gaussian: the constant 1/eta) stored
+__device__ __forceinline__ void pg_cell(const PgLlArgs& g, int n, long t, double& ll) {
+    const double psi = g.Psi[t * g.ldpsi + n] + (g.bias ? g.bias[n] : 0.0);
+    g.Psi[t * g.ldpsi + n] = psi;
+    const double y = g.Y[t * g.ldy + n];
+    if (g.obs == 2) {
+        double omega, kappa;
+        gauss_cell(y, psi, g.inv_eta[n], ll, omega, kappa);
+        if (g.Kappa) g.Kappa[t * g.ldk + n] = kappa;
+        if (g.Omega) g.Omega[t * g.ldo + n] = omega;
+        return;
     }
-    red[wave][lane] = ll;
-    __syncthreads();
-    if (wave == 0 && n < g.nloc) g.llpart[(long)blockIdx.x * g.nloc + n] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+    double a, b, logc;
+    pg_abc(g, n, t, y, a, b, logc);
+    ll += pg_ll_term(logc, a, b, psi);
+    if (g.Kappa) g.Kappa[t * g.ldk + n] = a - 0.5 * b;
+    if (g.Omega) {
+        const uint64_t stream = ((uint64_t)g.sweep << 32) | (uint64_t)(uint32_t)(g.neuron0 + n);
+        g.Omega[t * g.ldo + n] = pgl_pg_draw(b, psi, g.seed, stream, g.elem0 + (uint64_t)t);
+    }
 }
 
-// The same for a NARROW shard (fewer than 64 local neurons: a small model, BASELINE configs[0]): with a lane per neuron most lanes would idle
-// and every busy one walk 16 time bins one after the other (0.37 of that sweep's 1.0 ms of GPU time at N = 4).  Here the block's
-// PGLL_ROWS x nloc cells are dealt to its 256 threads, each cell's log-likelihood term goes to LDS, and then thread (wave, neuron) adds ITS rows'
-// terms in the order the kernel above adds them -- the same numbers in the same order: the same log-likelihood to the last bit, whatever the shard.
+__global__ __launch_bounds__(256) void pg_loglik_kernel(PgLlArgs g) {
+    psi_walk(g.T, g.nloc, g.llpart, [&](int n, long t, double& ll) { pg_cell(g, n, t, ll); });
+}
+
 __global__ __launch_bounds__(256) void pg_loglik_narrow_kernel(PgLlArgs g) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nl = g.nloc;                                    // < 64
-    const int t0 = blockIdx.x * PGLL_ROWS;
-    __shared__ double term[PGLL_ROWS][64];
-    __shared__ double red[4][64];
-    for (int c = tid; c < PGLL_ROWS * nl; c += 256) {
-        const int r = c / nl, n = c - r * nl, t = t0 + r;
-        double v = 0.0;
-        if (t < g.T) {
-            const double bn = g.bias ? g.bias[n] : 0.0;
-            const uint64_t stream = ((uint64_t)g.sweep << 32) | (uint64_t)(uint32_t)(g.neuron0 + n);
-            const double psi = g.Psi[(long)t * g.ldpsi + n] + bn;
-            g.Psi[(long)t * g.ldpsi + n] = psi;
-            const double y = g.Y[(long)t * g.ldy + n];
-            double a, b, logc;
-            pg_abc(g, n, t, y, a, b, logc);
-            v = pg_ll_term(logc, a, b, psi);
-            if (g.Kappa) g.Kappa[(long)t * g.ldk + n] = a - 0.5 * b;
-            if (g.Omega) g.Omega[(long)t * g.ldo + n] = pgl_pg_draw(b, psi, g.seed, stream, g.elem0 + (uint64_t)t);
-        }
-        term[r][n] = v;
-    }
-    __syncthreads();
-    double ll = 0.0;
-    if (lane < nl)
-        for (int r = wave; r < PGLL_ROWS; r += 4) {
-            if (t0 + r >= g.T) break;
-            ll += term[r][lane];
-        }
-    red[wave][lane] = ll;
-    __syncthreads();
-    if (wave == 0 && lane < nl) g.llpart[(long)blockIdx.x * nl + lane] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+    psi_walk_narrow(g.T, g.nloc, g.llpart, [&](int n, long t, double& ll) { pg_cell(g, n, t, ll); });
 }
 
 __global__ void colsum_partials_kernel(const double* __restrict__ part, int nblk, int ncol, double* __restrict__ out, int accumulate) {
@@ -295,28 +250,12 @@ int pgl_k_row_stats(const int* a, const double* W, double* out, int N, int B, in
     return PGL_OK;
 }
 
-int pgl_k_pg_loglik(double* Psi, long ldpsi, const double* bias, const double* Y, long ldy, double* Omega, long ldo, double* Kappa, long ldk,
-                    double* llpart, double* ll_out, int accumulate, int T, int nloc, int obs, double xi, const double* param, const double* hooks,
-                    long ldh, uint64_t seed, uint64_t sweep, uint64_t neuron0, uint64_t elem0, hipStream_t st) {
-    PgLlArgs a{Psi, ldpsi, bias, Y, ldy, Omega, ldo, Kappa, ldk, llpart, T, nloc, obs, xi, nullptr, seed, sweep, neuron0, elem0, param, hooks, ldh};
-    const int nblk = (T + PGLL_ROWS - 1) / PGLL_ROWS;
-    if (nloc < 64 && obs != 2) hipLaunchKernelGGL(pg_loglik_narrow_kernel, dim3(nblk), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(pg_loglik_kernel, dim3(nblk, (nloc + 63) / 64), dim3(256), 0, st, a);
+int pgl_k_pg_loglik(const PgLlArgs& a, double* ll_out, int accumulate, hipStream_t st) {
+    const bool narrow = psi_narrow(a.nloc, a.obs);
+    if (narrow) hipLaunchKernelGGL(pg_loglik_narrow_kernel, psi_grid(a.T, a.nloc, narrow), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(pg_loglik_kernel, psi_grid(a.T, a.nloc, narrow), dim3(256), 0, st, a);
     PGL_CHECK_LAUNCH();
-    hipLaunchKernelGGL(colsum_partials_kernel, dim3((nloc + 255) / 256), dim3(256), 0, st, llpart, nblk, nloc, ll_out, accumulate);
-    PGL_CHECK_LAUNCH();
-    return PGL_OK;
-}
-
-int pgl_k_gaussian_stats(double* Psi, long ldpsi, const double* bias, const double* Y, long ldy, const double* inv_eta, double* Omega, long ldo,
-                         double* Kappa, long ldk, double* part, double* sse_out, int accumulate, int T, int nloc, hipStream_t st) {
-    PgLlArgs a{Psi, ldpsi, bias, Y, ldy, Omega, ldo, Kappa, ldk, part, T, nloc, 2, 1.0, inv_eta, 0, 0, 0, 0, nullptr, nullptr, 0};
-    const int nblk = (T + PGLL_ROWS - 1) / PGLL_ROWS;
-    hipLaunchKernelGGL(pg_loglik_kernel, dim3(nblk, (nloc + 63) / 64), dim3(256), 0, st, a);
-    PGL_CHECK_LAUNCH();
-    hipLaunchKernelGGL(colsum_partials_kernel, dim3((nloc + 255) / 256), dim3(256), 0, st, part, nblk, nloc, sse_out, accumulate);
-    PGL_CHECK_LAUNCH();
-    return PGL_OK;
+    return pgl_k_colsum_partials(a.llpart, psi_row_blocks(a.T), a.nloc, ll_out, accumulate, st);
 }
 
 int pgl_k_scaled_gram(const double* G0, long ldg, const double* inv_eta, double* J, long ldj, long strideJ, int D, int nb, hipStream_t st) {
@@ -325,8 +264,6 @@ int pgl_k_scaled_gram(const double* G0, long ldg, const double* inv_eta, double*
     PGL_CHECK_LAUNCH();
     return PGL_OK;
 }
-
-int pgl_k_pg_loglik_nblk(int T) { return (T + PGLL_ROWS - 1) / PGLL_ROWS; }
 
 int pgl_k_colsum_partials(const double* part, int nblk, int ncol, double* out, int accumulate, hipStream_t st) {
     hipLaunchKernelGGL(colsum_partials_kernel, dim3((ncol + 255) / 256), dim3(256), 0, st, part, nblk, ncol, out, accumulate);

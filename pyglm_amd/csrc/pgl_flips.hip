@@ -746,19 +746,30 @@ int pgl_k_flip_window_blocks(int B) {
     return r < 1 ? 0 : r;
 }
 
+// the kernels' argument block from the caller's state; R (blocks per window), c_begin and row_off belong to the launch
+static FlipArgs mk(const pgl_flip_t& s, int R, int c_begin = 0, const int* row_off = nullptr) {
+    FlipArgs g{};
+    g.M = s.M; g.ldj = s.ldj; g.strideM = s.strideM;
+    g.N = s.N; g.B = s.B; g.R = R;
+    g.perm = s.perm; g.u = s.u; g.rho = s.rho; g.c0 = s.c0; g.a = s.a; g.skip = s.skip;
+    g.d_idx = s.d_idx; g.d_sign = s.d_sign; g.d_cnt = s.d_cnt; g.batch_k = s.batch_k;
+    g.G = s.G; g.Lws = s.Lws; g.Ut = s.Ut; g.Wt = s.Wt; g.ldu = s.ldu;
+    g.status = s.status; g.permuted = s.visit_order; g.c_begin = c_begin; g.logodds = s.logodds; g.row_off = row_off;
+    return g;
+}
+
 // apply the pivot list currently in (d_idx, d_sign, d_cnt) to every neuron's tableau
 // window >= 0 (visit-order tableau only): the pivots lie in proposal window `window`, whose rows -- like those of all earlier windows --
 // are dead afterwards: only the trailing square is updated, the pivot rows and columns are not rewritten.
-int pgl_k_flip_apply(const PglFlipState& s, int have_G, int max_pivots, int window, hipStream_t st) {
+int pgl_k_flip_apply(const pgl_flip_t& s, int have_G, int max_pivots, int window, hipStream_t st) {
     const int R_ = pgl_k_flip_window_blocks(s.B);
     const int Md_ = s.N * s.B + 2;
     int r0 = 0;                      // first live row / column
-    if (window >= 0 && s.permuted) {
+    if (window >= 0 && s.visit_order) {
         if ((long)(window + 1) * R_ >= s.N) return PGL_OK;          // last window: nothing is read afterwards
         r0 = ((window + 1) * R_ * s.B) & ~1;
     }
-    FlipArgs g{s.M, s.ldj, s.strideM, s.N, s.B, R_, s.perm, s.u, s.rho, s.c0, s.a, s.skip, s.d_idx, s.d_sign, s.d_cnt,
-               s.batch_k, s.G, s.Lws, s.Ut, s.Wt, s.ldu, s.status, s.permuted, r0, s.logodds};
+    FlipArgs g = mk(s, R_, r0);
     const size_t lds_inv = ((size_t)KMAX + 128 * 129) * sizeof(double);
     static PglPerDevice once;
     if (int rc = pgl_set_dynamic_lds(reinterpret_cast<const void*>(invert_kernel), lds_inv, once)) return rc;
@@ -779,7 +790,7 @@ int pgl_k_flip_apply(const PglFlipState& s, int have_G, int max_pivots, int wind
             return pgl_launch_gemm(PGL_GEMM_PLAIN, q, st);
         };
         struct Rec {
-            static int inv(const decltype(block_gemm)& gemm, const PglFlipState& s, const FlipArgs& g, double* Akk, int o, int n, hipStream_t st) {
+            static int inv(const decltype(block_gemm)& gemm, const pgl_flip_t& s, const FlipArgs& g, double* Akk, int o, int n, hipStream_t st) {
                 if (n == KB2) {
                     hipLaunchKernelGGL(invert128_kernel, dim3(s.nb), dim3(256), 0, st, g, (const double*)Akk, s.G, o);
                     PGL_CHECK_LAUNCH();
@@ -871,13 +882,12 @@ __global__ __launch_bounds__(256) void pair_plan_second_kernel(const int* __rest
     if (n < nb) ws[3 * nb + n] = ws[n] + batch_k[n];
 }
 
-int pgl_k_flip_apply_pair(const PglFlipState& s, int phase, int window, int* ws, hipStream_t st) {
+int pgl_k_flip_apply_pair(const pgl_flip_t& s, int phase, int window, int* ws, hipStream_t st) {
     const int R_ = pgl_k_flip_window_blocks(s.B);
     const int Md = s.N * s.B + 2;
-    if (!s.permuted || (long)(window + 1) * R_ >= s.N) return PGL_OK;          // last window: nothing is read afterwards
+    if (!s.visit_order || (long)(window + 1) * R_ >= s.N) return PGL_OK;          // last window: nothing is read afterwards
     const int r0 = ((window + 1) * R_ * s.B) & ~1;                                // first live row / column after `window`
-    FlipArgs g{s.M, s.ldj, s.strideM, s.N, s.B, R_, s.perm, s.u, s.rho, s.c0, s.a, s.skip, s.d_idx, s.d_sign, s.d_cnt,
-               s.batch_k, s.G, s.Lws, s.Ut, s.Wt, s.ldu, s.status, s.permuted, r0, s.logodds, phase ? ws : nullptr};
+    FlipArgs g = mk(s, R_, r0, phase ? ws : nullptr);
     hipLaunchKernelGGL(gather_panel_kernel, dim3((unsigned)((s.ldu - r0 + GT - 1) / GT), KMAX / GT, s.nb), dim3(256), 0, st, g);
     PGL_CHECK_LAUNCH();
     const int ncol = (int)s.ldu - r0;
@@ -914,9 +924,9 @@ int pgl_k_flip_apply_pair(const PglFlipState& s, int phase, int window, int* ws,
     return pgl_launch_gemm(PGL_GEMM_TRI1, t, st);
 }
 
-int pgl_k_flip_permute(const PglFlipState& s, const double* J, long ldjs, long strideJ, hipStream_t st) {
-    FlipArgs g{s.M, s.ldj, s.strideM, s.N, s.B, 0, s.perm, s.u, s.rho, s.c0, s.a, s.skip, s.d_idx, s.d_sign, s.d_cnt,
-               s.batch_k, s.G, s.Lws, s.Ut, s.Wt, s.ldu, s.status, 1, 0, s.logodds};
+int pgl_k_flip_permute(const pgl_flip_t& s, const double* J, long ldjs, long strideJ, hipStream_t st) {
+    FlipArgs g = mk(s, 0);
+    g.permuted = 1;
     const dim3 grid(1, s.N + 2, s.nb);
 #define PGL_PERMUTE(b_) case b_: hipLaunchKernelGGL(permute_tableau_kernel<b_>, grid, dim3(256), 0, st, g, J, ldjs, strideJ); break;
     switch (s.B) {
@@ -928,11 +938,10 @@ int pgl_k_flip_permute(const PglFlipState& s, const double* J, long ldjs, long s
     return PGL_OK;
 }
 
-int pgl_k_flip_decide(const PglFlipState& s, int window, hipStream_t st) {
+int pgl_k_flip_decide(const pgl_flip_t& s, int window, hipStream_t st) {
     const int R = pgl_k_flip_window_blocks(s.B);
     if (R < 1) { pgl_set_error("B=%d exceeds the window capacity %d", s.B, KWIN); return PGL_ERR_ARG; }
-    FlipArgs g{s.M, s.ldj, s.strideM, s.N, s.B, R, s.perm, s.u, s.rho, s.c0, s.a, s.skip, s.d_idx, s.d_sign, s.d_cnt,
-               s.batch_k, s.G, s.Lws, s.Ut, s.Wt, s.ldu, s.status, s.permuted, 0, s.logodds};
+    FlipArgs g = mk(s, R);
     const size_t lds = pgl_k_flip_lds_decide(s.B, R);
     // (one LDS high-water mark for all instantiations: the request is raised on each of them whenever any launch needs more)
 #define PGL_DECIDE(b_)                                                                                                      \
@@ -950,18 +959,16 @@ int pgl_k_flip_decide(const PglFlipState& s, int window, hipStream_t st) {
     return PGL_OK;
 }
 
-int pgl_k_flip_pivot_list(const PglFlipState& s, int* list, long ldl, int* count, hipStream_t st) {
-    FlipArgs g{s.M, s.ldj, s.strideM, s.N, s.B, 0, s.perm, s.u, s.rho, s.c0, s.a, s.skip, s.d_idx, s.d_sign, s.d_cnt,
-               s.batch_k, s.G, s.Lws, s.Ut, s.Wt, s.ldu, s.status, s.permuted, 0, s.logodds};
+int pgl_k_flip_pivot_list(const pgl_flip_t& s, int* list, long ldl, int* count, hipStream_t st) {
+    FlipArgs g = mk(s, 0);
     hipLaunchKernelGGL(pivot_list_kernel, dim3(s.nb), dim3(256), 0, st, g, list, ldl, count);
     PGL_CHECK_LAUNCH();
     return PGL_OK;
 }
 
-int pgl_k_flip_pivot_chunk(const PglFlipState& s, const int* list, long ldl, const int* count, int chunk, int per_chunk, hipStream_t st) {
+int pgl_k_flip_pivot_chunk(const pgl_flip_t& s, const int* list, long ldl, const int* count, int chunk, int per_chunk, hipStream_t st) {
     if (per_chunk < 1 || per_chunk > KMAX) { pgl_set_error("pivot chunk of %d rows (max %d)", per_chunk, KMAX); return PGL_ERR_ARG; }
-    FlipArgs g{s.M, s.ldj, s.strideM, s.N, s.B, 0, s.perm, s.u, s.rho, s.c0, s.a, s.skip, s.d_idx, s.d_sign, s.d_cnt,
-               s.batch_k, s.G, s.Lws, s.Ut, s.Wt, s.ldu, s.status, s.permuted, 0, s.logodds};
+    FlipArgs g = mk(s, 0);
     hipLaunchKernelGGL(pivot_chunk_kernel, dim3(s.nb), dim3(256), 0, st, g, list, ldl, count, chunk, per_chunk);
     PGL_CHECK_LAUNCH();
     return PGL_OK;

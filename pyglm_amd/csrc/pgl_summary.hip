@@ -3,24 +3,13 @@
 //
 // pgl_summary_fold is ONE pass over a data set's Psi.  It is HBM-bound: per cell it reads psi and y (16 B; + 24 B of a | b | log c in the hooks
 // mode), reads and writes the two rate accumulators (16 + 16 B) and, with the pointwise accumulators, four more (32 + 32 B).  Lane = neuron
-// column, wave = time bin, as in pg_loglik_kernel: a wave touches 64 consecutive doubles of a row in every array (they share the leading
-// dimension).  The log-likelihood goes through the block shape, the partials and the order of addition of pg_loglik_kernel /
-// pg_loglik_narrow_kernel (pgl_obs.h has the shared terms), so the per-neuron totals are those of pgl_pg_loglik_ex / pgl_gaussian_stats bit for
-// bit; the grid is therefore one block per PGLL_ROWS time bins and column group, not a capped grid-stride.  No atomics: every cell has one owner.
+// column, wave = time bin: a wave touches 64 consecutive doubles of a row in every array (they share the leading dimension).  The
+// log-likelihood goes through the shared walk of pgl_obs.h (block shape, partials, order of addition, and the per-cell terms), as
+// pg_loglik_kernel / pg_loglik_narrow_kernel do, so the per-neuron totals are those of pgl_pg_loglik_ex / pgl_gaussian_stats bit for bit.
 #include "pgl_common.h"
 #include "pgl_obs.h"
 
 namespace {
-
-// (OBS is a template parameter of the kernels: one observation model's arithmetic per instantiation, and the row loop is not unrolled.  The
-// Bernoulli, Gaussian and hooks passes carry no lgamma and fit 80-106 VGPRs, 4-6 waves per SIMD; with every model in one kernel all of them
-// ran at 244 VGPRs, 2 waves per SIMD, too few to cover the HBM latency.  The lgamma modes (obs 1, 3) stay at 220 VGPRs and are VALU-bound.)
-template <int OBS>
-__device__ __forceinline__ PgLlArgs obs_args(const PglSummaryFold& f) {
-    PgLlArgs g{};
-    g.obs = OBS; g.xi = f.xi; g.param = f.param; g.hooks = f.hooks; g.ldh = f.ldh;
-    return g;
-}
 
 // Welford step k (1-based) of (mean, M2) at index i with the new value x
 __device__ __forceinline__ void welford(double* __restrict__ mean, double* __restrict__ M2, long i, double x, double k) {
@@ -31,21 +20,20 @@ __device__ __forceinline__ void welford(double* __restrict__ mean, double* __res
 
 // one cell (t, n): adds its log-likelihood term (Gaussian: its squared residual, as pgl_gaussian_stats) to ll and folds the rate and the
 // pointwise term into their accumulators
-template <int OBS>
-__device__ __forceinline__ void fold_cell(const PglSummaryFold& f, const PgLlArgs& g, int n, long t, double& ll) {
-    const long i = t * f.ld + n;
+__device__ __forceinline__ void fold_cell(const PglSummaryFold& f, int n, long t, double& ll) {
+    const long i = t * f.ldpsi + n;
     const double bn = f.bias ? f.bias[n] : 0.0;
     const double psi = f.Psi[i] + bn;
     const double y = f.Y[i];
     const double kd = (double)f.k;
     double l;
-    if (OBS == 2) {
-        const double ie = f.inv_eta[n], r = y - psi;
-        ll += r * r;
+    if (f.obs == 2) {
+        double omega, kappa;
+        const double ie = f.inv_eta[n], r = gauss_cell(y, psi, ie, ll, omega, kappa);
         l = -0.5 * log(6.283185307179586 / ie) - 0.5 * (r * r) * ie;      // regression.py:399-403 with eta = 1 / inv_eta
     } else {
         double a, b, logc;
-        pg_abc(g, n, t, y, a, b, logc);
+        pg_abc(f, n, t, y, a, b, logc);
         l = pg_ll_term(logc, a, b, psi);
         ll += l;
     }
@@ -70,73 +58,25 @@ __device__ __forceinline__ void fold_cell(const PglSummaryFold& f, const PgLlArg
     }
 }
 
-// block shape and order of addition of pg_loglik_kernel
+// OBS is a template parameter of the kernels: f.obs = OBS (what pgl_k_summary_fold's switch launched) makes the model a constant, one
+// observation model's arithmetic per instantiation.  The Bernoulli, Gaussian and hooks passes carry no lgamma and fit 80-106 VGPRs, 4-6
+// waves per SIMD; with every model in one kernel all of them ran at 244 VGPRs, 2 waves per SIMD, too few to cover the HBM latency.  The
+// lgamma modes (obs 1, 3) stay at 220 VGPRs and are VALU-bound.
 template <int OBS>
 __global__ __launch_bounds__(256) void summary_fold_kernel(PglSummaryFold f) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = blockIdx.y * 64 + lane;
-    const int t0 = blockIdx.x * PGLL_ROWS;
-    __shared__ double red[4][64];
-    const PgLlArgs g = obs_args<OBS>(f);
-    double ll = 0.0;
-    if (n < f.nloc) {
-#pragma unroll 1
-        for (int r = wave; r < PGLL_ROWS; r += 4) {
-            const int t = t0 + r;
-            if (t >= f.T) break;
-            fold_cell<OBS>(f, g, n, t, ll);
-        }
-    }
-    red[wave][lane] = ll;
-    __syncthreads();
-    if (wave == 0 && n < f.nloc) f.llpart[(long)blockIdx.x * f.nloc + n] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+    f.obs = OBS;
+    psi_walk(f.T, f.nloc, f.llpart, [&](int n, long t, double& ll) { fold_cell(f, n, t, ll); });
 }
 
-// the same for a narrow shard (fewer than 64 local neurons), in the shape and order of pg_loglik_narrow_kernel
 template <int OBS>
 __global__ __launch_bounds__(256) void summary_fold_narrow_kernel(PglSummaryFold f) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nl = f.nloc;                                    // < 64
-    const int t0 = blockIdx.x * PGLL_ROWS;
-    __shared__ double term[PGLL_ROWS][64];
-    __shared__ double red[4][64];
-    const PgLlArgs g = obs_args<OBS>(f);
-#pragma unroll 1
-    for (int c = tid; c < PGLL_ROWS * nl; c += 256) {
-        const int r = c / nl, n = c - r * nl, t = t0 + r;
-        double v = 0.0;
-        if (t < f.T) fold_cell<OBS>(f, g, n, t, v);
-        term[r][n] = v;
-    }
-    __syncthreads();
-    double ll = 0.0;
-    if (lane < nl)
-        for (int r = wave; r < PGLL_ROWS; r += 4) {
-            if (t0 + r >= f.T) break;
-            ll += term[r][lane];
-        }
-    red[wave][lane] = ll;
-    __syncthreads();
-    if (wave == 0 && lane < nl) f.llpart[(long)blockIdx.x * nl + lane] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+    f.obs = OBS;
+    psi_walk_narrow(f.T, f.nloc, f.llpart, [&](int n, long t, double& ll) { fold_cell(f, n, t, ll); });
 }
 
-// per-neuron sums over time of V [T][ldv]: block partials in the shape above (a column's partial never depends on its neighbours or on
-// how many there are), added up by colsum_partials_kernel
+// per-neuron sums over time of V [T][ldv]: block partials of the same walk, added up by colsum_partials_kernel
 __global__ __launch_bounds__(256) void summary_colpart_kernel(const double* __restrict__ V, long ldv, int T, int nloc, double* __restrict__ part) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = blockIdx.y * 64 + lane;
-    const int t0 = blockIdx.x * PGLL_ROWS;
-    __shared__ double red[4][64];
-    double s = 0.0;
-    if (n < nloc)
-        for (int r = wave; r < PGLL_ROWS; r += 4) {
-            const int t = t0 + r;
-            if (t >= T) break;
-            s += V[(long)t * ldv + n];
-        }
-    red[wave][lane] = s;
-    __syncthreads();
-    if (wave == 0 && n < nloc) part[(long)blockIdx.x * nloc + n] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+    psi_walk(T, nloc, part, [&](int n, long t, double& s) { s += V[t * ldv + n]; });
 }
 
 // the shard's state: one thread per entry (n, d) of the effective weights a * W -- read from the k-major copy the activation contracts with --
@@ -165,22 +105,22 @@ __global__ __launch_bounds__(256) void summary_state_kernel(const int* __restric
 }  // namespace
 
 template <int OBS>
-static void launch_fold(const PglSummaryFold& f, int nblk, hipStream_t st) {
-    if (f.nloc < 64 && OBS != 2) hipLaunchKernelGGL(summary_fold_narrow_kernel<OBS>, dim3(nblk), dim3(256), 0, st, f);
-    else hipLaunchKernelGGL(summary_fold_kernel<OBS>, dim3(nblk, (f.nloc + 63) / 64), dim3(256), 0, st, f);
+static void launch_fold(const PglSummaryFold& f, hipStream_t st) {
+    const bool narrow = psi_narrow(f.nloc, OBS);
+    if (narrow) hipLaunchKernelGGL(summary_fold_narrow_kernel<OBS>, psi_grid(f.T, f.nloc, narrow), dim3(256), 0, st, f);
+    else hipLaunchKernelGGL(summary_fold_kernel<OBS>, psi_grid(f.T, f.nloc, narrow), dim3(256), 0, st, f);
 }
 
 int pgl_k_summary_fold(const PglSummaryFold& f, hipStream_t st) {
-    const int nblk = (f.T + PGLL_ROWS - 1) / PGLL_ROWS;
     switch (f.obs) {
-        case 0: launch_fold<0>(f, nblk, st); break;
-        case 1: launch_fold<1>(f, nblk, st); break;
-        case 2: launch_fold<2>(f, nblk, st); break;
-        case 3: launch_fold<3>(f, nblk, st); break;
-        default: launch_fold<4>(f, nblk, st); break;
+        case 0: launch_fold<0>(f, st); break;
+        case 1: launch_fold<1>(f, st); break;
+        case 2: launch_fold<2>(f, st); break;
+        case 3: launch_fold<3>(f, st); break;
+        default: launch_fold<4>(f, st); break;
     }
     PGL_CHECK_LAUNCH();
-    return pgl_k_colsum_partials(f.llpart, nblk, f.nloc, f.ll_out, f.accumulate, st);
+    return pgl_k_colsum_partials(f.llpart, psi_row_blocks(f.T), f.nloc, f.ll_out, f.accumulate, st);
 }
 
 int pgl_k_summary_state(const int* a, const double* Wt, long ldw, const double* bias, double* edge, double* wmean, double* wM2, double* bmean,
@@ -193,8 +133,7 @@ int pgl_k_summary_state(const int* a, const double* Wt, long ldw, const double* 
 }
 
 int pgl_k_summary_colsum(const double* V, long ldv, int T, int nloc, double* part, double* out, int accumulate, hipStream_t st) {
-    const int nblk = (T + PGLL_ROWS - 1) / PGLL_ROWS;
-    hipLaunchKernelGGL(summary_colpart_kernel, dim3(nblk, (nloc + 63) / 64), dim3(256), 0, st, V, ldv, T, nloc, part);
+    hipLaunchKernelGGL(summary_colpart_kernel, psi_grid(T, nloc, false), dim3(256), 0, st, V, ldv, T, nloc, part);
     PGL_CHECK_LAUNCH();
-    return pgl_k_colsum_partials(part, nblk, nloc, out, accumulate, st);
+    return pgl_k_colsum_partials(part, psi_row_blocks(T), nloc, out, accumulate, st);
 }

@@ -9,7 +9,7 @@
 // from a and perm by pivot_list_kernel; the weight draw runs to the largest possible active size and stops per neuron at its own), so a
 // binder in any language gets the whole sweep from include/pyglm_hip.h, and pyglm_amd/engine.py is a thin caller of this function.
 #include "pgl_common.h"
-#include "../../include/pyglm_hip.h"
+#include "pgl_obs.h"
 #include <cmath>
 #include <tuple>
 #include <vector>
@@ -309,11 +309,15 @@ int pgl_sweep(const pgl_sweep_t* s, uint64_t seed, uint64_t sweep, void* hip_str
         }
         clk.toc(m);
         m = clk.tic(ST_PG, (double)d.T * nrun);
-        if (s->obs == 2) RC(pgl_k_gaussian_stats(d.Psi + nf, ldn, s->bias + nf, d.Y + nf, ldn, s->inv_eta + nf, d.OK + nf, 2 * ldn, d.OK + ldn + nf, 2 * ldn, d.llpart,
-                                                 s->ll + nf, i > 0, d.T, nrun, st));
-        else RC(pgl_k_pg_loglik(d.Psi + nf, ldn, s->bias + nf, d.Y + nf, ldn, d.OK + nf, 2 * ldn, d.OK + ldn + nf, 2 * ldn, d.llpart, s->ll + nf, i > 0, d.T, nrun,
-                                s->obs, s->xi, s->obs_param ? s->obs_param + nf : nullptr, s->obs == 4 ? d.hooks + nf : nullptr, ldn, seed, sweep,
-                                (uint64_t)(s->n0 + nf), d.elem0, st));
+        {   // the neurons [nf, nf + nrun): omega and kappa are the two halves of a row of OK
+            PgLlArgs q{};
+            q.Psi = d.Psi + nf; q.ldpsi = ldn; q.bias = s->bias + nf; q.Y = d.Y + nf; q.ldy = ldn; q.llpart = d.llpart; q.T = d.T; q.nloc = nrun;
+            q.obs = s->obs; q.xi = s->xi; q.param = s->obs_param ? s->obs_param + nf : nullptr;
+            q.hooks = s->obs == 4 ? d.hooks + nf : nullptr; q.ldh = ldn; q.inv_eta = s->obs == 2 ? s->inv_eta + nf : nullptr;
+            q.Omega = d.OK + nf; q.ldo = 2 * ldn; q.Kappa = d.OK + ldn + nf; q.ldk = 2 * ldn;
+            q.seed = seed; q.sweep = sweep; q.neuron0 = (uint64_t)(s->n0 + nf); q.elem0 = d.elem0;
+            RC(pgl_k_pg_loglik(q, s->ll + nf, i > 0, st));           // (Gaussian: s->ll then holds the sums of squared residuals)
+        }
         clk.toc(m);
         if (d.omega_override) {       // test hook: the reference fixtures inject omega
             if (hipMemcpy2DAsync(d.OK, (size_t)2 * ldn * sizeof(double), d.omega_override, (size_t)nloc * sizeof(double), (size_t)nloc * sizeof(double),
@@ -419,9 +423,13 @@ int pgl_sweep(const pgl_sweep_t* s, uint64_t seed, uint64_t sweep, void* hip_str
         // ---- collapsed flips (regression.py:282-320)
         auto mf = clk.tic(ST_FLIPS);
         if (!s->all_deterministic) {
-            PglFlipState fs{s->Mtab, ldj, strideJ, nbb, N, B, s->perm + (long)s0 * N, s->u + (long)s0 * N, s->rho + (long)s0 * N, c0 + (long)s0 * N,
-                            s->a + (long)s0 * N, s->skip + s0, s->d_idx, s->d_sign, s->d_cnt, s->batch_k, s->G, s->Lws, s->Ut, s->Wt_ws, ldj, s->status + s0,
-                            s->visit_order ? 1 : 0, s->logodds ? s->logodds + (long)s0 * N : nullptr};
+            pgl_flip_t fs{};
+            fs.M = s->Mtab; fs.ldj = ldj; fs.strideM = strideJ; fs.nb = nbb; fs.N = N; fs.B = B;
+            fs.perm = s->perm + (long)s0 * N; fs.u = s->u + (long)s0 * N; fs.rho = s->rho + (long)s0 * N; fs.c0 = c0 + (long)s0 * N;
+            fs.a = s->a + (long)s0 * N; fs.skip = s->skip + s0;
+            fs.d_idx = s->d_idx; fs.d_sign = s->d_sign; fs.d_cnt = s->d_cnt; fs.batch_k = s->batch_k;
+            fs.G = s->G; fs.Lws = s->Lws; fs.Ut = s->Ut; fs.Wt = s->Wt_ws; fs.ldu = ldj;
+            fs.status = s->status + s0; fs.visit_order = s->visit_order ? 1 : 0; fs.logodds = s->logodds ? s->logodds + (long)s0 * N : nullptr;
             if (s->visit_order) RC(pgl_k_flip_permute(fs, s->Jbuf, ldj, strideJ, st));
             else if (hipMemcpyAsync(s->Mtab, s->Jbuf, (size_t)nbb * strideJ * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess) {
                 pgl_set_error("tableau copy failed"); return PGL_ERR_HIP;
@@ -456,8 +464,12 @@ int pgl_sweep(const pgl_sweep_t* s, uint64_t seed, uint64_t sweep, void* hip_str
         clk.toc(mf);
         // ---- weights (regression.py:323-340); runs to the largest possible active size, every neuron stops at its own
         auto mw = clk.tic(ST_W);
-        PglCholState cs{s->Jbuf, ldj, strideJ, s->a + (long)s0 * N, s->act, D + 1, s->na, s->Ac, ldj, strideJ, s->hc, s->Tinv, s->z + (long)s0 * (D + 1), D + 1,
-                        s->W + (long)s0 * D, s->b + s0, nbb, N, B, s->status + s0};
+        pgl_chol_t cs{};
+        cs.J = s->Jbuf; cs.ldj = ldj; cs.strideJ = strideJ; cs.a = s->a + (long)s0 * N;
+        cs.act = s->act; cs.ldact = D + 1; cs.na = s->na;
+        cs.Ac = s->Ac; cs.ldc = ldj; cs.strideC = strideJ; cs.hc = s->hc; cs.Tinv = s->Tinv;
+        cs.z = s->z + (long)s0 * (D + 1); cs.ldz = D + 1; cs.W = s->W + (long)s0 * D; cs.b = s->b + s0;
+        cs.nb = nbb; cs.N = N; cs.B = B; cs.status = s->status + s0;
         RC(pgl_k_chol_index(cs, st));
         long na_bound = s->active_rows_bound > 0 && s->active_rows_bound <= D + 1 ? s->active_rows_bound : D + 1;
         RC(pgl_k_chol_sample(cs, (int)na_bound, st));

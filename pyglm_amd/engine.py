@@ -608,13 +608,17 @@ class GibbsEngine(object):
         self.Wt.copy_(torch.from_numpy(Wt))
         self.bias.copy_(torch.from_numpy(np.asarray(b, dtype=np.float64).reshape(self.nloc)))
 
+    def _activation(self, ds, st):
+        """queues Psi = X (a * W)' of data set ds for the whole shard (regression.py:195-201; bias not added), as its own stage"""
+        h = self._tic("activation", 2.0 * ds.T * self.D * self.nloc)
+        call("pgl_activation", ptr(ds.Xt), ds.Tp, ptr(self.Wt), self.ldn, ptr(ds.Psi), self.ldn, ds.T, self.Dp, self.nloc, st)
+        self._toc(h)
+
     def _psi_pass(self, draw, seed, sweep):
         """activation (regression.py:195-201) for the whole shard + PG/kappa/log-lik (:491-511). Returns ll (nloc,) device."""
         st = self._st()
         for i, ds in enumerate(self.datasets):
-            h = self._tic("activation", 2.0 * ds.T * self.D * self.nloc)
-            call("pgl_activation", ptr(ds.Xt), ds.Tp, ptr(self.Wt), self.ldn, ptr(ds.Psi), self.ldn, ds.T, self.Dp, self.nloc, st)
-            self._toc(h)
+            self._activation(ds, st)
             h = self._tic("pg_loglik", float(ds.T) * self.nloc)
             om = ds.OK if draw else None
             kp = ctypes.c_void_p(ds.OK.data_ptr() + 8 * self.ldn) if draw else None
@@ -710,9 +714,7 @@ class GibbsEngine(object):
         st = self._st()
         none2, none4 = (None, None), (None,) * 4
         for i, ds in enumerate(self.datasets):
-            h = self._tic("activation", 2.0 * ds.T * self.D * self.nloc)
-            call("pgl_activation", ptr(ds.Xt), ds.Tp, ptr(self.Wt), self.ldn, ptr(ds.Psi), self.ldn, ds.T, self.Dp, self.nloc, st)
-            self._toc(h)
+            self._activation(ds, st)
             h = self._tic("summary_fold", float(ds.T) * self.nloc)
             r, p = s.rate[i] if s.rate else none2, s.pw[i] if s.pw else none4
             call("pgl_summary_fold", ptr(ds.Psi), self.ldn, ptr(self.bias), ptr(ds.Y), ptr(ds.llpart), ptr(self.ll), int(i > 0), ds.T, self.nloc,
