@@ -380,6 +380,30 @@ size_t pgl_generate_work_bytes(int N, int B);
 int pgl_generate(const double* Wm, const double* bias, const double* basis, int N, int B, int L, int obs, double noise_scale, const double* U,
                  double* ring, double* Y, long t0, int Tc, void* work, int* status, void* hip_stream);
 
+/* Posterior predictive simulation: bins [t0, t0 + Tc) of R replicate trajectories of the fitted model in ONE cooperative launch, with one
+ * grid barrier per bin for all R.  Stands for the loop of pyglm/models.py:98-151 run R times, and for the per-neuron draws of the
+ * regressions' rvs (pyglm/regression.py:528-541; the count models are this project's), with two differences that a predictive check
+ * needs: the activation is that of `means` and log_likelihood(),
+ *   psi_t[r][n] = sum_{d < N*B} Wm[n][d] x_t[r][d] + bias[n],  Wm [N][N*B] = a*W;   x_t[r][m][:] = sum_{l < L} Y_r[t-1-l][m] basis[l][:],
+ * and neuron n draws from its OWN model kind[n] (0 Bernoulli, 1 Gaussian, 2 negative binomial, 3 binomial) with par[n] (unused, sqrt(eta_n),
+ * xi_n, n_n <= PGL_SIM_BINOMIAL_MAX_N).  The draws come from the device's own stream: Philox4x32-10, key = seed, purpose 2, stream =
+ * ((rep0 + r) << 32) | n, element = t, call index j = 0, 1, ...; u1, u2 = the uniforms of call 0:
+ *   Bernoulli  y = u1 < 1 / (1 + exp(-psi));      Gaussian  y = psi + par sqrt(-2 log u1) cos(2 pi u2);
+ *   binomial   chop-down inversion on u1 from k = 0, f = q^n, f <- f (n - k) / (k + 1) p / q, mirrored (1 - p, n - k) for p > 1/2;
+ *   negative binomial  inversion on u1, f0 = exp(-xi softplus(psi)), f <- f p (k + xi) / (k + 1), at most 65 535 steps
+ * (the order of the fp64 operations: pgl_generate.hip, "THE LAW").  Path r depends on (seed, rep0 + r, the parameters, its initial history)
+ * only -- not on R, on how the bins are cut into calls, or on the launch geometry.
+ * ring [R][L][N] (row t mod L of replicate r = Y_r[t]): the histories, read and updated; zero, or the last L bins before t0.  Y: [R] blocks of
+ * [Tc][N] at stride ldr doubles, or NULL: no trajectory is stored.  sum, sumsq [R][N]: running sums of y and y^2, updated in time order (the
+ * caller zeroes them before the first call).  work: pgl_simulate_work_bytes(N, B, R) bytes, 16-byte aligned.  status [4] (device int, zeroed
+ * by the caller): {1, bin} a grid barrier did not complete within 2 s; {2, bin, replicate, neuron} a negative-binomial walk reached its cap;
+ * either ends the launch early.  t0 + Tc and rep0 + R < 2^31. */
+#define PGL_SIM_BINOMIAL_MAX_N 64
+size_t pgl_simulate_work_bytes(int N, int B, int R);
+int pgl_simulate(const double* Wm, const double* bias, const double* basis, int N, int B, int L, const int* kind, const double* par, int R,
+                 long rep0, unsigned long long seed, double* ring, double* Y, long ldr, double* sum, double* sumsq, long t0, int Tc,
+                 void* work, int* status, void* hip_stream);
+
 /* ---- box calibration (diagnostic; nothing on the sampling path calls it) ------------------------------------------------------- */
 /* What the matrix cores of the current device sustain right now: a register-only MFMA loop on every CU for ~`seconds` (a quarter of it
  * untimed first, so that clocks and the package power limiter settle), timed with HIP events on `stream`; WAITS for the stream.

@@ -21,6 +21,7 @@
 // Residency: the grid is <= one workgroup per CU and launched cooperatively (the runtime checks it).  A model with N*N*B <=
 // PGL_GEN_ONE_WG_MAX runs as ONE workgroup: no grid barrier, the bins are separated by the workgroup barrier alone.
 #include "pgl_common.h"
+#include "pgl_rng.h"
 #include "../../include/pyglm_hip.h"
 #include <algorithm>
 
@@ -267,6 +268,342 @@ int launch(const GenArgs& a, int G, size_t lds, hipStream_t st) {
     return PGL_OK;
 }
 
+long long wall_clock_khz(int dev) {
+    static std::atomic<long long> tick_khz[PGL_MAX_DEVICES];
+    long long khz = tick_khz[dev & (PGL_MAX_DEVICES - 1)].load(std::memory_order_relaxed);
+    if (khz <= 0) {
+        int r = 0;
+        if (hipDeviceGetAttribute(&r, hipDeviceAttributeWallClockRate, dev) != hipSuccess || r <= 0) r = 100000;
+        khz = r;
+        tick_khz[dev & (PGL_MAX_DEVICES - 1)].store(khz, std::memory_order_relaxed);
+    }
+    return khz;
+}
+
+// =====================================================================================================================================
+// pgl_simulate: R replicate trajectories of the FITTED model per launch -- posterior predictive simulation.
+//
+// THE LAW (pyglm_amd/simulate.py holds the separately written NumPy version of exactly this; the two are checked against each other).
+//   activation   psi_t[r, n] = Wm[n, :] . x_t[r] + bias[n],   Wm = a*W (the activation of `means` and log_likelihood(), NOT generate()'s
+//                stored W),  x_t[r][m, :] = sum_l Y_r[t-1-l, m] basis[l, :]  as in generate_kernel
+//   model        kind[n] in {0 Bernoulli, 1 Gaussian, 2 negative binomial, 3 binomial}, par[n] = (unused, sqrt(eta_n), xi_n, n_n): every
+//                neuron draws from its OWN regression's model
+//   stream       Philox4x32-10, key = seed, purpose = PGL_PURPOSE_SIM, stream = (replicate << 32) | global neuron, element = global
+//                time bin t, call index j = 0, 1, ...; one lane owns one draw (pgl_unif).  u1, u2 = the two uniforms of call j = 0.
+//                Path r is a function of (seed, r, parameters, initial history): not of R, the chunking or the launch geometry.
+//   Bernoulli    y = u1 < 1 / (1 + exp(-psi))
+//   Gaussian     y = psi + par * (sqrt(-2 log u1) * cos(2 pi u2))
+//   binomial     n = par <= PGL_SIM_BINOMIAL_MAX_N (64; the host refuses a larger n).  pp = 1 / (1 + exp(|psi|)) = min(p, 1 - p), q = 1 - pp,
+//                s = pp / q;  f = q^n by n multiplications;  c = f, k = 0;  while u1 >= c and k < n:  f = f * (n - k) / (k + 1) * s, k += 1,
+//                c = c + f.   y = k, mirrored to n - k when psi > 0 (p > 1/2)
+//   neg. binom.  xi = par, p = 1 / (1 + exp(-psi)), softplus = max(psi, 0) + log1p(exp(-|psi|));  f = exp(-xi * softplus) = (1 - p)^xi;
+//                c = f, k = 0;  while u1 >= c and k < PGL_SIM_NEGBIN_CAP (65 535):  f = f * p * (k + xi) / (k + 1), k += 1, c = c + f.   y = k.
+//                A walk that reaches the cap sets the status word {2, bin, replicate, neuron}: an exploding count model ends as an error.
+//   Every fp64 operation of the walks is evaluated left to right as written, uncontracted, on both sides.
+//
+// Structure: as generate_kernel -- workgroup k owns its neurons for EVERY replicate (their ring rows [R][L][N], their draws, their running
+// sums of y and y^2, added by the owning lane in time order and carried in `sum` / `sumsq` from launch to launch: no atomics) -- with ONE
+// grid barrier per bin for all R replicates: the exchange buffer is [2][R][N*B].  Within a bin the replicates are independent: with the
+// rows of Wm in registers (N*B <= GEN_KR * 64) x_{r+1} is fetched into registers while the dot products of x_r run out of LDS (two LDS
+// buffers, one workgroup barrier per replicate).  The history sums of all R replicates are spread over the workgroup together; their
+// order of addition is that of own_history (set by the geometry, not by R).
+constexpr int SIM_NEGBIN_CAP = 65535;
+constexpr int SIM_PF = GEN_KR * 64 / GEN_THREADS;     // doubles of x per thread in the register-staged copy
+constexpr size_t SIM_RING_LDS_MAX = 64 * 1024;
+constexpr size_t SIM_LDS_BYTES = 160 * 1024;          // LDS of a gfx950 CU: the launch's whole request stays below it
+constexpr int SIM_PSI_MAX = 1024;                     // activations (replicate, neuron) of a workgroup held in LDS between the two phases of a bin
+
+struct SimArgs {
+    GenArgs g;               // Wm, bias, basis, ring ([R][L][N]), xbuf ([2][R][N*B]), bar, status ([4]), t0, Tc, N, B, L, npw, lpn, lpp, offsets, spin_ticks
+    const int* kind; const double* par;
+    double* Y; long ldr;     // [R][Tc][N], replicate stride ldr; or null
+    double* sum; double* sumsq;
+    int R; long rep0; unsigned long long seed;
+    int psi_off;             // byte offset of the activation table in LDS
+};
+
+__device__ __forceinline__ void sim_cap_fail(int* status, long bin, long rep, int n) {
+    int expect = 0;
+    if (__hip_atomic_compare_exchange_strong(status, &expect, 2, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+        __hip_atomic_store(status + 1, (int)bin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(status + 2, (int)rep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(status + 3, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// one draw of neuron's model at activation psi (THE LAW above); every loop is bounded
+__device__ double sim_draw(int kind, double par, double psi, PglPhilox& rng, bool& capped) {
+#pragma clang fp contract(off)
+    const double u1 = pgl_unif(rng);
+    if (kind == 0) return u1 < 1.0 / (1.0 + exp(-psi)) ? 1.0 : 0.0;
+    if (kind == 1) {
+        const double u2 = pgl_unif(rng);
+        const double gauss = sqrt(-2.0 * log(u1)) * cos(2.0 * PGL_PI * u2);
+        return __dadd_rn(psi, __dmul_rn(par, gauss));
+    }
+    if (kind == 3) {
+        int n = (int)par;
+        n = n < 0 ? 0 : n > PGL_SIM_BINOMIAL_MAX_N ? PGL_SIM_BINOMIAL_MAX_N : n;
+        const double pp = 1.0 / (1.0 + exp(fabs(psi)));
+        const double q = 1.0 - pp, s = pp / q;
+        double f = 1.0;
+        for (int i = 0; i < n; ++i) f = f * q;
+        double c = f;
+        int k = 0;
+        while (u1 >= c && k < n) {
+            f = f * (double)(n - k) / (double)(k + 1) * s;
+            ++k;
+            c = c + f;
+        }
+        return (double)(psi > 0.0 ? n - k : k);
+    }
+    const double xi = par;
+    const double p = 1.0 / (1.0 + exp(-psi));
+    const double softplus = (psi > 0.0 ? psi : 0.0) + log1p(exp(-fabs(psi)));
+    double f = exp(-xi * softplus), c = f;
+    int k = 0;
+    while (u1 >= c && k < SIM_NEGBIN_CAP) {
+        f = f * p * ((double)k + xi) / (double)(k + 1);
+        ++k;
+        c = c + f;
+    }
+    if (k >= SIM_NEGBIN_CAP) capped = true;
+    return (double)k;
+}
+
+// x_{tl+1}[r][m, :] of the workgroup's neurons m for all R replicates into out[r][m*B + b]: own_history's sums (the same lanes per sum, the
+// same order of addition), the (replicate, neuron, basis function) triples spread over the workgroup together.  ring0 / rs / rr: the
+// workgroup's first ring row, the stride between rows and between replicates -- in LDS or in global memory, like bas0 (the caller picks:
+// the two instances keep the loads of either address space apart)
+template <typename RingPtr, typename BasisPtr>
+__device__ __forceinline__ void sim_history_from(const SimArgs& s, long tl, int n_lo, int nown, RingPtr ring0, int rs, long rr, BasisPtr bas0,
+                                                 double* out) {
+    const GenArgs& g = s.g;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lpp = g.lpp, gpw = 64 / lpp, grp = lane / lpp, gl = lane % lpp;
+    const int P = nown * g.B, L = g.L, items = s.R * P;
+    const long NB = (long)g.N * g.B;
+    int r_top = (int)(tl % L);
+    if (r_top < 0) r_top += L;
+    for (int i0 = 0; i0 < items; i0 += GEN_WAVES * gpw) {               // wave-uniform trip count
+        const int it = i0 + wave * gpw + grp;
+        const bool on = it < items;
+        const int r = on ? it / P : 0, p = on ? it % P : 0, ml = p / g.B, b = p % g.B;
+        RingPtr ring = ring0 + r * rr + ml;
+        BasisPtr bas = bas0 + b;
+        double acc = 0.0;
+        if (on) {
+            int l = gl;
+            for (; l + 3 * lpp < L; l += 4 * lpp) {                   // four loads in flight; the additions in own_history's order
+                double y[4], w[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    int row = r_top - (l + q * lpp);
+                    if (row < 0) row += L;
+                    y[q] = ring[(long)row * rs];
+                    w[q] = bas[(l + q * lpp) * g.B];
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc = fma(y[q], w[q], acc);
+            }
+            for (; l < L; l += lpp) {
+                int row = r_top - l;
+                if (row < 0) row += L;
+                acc = fma(ring[(long)row * rs], bas[l * g.B], acc);
+            }
+        }
+        for (int off = lpp >> 1; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+        if (on && gl == 0) out[(long)r * NB + (n_lo + ml) * g.B + b] = acc;
+    }
+}
+
+typedef __attribute__((address_space(3))) const double* LdsPtr;
+
+__device__ void sim_history(const SimArgs& s, long tl, int n_lo, int nown, const double* rl, const double* sb, double* out) {
+    const GenArgs& g = s.g;
+    if (rl && sb)
+        sim_history_from(s, tl, n_lo, nown, (LdsPtr)rl, nown, (long)g.L * nown, (LdsPtr)sb, out);
+    else if (rl)
+        sim_history_from(s, tl, n_lo, nown, (LdsPtr)rl, nown, (long)g.L * nown, g.basis, out);
+    else
+        sim_history_from(s, tl, n_lo, nown, (const double*)(g.ring + n_lo), g.N, (long)g.L * g.N, sb ? sb : g.basis, out);
+}
+
+// KR > 0: the rows of Wm in registers and x_r double-buffered in LDS; KR = 0, XLDS: x_r staged in LDS one replicate at a time; else x_r
+// read from the exchange buffer.  A bin runs in two phases per group of replicates: the dot products, one replicate after the other, leave
+// psi[r][n] in an LDS table; then the draws of ALL (replicate, neuron) pairs of the group run side by side, one lane each.  The pair a
+// thread takes first is the same in every bin: its model and its running sums stay in registers for the whole launch.
+template <bool XLDS, int KR>
+__global__ __launch_bounds__(GEN_THREADS) void simulate_kernel(SimArgs s) {
+    // dynamic LDS: [16 B: barrier verdict][x: 2 * KR * 64 (KR > 0) or N*B (XLDS)][ring: R x L x npw (ring_off > 0)][basis (basis_off > 0)]
+    //              [psi: SIM_PSI_MAX]
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const GenArgs& g = s.g;
+    int* ok_lds = reinterpret_cast<int*>(smem);
+    double* xs = reinterpret_cast<double*>(smem + 16);
+    double* rl = g.ring_off ? reinterpret_cast<double*>(smem + g.ring_off) : nullptr;
+    double* sb = g.basis_off ? reinterpret_cast<double*>(smem + g.basis_off) : nullptr;
+    double* psi_l = reinterpret_cast<double*>(smem + s.psi_off);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n_lo = blockIdx.x * g.npw;
+    const int nown = min(g.N, n_lo + g.npw) - n_lo;
+    const int N = g.N, NB = g.N * g.B, L = g.L, R = s.R;
+    const int lpn = g.lpn, gpw = 64 / lpn, grp = lane / lpn, gl = lane % lpn;
+    const long ringN = (long)L * N, ringW = (long)L * nown;
+    const int RB = SIM_PSI_MAX / g.npw;                              // replicates per group (the host checks npw <= SIM_PSI_MAX)
+    unsigned epoch = 0;
+
+    if (rl)
+        for (long e = threadIdx.x; e < R * ringW; e += GEN_THREADS) {
+            const long r = e / ringW, q = e % ringW;
+            rl[e] = g.ring[r * ringN + (q / nown) * N + n_lo + q % nown];
+        }
+    if (sb)
+        for (int e = threadIdx.x; e < L * g.B; e += GEN_THREADS) sb[e] = g.basis[e];
+    double wr[KR > 0 ? KR : 1];
+    if (KR > 0) {                                                    // (the host picks KR only with one neuron per wave)
+        const int i = wave * gpw + grp;
+        const double* w = g.Wm + (long)(n_lo + (i < nown ? i : 0)) * NB;
+#pragma unroll
+        for (int q = 0; q < (KR > 0 ? KR : 1); ++q) wr[q] = (i < nown && gl + q * 64 < NB) ? w[gl + q * 64] : 0.0;
+    }
+    __syncthreads();
+
+    const bool one_round = nown <= GEN_WAVES * gpw;
+    const int i1 = wave * gpw + grp;
+    const bool mine1 = one_round && i1 < nown && gl == 0;
+    const double bias1 = mine1 ? g.bias[n_lo + i1] : 0.0;
+    // the thread's pair in the first group of replicates
+    const bool own1 = (int)threadIdx.x < min(RB, R) * nown;
+    const int r1 = own1 ? threadIdx.x / nown : 0, n1 = n_lo + (own1 ? threadIdx.x % nown : 0);
+    const int kind1 = own1 ? s.kind[n1] : 0;
+    const double par1 = own1 ? s.par[n1] : 0.0;
+    double sum1 = own1 ? s.sum[(long)r1 * N + n1] : 0.0, sq1 = own1 ? s.sumsq[(long)r1 * N + n1] : 0.0;
+    sim_history(s, g.t0 - 1, n_lo, nown, rl, sb, g.xbuf + (g.t0 & 1) * (long)R * NB);                // x_{t0} from the rings
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (!grid_sync(g, ++epoch, g.t0, ok_lds)) return;
+    for (int k = 0; k < g.Tc; ++k) {
+        const long t = g.t0 + k;
+        const double* xt = g.xbuf + (t & 1) * (long)R * NB;
+        const int row = (int)(t % L);
+        int capped = 0;
+        double pf[KR > 0 ? SIM_PF : 1];
+        if (KR > 0) {                                                // x_0 into the first buffer
+#pragma unroll
+            for (int q = 0; q < SIM_PF; ++q) { const int j = threadIdx.x + q * GEN_THREADS; pf[q] = j < NB ? xt[j] : 0.0; }
+#pragma unroll
+            for (int q = 0; q < SIM_PF; ++q) xs[threadIdx.x + q * GEN_THREADS] = pf[q];
+            __syncthreads();
+        }
+        for (int rb = 0; rb < R; rb += RB) {
+            const int rn = min(RB, R - rb);
+            for (int r = rb; r < rb + rn; ++r) {
+                const double* x = xt + (long)r * NB;
+                const double* xc = xs;                               // what the dot products read x_r from, when from LDS
+                if (KR > 0) {
+                    xc = xs + (r & 1) * (KR * 64);
+                    if (r + 1 < R) {                                 // x_{r+1} on its way while the dot products of x_r run
+#pragma unroll
+                        for (int q = 0; q < SIM_PF; ++q) { const int j = threadIdx.x + q * GEN_THREADS; pf[q] = j < NB ? x[NB + j] : 0.0; }
+                    }
+                } else if (XLDS) {
+                    for (int j = threadIdx.x; j < NB; j += GEN_THREADS) xs[j] = x[j];
+                    __syncthreads();
+                }
+                for (int r0 = 0; r0 < nown; r0 += GEN_WAVES * gpw) { // wave-uniform trip count: the shuffles below see every lane
+                    const int i = r0 + wave * gpw + grp;
+                    double acc = 0.0;
+                    if (i < nown) {
+                        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+                        if (KR > 0) {                                // lpn = 64; the buffer is zero beyond N*B up to KR*64
+#pragma unroll
+                            for (int q = 0; q < (KR > 0 ? KR : 1); q += 4) {
+                                a0 = fma(wr[q], xc[gl + q * 64], a0);
+                                if (q + 1 < KR) a1 = fma(wr[q + 1], xc[gl + (q + 1) * 64], a1);
+                                if (q + 2 < KR) a2 = fma(wr[q + 2], xc[gl + (q + 2) * 64], a2);
+                                if (q + 3 < KR) a3 = fma(wr[q + 3], xc[gl + (q + 3) * 64], a3);
+                            }
+                        } else {
+                            const double* w = g.Wm + (long)(n_lo + i) * NB;
+                            int j = gl;
+                            for (; j + 7 * lpn < NB; j += 8 * lpn) {
+                                double wv[8], xv[8];
+#pragma unroll
+                                for (int q = 0; q < 8; ++q) wv[q] = w[j + q * lpn];
+#pragma unroll
+                                for (int q = 0; q < 8; ++q) xv[q] = XLDS ? xs[j + q * lpn] : x[j + q * lpn];
+                                a0 = fma(wv[0], xv[0], a0); a1 = fma(wv[1], xv[1], a1); a2 = fma(wv[2], xv[2], a2); a3 = fma(wv[3], xv[3], a3);
+                                a0 = fma(wv[4], xv[4], a0); a1 = fma(wv[5], xv[5], a1); a2 = fma(wv[6], xv[6], a2); a3 = fma(wv[7], xv[7], a3);
+                            }
+                            for (; j < NB; j += lpn) a0 = fma(w[j], XLDS ? xs[j] : x[j], a0);
+                        }
+                        acc = (a0 + a1) + (a2 + a3);
+                    }
+                    for (int off = lpn >> 1; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+                    if (i < nown && gl == 0) psi_l[(r - rb) * nown + i] = acc + (one_round ? bias1 : g.bias[n_lo + i]);
+                }
+                if (KR > 0) {
+                    if (r + 1 < R) {
+                        double* xn = xs + ((r + 1) & 1) * (KR * 64);
+#pragma unroll
+                        for (int q = 0; q < SIM_PF; ++q) xn[threadIdx.x + q * GEN_THREADS] = pf[q];
+                    }
+                    __syncthreads();                                  // x_{r+1} is complete, and x_r is no longer read
+                } else if (XLDS) {
+                    __syncthreads();                                  // x_r is no longer read
+                }
+            }
+            __syncthreads();                                          // the group's activations are in the table
+            for (int it = threadIdx.x; it < rn * nown; it += GEN_THREADS) {
+                const bool first = rb == 0 && it == (int)threadIdx.x;  // the pair whose model and sums the thread keeps
+                const int r = rb + it / nown, i = it % nown, n = n_lo + i;
+                PglPhilox rng;
+                pgl_rng_init(rng, s.seed, ((uint64_t)(s.rep0 + r) << 32) | (uint32_t)n, (uint64_t)t, PGL_PURPOSE_SIM);
+                bool cap = false;
+                const double y = sim_draw(first ? kind1 : s.kind[n], first ? par1 : s.par[n], psi_l[it], rng, cap);
+                if (cap) { sim_cap_fail(g.status, t, s.rep0 + r, n); capped = 1; }
+                if (s.Y) s.Y[(long)r * s.ldr + (long)k * N + n] = y;
+                if (rl) rl[r * ringW + (long)row * nown + i] = y;
+                else g.ring[r * ringN + (long)row * N + n] = y;
+                if (first) {
+                    sum1 = __dadd_rn(sum1, y);
+                    sq1 = __dadd_rn(sq1, __dmul_rn(y, y));
+                } else {
+                    s.sum[(long)r * N + n] = __dadd_rn(s.sum[(long)r * N + n], y);
+                    s.sumsq[(long)r * N + n] = __dadd_rn(s.sumsq[(long)r * N + n], __dmul_rn(y, y));
+                }
+            }
+            if (rb + RB < R) __syncthreads();                         // the table is free for the next group
+        }
+        if (!rl) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (rings in global memory: this bin's rows before they are read)
+        if (__syncthreads_or(capped)) return;                         // a capped walk ends the launch: the status word names it
+        if (k + 1 == g.Tc) break;
+        sim_history(s, t, n_lo, nown, rl, sb, g.xbuf + ((t + 1) & 1) * (long)R * NB);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (!grid_sync(g, ++epoch, t + 1, ok_lds)) return;
+    }
+    if (own1) { s.sum[(long)r1 * N + n1] = sum1; s.sumsq[(long)r1 * N + n1] = sq1; }
+    if (rl) {                                                         // the rings go back for the next launch
+        __syncthreads();
+        for (long e = threadIdx.x; e < R * ringW; e += GEN_THREADS) {
+            const long r = e / ringW, q = e % ringW;
+            g.ring[r * ringN + (q / nown) * N + n_lo + q % nown] = rl[e];
+        }
+    }
+}
+
+template <bool XLDS, int KR>
+int launch_sim(const SimArgs& a, int G, size_t lds, hipStream_t st) {
+    static PglPerDeviceSize lds_set;
+    int rc = pgl_grow_dynamic_lds(reinterpret_cast<const void*>(&simulate_kernel<XLDS, KR>), lds, lds_set);
+    if (rc) return rc;
+    void* args[] = {const_cast<SimArgs*>(&a)};
+    hipError_t e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&simulate_kernel<XLDS, KR>), dim3(G), dim3(GEN_THREADS), args, lds, st);
+    if (e != hipSuccess) { pgl_set_error("pgl_simulate: cooperative launch of %d workgroups: %s", G, hipGetErrorString(e)); return PGL_ERR_HIP; }
+    PGL_CHECK_LAUNCH();
+    return PGL_OK;
+}
+
 }  // namespace
 
 extern "C" size_t pgl_generate_work_bytes(int N, int B) {
@@ -281,15 +618,7 @@ extern "C" int pgl_generate(const double* Wm, const double* bias, const double* 
     PGL_CHECK_ARG((long)N * B <= (1L << 30) && (long)L * N <= (1L << 31) - 1);
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     const GenGeometry q = geometry(N, B);
-    const int dev = pgl_device();
-    static std::atomic<long long> tick_khz[PGL_MAX_DEVICES];
-    long long khz = tick_khz[dev & (PGL_MAX_DEVICES - 1)].load(std::memory_order_relaxed);
-    if (khz <= 0) {
-        int r = 0;
-        if (hipDeviceGetAttribute(&r, hipDeviceAttributeWallClockRate, dev) != hipSuccess || r <= 0) r = 100000;
-        khz = r;
-        tick_khz[dev & (PGL_MAX_DEVICES - 1)].store(khz, std::memory_order_relaxed);
-    }
+    const long long khz = wall_clock_khz(pgl_device());
     const int NB = N * B;
     const bool xlds = NB <= GEN_XLDS_MAX;
     auto al16 = [](size_t x) { return (x + 15) / 16 * 16; };
@@ -312,4 +641,50 @@ extern "C" int pgl_generate(const double* Wm, const double* bias, const double* 
     if (regs) return launch<true, GEN_KR>(a, q.G, lds, st);
     if (xlds) return launch<true, 0>(a, q.G, lds, st);
     return launch<false, 0>(a, q.G, lds, st);
+}
+
+extern "C" size_t pgl_simulate_work_bytes(int N, int B, int R) {
+    if (N <= 0 || B <= 0 || R <= 0) return 0;
+    return GEN_BAR_BYTES + 2 * (size_t)R * N * B * sizeof(double);
+}
+
+extern "C" int pgl_simulate(const double* Wm, const double* bias, const double* basis, int N, int B, int L, const int* kind, const double* par,
+                            int R, long rep0, unsigned long long seed, double* ring, double* Y, long ldr, double* sum, double* sumsq, long t0,
+                            int Tc, void* work, int* status, void* hip_stream) {
+    PGL_CHECK_ARG(Wm && bias && basis && kind && par && ring && sum && sumsq && work && status);
+    PGL_CHECK_ARG(N > 0 && B > 0 && L > 0 && R > 0 && Tc > 0 && t0 >= 0 && rep0 >= 0);
+    PGL_CHECK_ARG(t0 + Tc <= (1L << 31) - 1 && rep0 + R <= (1L << 31) - 1);           // the status word and the Philox counter hold them in 32 bits
+    PGL_CHECK_ARG((long)N * B <= (1L << 30) && (long)L * N <= (1L << 31) - 1);
+    PGL_CHECK_ARG(!Y || ldr >= (long)Tc * N);
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    const GenGeometry q = geometry(N, B);
+    PGL_CHECK_ARG((long)R * q.npw * B <= (1L << 30) && (long)R * L * q.npw <= (1L << 30) && q.npw <= SIM_PSI_MAX);
+    const int NB = N * B;
+    const bool xlds = NB <= GEN_XLDS_MAX;
+    auto al16 = [](size_t x) { return (x + 15) / 16 * 16; };
+    const bool regs = xlds && q.npw <= GEN_WAVES && q.lpn == 64 && NB <= GEN_KR * 64;
+    size_t lds = 16 + (regs ? 2 * (size_t)GEN_KR * 64 * sizeof(double) : xlds ? al16((size_t)NB * sizeof(double)) : 0);
+    SimArgs s{};
+    GenArgs& a = s.g;
+    // the rings go into LDS when they, the basis and the activation table still fit the CU's 160 KiB beside x
+    const size_t ring_bytes = (size_t)R * L * q.npw * sizeof(double), basis_bytes = (size_t)L * B * sizeof(double);
+    const bool basis_lds = basis_bytes <= GEN_BASIS_LDS_MAX;
+    const size_t rest = (basis_lds ? al16(basis_bytes) : 0) + SIM_PSI_MAX * sizeof(double);
+    if (ring_bytes <= SIM_RING_LDS_MAX && lds + al16(ring_bytes) + rest <= SIM_LDS_BYTES) { a.ring_off = (int)lds; lds += al16(ring_bytes); }
+    if (basis_lds) { a.basis_off = (int)lds; lds += al16(basis_bytes); }
+    a.Wm = Wm; a.bias = bias; a.basis = basis; a.ring = ring;
+    a.bar = static_cast<unsigned*>(work);
+    a.xbuf = reinterpret_cast<double*>(static_cast<char*>(work) + GEN_BAR_BYTES);
+    a.status = status;
+    a.t0 = t0; a.Tc = Tc; a.N = N; a.B = B; a.L = L;
+    a.npw = q.npw; a.lpn = q.lpn; a.lpp = q.lpp;
+    a.spin_ticks = (unsigned long long)wall_clock_khz(pgl_device()) * 2000ULL;        // 2 s of the wall clock per barrier
+    s.psi_off = (int)lds;
+    lds += SIM_PSI_MAX * sizeof(double);
+    s.kind = kind; s.par = par; s.Y = Y; s.ldr = ldr; s.sum = sum; s.sumsq = sumsq; s.R = R; s.rep0 = rep0; s.seed = seed;
+    hipError_t e = hipMemsetAsync(work, 0, GEN_BAR_BYTES, st);
+    if (e != hipSuccess) { pgl_set_error("pgl_simulate: hipMemsetAsync: %s", hipGetErrorString(e)); return PGL_ERR_HIP; }
+    if (regs) return launch_sim<true, GEN_KR>(s, q.G, lds, st);
+    if (xlds) return launch_sim<true, 0>(s, q.G, lds, st);
+    return launch_sim<false, 0>(s, q.G, lds, st);
 }

@@ -492,6 +492,52 @@ class NonlinearAutoregressiveModel(object):
             self.add_data(Y[L:], X=X[L:])
         return X[L:], Y[L:]
 
+    def simulate(self, T, replicates=1, seed=0, first_replicate=0, history=None, keep_paths=True, gpu=None, t0=None):
+        """Posterior predictive simulation: `replicates` independent trajectories of T bins from the model's CURRENT state, every neuron
+        drawing from its own regression's observation model (Bernoulli, Gaussian, negative binomial, binomial; mixed lists work).  Unlike
+        generate() -- which stays the reference's loop, quirks included -- the activation is that of `means` and log_likelihood(),
+        psi = (a*W) . x + b, and the random numbers are the package's own Philox stream keyed by (seed, replicate, neuron, time bin): replicate
+        r = first_replicate + i depends on (seed, r, the state, its initial history) and on nothing else -- not on NumPy's global generator,
+        on `replicates`, or on where the run is cut into calls (pyglm_amd/simulate.py states the law).
+
+        Returns a simulate.Simulation: Y (R, T, N) float64, or None with keep_paths=False; sum and sumsq (R, N), the sums of y and y^2 over
+        the bins; history (R, L, N), the last L bins of every replicate; t0, t1.  It unpacks as (Y, sum, sumsq, history).
+        history: None -- from silence at bin t0 (default 0); a Simulation -- continue its trajectories from its t1 (T1 bins, then T2 bins from
+        the result, are the T1 + T2 bins of one call); an array (rows, N) -- e.g. the last L rows of a recording, shared by all replicates:
+        a forecast -- or (R, rows, N); an array starts at bin t0.
+        gpu=None: on the device (pgl_simulate) when there is one, else the NumPy path; True: the device or a PglError; False: NumPy.  Both
+        follow the same law; a model with an engine_factory takes the NumPy path.  With keep_paths=True the device path checks that the
+        paths fit into free device memory first and raises with the number of bytes needed.  A negative-binomial draw that reaches
+        simulate.NEGBIN_CAP raises PglError naming bin, replicate and neuron.
+        On a sharded model every rank holds the gathered state: each rank computes the same result on its own device, with no collective."""
+        from . import simulate as _sim
+        from ._lib import PglError
+        A, W, b = self._adopt_state()
+        kind, par = _sim.observation_kinds(self.regressions)
+        if self._engine_factory is not None:
+            if gpu:
+                raise ValueError("simulate(gpu=True): a model with an engine_factory takes the NumPy path (gpu=None or False)")
+            gpu = False
+        if gpu is None or gpu:
+            import torch
+            if not torch.cuda.is_available():
+                if gpu:
+                    raise PglError("simulate(gpu=True) needs a ROCm GPU (torch.cuda.is_available() is False)")
+                gpu = False
+            else:
+                gpu = True
+        Wm = (W * A[:, :, None]).reshape(self.N, self.N * self.B)
+        return _sim.simulate(Wm, b.ravel(), np.asarray(self.basis, dtype=np.float64), kind, par, T, replicates=replicates, seed=seed,
+                             first_replicate=first_replicate, history=history, keep_paths=keep_paths, t0=t0, on_device=bool(gpu),
+                             device=self._device)
+
+    def predictive_check(self, replicates=8, seed=0, data=0, gpu=None):
+        """a posterior predictive check of data set `data` bound to this model (simulate.PredictiveCheck): call its collect() after every
+        sweep to be kept -- it simulates `replicates` fresh trajectories of the data set's length from the current state --, read
+        rate_quantiles(q) / fano_quantiles(q) / pvalue("rate" | "fano") at the end.  Changes nothing in the chain."""
+        from .simulate import PredictiveCheck
+        return PredictiveCheck(self, replicates=replicates, seed=seed, data=data, gpu=gpu)
+
     # ---- Gibbs
     def resample_model(self):
         self.resample_regressions()

@@ -1,4 +1,8 @@
-"""Forward simulation of a population model on the GPU: the device path of `NetworkGLM.generate()` (reference pyglm/models.py:98-151).
+"""Forward simulation of a population model: the device path of `NetworkGLM.generate()` (reference pyglm/models.py:98-151), and -- second half
+of this file -- posterior predictive simulation, `model.simulate()` / `model.predictive_check()`: its law, the NumPy path and the driver of
+pgl_simulate.
+
+generate():
 
 The bins are simulated by pgl_generate (pyglm_amd/csrc/pgl_generate.hip), a chunk of bins per launch, serial in t inside the launch.
 The random numbers are NumPy's, drawn on the host in the reference's order: the reference draws `npr.rand(N)` (Bernoulli) or
@@ -22,9 +26,9 @@ CHUNK_MACS = 1 << 33            # multiply-adds per launch (N * N * B * bins): n
 X_BLOCK_BYTES = 1 << 30         # device scratch of the design matrix, formed in blocks of rows
 
 
-def chunk_bins(N, B):
-    """bins per launch for an N-neuron, B-basis model"""
-    return int(max(1, min(MAX_CHUNK_BINS, CHUNK_DRAWS // N, CHUNK_MACS // (N * N * B))))
+def chunk_bins(N, B, R=1):
+    """bins per launch for an N-neuron, B-basis model, R replicates sharing the launch"""
+    return int(max(1, min(MAX_CHUNK_BINS, CHUNK_DRAWS // (N * R), CHUNK_MACS // (N * N * B * R))))
 
 
 def generate(Wm, bias, basis, T, obs, noise_scale=0.0, device=None, verbose=False, intvl=10, chunk=None):
@@ -87,3 +91,372 @@ def generate(Wm, bias, basis, T, obs, noise_scale=0.0, device=None, verbose=Fals
             call("pgl_design_matrix", ptr(Y_d[r0 - h:]), N, ptr(basis_d), ptr(Xs), D + 1, None, 0, r1 - r0 + h, N, B, L, 0, st)
             X2[r0:r1].copy_(Xs[h:h + r1 - r0, :D])
     return X, Y
+
+
+# =====================================================================================================================================
+# Posterior predictive simulation: model.simulate() / model.predictive_check().
+#
+# THE LAW (the header comment of pgl_simulate in pyglm_amd/csrc/pgl_generate.hip states the same; the kernel and the NumPy path below are
+# two separately written implementations of it and are tested against each other):
+#   activation   psi_t[r, n] = (a*W)[n, :] . x_t[r] + b[n]  -- the activation of `means` and log_likelihood(), not generate()'s stored W --
+#                x_t[r][m, :] = sum_l Y_r[t-1-l, m] basis[l, :]
+#   model        per neuron, from its own regression: kind[n] in KINDS, par[n] = (unused, sqrt(eta_n), xi_n, n_n)
+#   stream       Philox4x32-10: key = seed, counter = (j | PURPOSE_SIM << 24, t, global neuron, replicate), j = 0, 1, ...; a call gives two
+#                uniforms ((x >> 11) + 0.5) / 2^53 from its low and high 64 bits; u1, u2 = those of call j = 0.  Path r depends on (seed, r,
+#                the parameters, its initial history) and on nothing else.
+#   Bernoulli    y = u1 < 1 / (1 + exp(-psi))
+#   Gaussian     y = psi + par * (sqrt(-2 log u1) * cos(2 pi u2))
+#   binomial     n = par <= BINOMIAL_MAX_N (a larger n is refused: f = q^n is formed by n multiplications).  pp = 1 / (1 + exp(|psi|)),
+#                q = 1 - pp, s = pp / q, f = q^n; c = f, k = 0; while u1 >= c and k < n: f = f * (n - k) / (k + 1) * s, k += 1, c = c + f.
+#                y = k, or n - k when psi > 0
+#   neg. binom.  xi = par, p = 1 / (1 + exp(-psi)), softplus = max(psi, 0) + log1p(exp(-|psi|)), f = exp(-xi * softplus); c = f, k = 0;
+#                while u1 >= c and k < NEGBIN_CAP: f = f * p * (k + xi) / (k + 1), k += 1, c = c + f.  y = k; k = NEGBIN_CAP is an error that
+#                names bin, replicate and neuron (an exploding count model)
+#   Every fp64 operation of the walks is evaluated left to right as written.
+PURPOSE_SIM = 2
+KIND_BERNOULLI, KIND_GAUSSIAN, KIND_NEGBIN, KIND_BINOMIAL = 0, 1, 2, 3
+KINDS = ("bernoulli", "gaussian", "negbin", "binomial")
+NEGBIN_CAP = 65535
+BINOMIAL_MAX_N = 64
+HOST_BLOCK_BINS = 4096          # bins the host path keeps in its rolling buffer when the paths are not kept
+
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32_10(c0, c1, c2, c3, seed):
+    """Philox4x32-10 on arrays of counter words (broadcast against each other), key = (seed lo, seed hi) -> four uint32 arrays"""
+    c = [np.asarray(v, dtype=np.uint64) & _M32 for v in np.broadcast_arrays(c0, c1, c2, c3)]
+    k0, k1 = np.uint64(int(seed) & 0xFFFFFFFF), np.uint64((int(seed) >> 32) & 0xFFFFFFFF)
+    m0, m1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = m0 * c[0], m1 * c[2]
+        c = [(p1 >> s32) ^ c[1] ^ k0, p1 & _M32, (p0 >> s32) ^ c[3] ^ k1, p0 & _M32]
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & _M32, (k1 + np.uint64(0xBB67AE85)) & _M32
+    return [v.astype(np.uint32) for v in c]
+
+
+def philox_words(seed, purpose, j, elem0, stream, n):
+    """(n, 4) uint32: the words of call j for elements elem0 .. elem0 + n - 1 of `stream` (what pgl_philox_words gives on the device)"""
+    elem = (int(elem0) + np.arange(n, dtype=np.uint64)) & _M32
+    w = philox4x32_10((int(j) & 0xFFFFFF) | (int(purpose) << 24), elem, int(stream) & 0xFFFFFFFF, (int(stream) >> 32) & 0xFFFFFFFF, seed)
+    return np.stack(w, axis=-1)
+
+
+def _unit(lo, hi):
+    x = lo.astype(np.uint64) | (hi.astype(np.uint64) << np.uint64(32))
+    return ((x >> np.uint64(11)).astype(np.float64) + 0.5) * (1.0 / 9007199254740992.0)
+
+
+def sim_uniforms(seed, t, neurons, replicates):
+    """(u1, u2), each (len(replicates), len(neurons)): the two uniforms of call 0 of every (replicate, neuron) stream at time bin t"""
+    o = philox4x32_10(PURPOSE_SIM << 24, int(t), np.asarray(neurons, dtype=np.uint64)[None, :], np.asarray(replicates, dtype=np.uint64)[:, None], seed)
+    return _unit(o[0], o[1]), _unit(o[2], o[3])
+
+
+def observation_kinds(regressions):
+    """-> (kind (N,) int32, par (N,) float64) of the regressions, each from its own model; ValueError for a regression whose rvs is not one
+    of the four built-in ones (an override in a class, an attribute of the instance, a subclass that changes the hooks but not rvs)"""
+    from . import regression as _reg
+    table = {_reg.SparseBernoulliRegression.rvs: ("bernoulli", KIND_BERNOULLI), _reg.SparseGaussianRegression.rvs: ("gaussian", KIND_GAUSSIAN),
+             _reg.SparseNegativeBinomialRegression.rvs: ("negbin", KIND_NEGBIN), _reg.SparseBinomialRegression.rvs: ("binomial", KIND_BINOMIAL)}
+    kind = np.zeros(len(regressions), dtype=np.int32)
+    par = np.zeros(len(regressions))
+    for i, r in enumerate(regressions):
+        entry = None if "rvs" in vars(r) else table.get(getattr(type(r), "rvs", None))
+        try:
+            model = _reg._kind(r)
+        except TypeError:
+            model = None
+        if entry is None or model != entry[0]:
+            raise ValueError("simulate(): regression %d (%s) does not draw from one of the built-in observation models (%s); a user-defined rvs "
+                             "or observation model cannot be simulated" % (i, type(r).__name__, ", ".join(KINDS)))
+        kind[i] = entry[1]
+        if entry[1] == KIND_GAUSSIAN:
+            par[i] = np.sqrt(float(r.eta))
+        elif entry[1] == KIND_NEGBIN:
+            par[i] = float(r.xi)
+        elif entry[1] == KIND_BINOMIAL:
+            if r.n > BINOMIAL_MAX_N:
+                raise ValueError("simulate(): regression %d is Binomial with n = %d; the sampler supports n <= %d" % (i, r.n, BINOMIAL_MAX_N))
+            par[i] = float(r.n)
+    return kind, par
+
+
+def host_draw(kind, par, psi, u1, u2):
+    """y (R, N) of THE LAW from psi, u1, u2 (R, N) and the per-neuron kind / par (N,); and the (replicate row, neuron) of the first
+    negative-binomial walk that reached NEGBIN_CAP, or None"""
+    y = np.empty_like(psi)
+    capped = None
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        m = np.flatnonzero(kind == KIND_BERNOULLI)
+        if m.size:
+            y[:, m] = u1[:, m] < 1.0 / (1.0 + np.exp(-psi[:, m]))
+        m = np.flatnonzero(kind == KIND_GAUSSIAN)
+        if m.size:
+            y[:, m] = psi[:, m] + par[m] * (np.sqrt(-2.0 * np.log(u1[:, m])) * np.cos(2.0 * np.pi * u2[:, m]))
+        m = np.flatnonzero(kind == KIND_BINOMIAL)
+        if m.size:
+            ps, u = psi[:, m], u1[:, m]
+            n = np.broadcast_to(par[m].astype(np.int64), ps.shape)
+            pp = 1.0 / (1.0 + np.exp(np.abs(ps)))
+            q = 1.0 - pp
+            s = pp / q
+            f = np.ones_like(ps)
+            for i in range(int(n.max()) if n.size else 0):
+                f = np.where(i < n, f * q, f)
+            c = f.copy()
+            k = np.zeros(ps.shape, dtype=np.int64)
+            while True:
+                act = (u >= c) & (k < n)
+                if not act.any():
+                    break
+                f = np.where(act, f * (n - k).astype(np.float64) / (k + 1).astype(np.float64) * s, f)
+                k = k + act
+                c = np.where(act, c + f, c)
+            y[:, m] = np.where(ps > 0.0, n - k, k)
+        m = np.flatnonzero(kind == KIND_NEGBIN)
+        if m.size:
+            ps, u = psi[:, m].ravel(), u1[:, m].ravel()
+            xi = np.broadcast_to(par[m], psi[:, m].shape).ravel()
+            p = 1.0 / (1.0 + np.exp(-ps))
+            softplus = np.where(ps > 0.0, ps, 0.0) + np.log1p(np.exp(-np.abs(ps)))
+            f = np.exp(-xi * softplus)
+            c = f.copy()
+            k = np.zeros(ps.shape, dtype=np.int64)
+            idx = np.flatnonzero(u >= c)                    # the walks still going (all at the same k: they all started at 0)
+            step = 0
+            while idx.size and step < NEGBIN_CAP:
+                fi = f[idx] * p[idx] * (step + xi[idx]) / float(step + 1)
+                step += 1
+                f[idx] = fi
+                k[idx] = step
+                ci = c[idx] + fi
+                c[idx] = ci
+                idx = idx[u[idx] >= ci]
+            hit = np.flatnonzero(k >= NEGBIN_CAP)
+            if hit.size:
+                capped = (int(hit[0] // m.size), int(m[hit[0] % m.size]))
+            y[:, m] = k.reshape(-1, m.size)
+    return y, capped
+
+
+class Simulation(object):
+    """what model.simulate() returns: Y (R, T, N) float64 or None (keep_paths=False); sum and sumsq (R, N), the sums of y and y^2 over the T
+    bins, added in time order; history (R, L, N), the last L bins of every replicate in time order; t0 / t1, the first bin simulated and the
+    first bin not simulated; seed and first_replicate.  Passed as `history=` of the next call it continues the same trajectories."""
+
+    def __init__(self, Y, sum, sumsq, history, t0, t1, seed, first_replicate):
+        self.Y, self.sum, self.sumsq, self.history = Y, sum, sumsq, history
+        self.t0, self.t1, self.seed, self.first_replicate = int(t0), int(t1), int(seed), int(first_replicate)
+
+    @property
+    def T(self):
+        return self.t1 - self.t0
+
+    def rate(self):
+        """mean of y per bin, (R, N)"""
+        return self.sum / self.T
+
+    def fano(self):
+        """variance / mean of y over the bins, (R, N); NaN where the mean is zero"""
+        return fano_factor(self.sum, self.sumsq, self.T)
+
+    def __iter__(self):                       # (Y, sum, sumsq, history) = model.simulate(...)
+        return iter((self.Y, self.sum, self.sumsq, self.history))
+
+
+def fano_factor(s, ss, T):
+    mean = np.asarray(s, dtype=np.float64) / T
+    var = np.asarray(ss, dtype=np.float64) / T - mean * mean
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(mean != 0.0, var / mean, np.nan)
+
+
+def _initial_history(history, R, L, N, t0):
+    """-> (hist (R, L, N) in time order, t0).  history: None (silence), a Simulation (continue it), (rows, N) -- the last rows of a data set,
+    the same for every replicate; fewer than L rows are preceded by silence, of more only the last L are used -- or (R, rows, N)"""
+    if isinstance(history, Simulation):
+        if t0 is None:
+            t0 = history.t1
+        history = history.history
+    t0 = 0 if t0 is None else int(t0)
+    hist = np.zeros((R, L, N))
+    if history is not None:
+        h = np.asarray(history, dtype=np.float64)
+        if h.ndim == 2:
+            h = np.broadcast_to(h[None], (R,) + h.shape)
+        if h.ndim != 3 or h.shape[0] != R or h.shape[2] != N:
+            raise ValueError("history must be (rows, N = %d) or (replicates = %d, rows, N), got %r" % (N, R, np.shape(history)))
+        h = h[:, -L:]
+        hist[:, L - h.shape[1]:] = h
+    if t0 < 0:
+        raise ValueError("t0 must be >= 0")
+    return hist, t0
+
+
+def _raise_cap(t, rep, n):
+    raise PglError("simulate(): the negative-binomial draw of neuron %d in replicate %d at bin %d reached the cap of %d: the count model "
+                   "explodes at this state (the rate grows without bound)" % (n, rep, t, NEGBIN_CAP))
+
+
+def simulate_host(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_paths):
+    """THE LAW in NumPy, vectorised over (R, N) per bin -> Simulation"""
+    Wm = np.ascontiguousarray(Wm, dtype=np.float64)
+    N = Wm.shape[0]
+    L, B = basis.shape
+    WmT = np.ascontiguousarray(Wm.T)
+    bias = np.asarray(bias, dtype=np.float64).reshape(N)
+    C = T if keep_paths else min(T, HOST_BLOCK_BINS)
+    buf = np.zeros((R, L + C, N))
+    buf[:, :L] = hist
+    s, ss = np.zeros((R, N)), np.zeros((R, N))
+    neurons, reps = np.arange(N), rep0 + np.arange(R)
+    pos = L                                          # buf[:, pos] receives bin t
+    for t in range(t0, t0 + T):
+        if pos == L + C:
+            buf[:, :L] = buf[:, C:].copy()
+            pos = L
+        x = np.einsum("rlm,lb->rmb", buf[:, pos - L:pos][:, ::-1], basis)
+        psi = x.reshape(R, N * B).dot(WmT) + bias
+        u1, u2 = sim_uniforms(seed, t, neurons, reps)
+        y, capped = host_draw(kind, par, psi, u1, u2)
+        if capped is not None:
+            _raise_cap(t, rep0 + capped[0], capped[1])
+        buf[:, pos] = y
+        s += y
+        ss += y * y
+        pos += 1
+    return Simulation(buf[:, L:L + T].copy() if keep_paths else None, s, ss, buf[:, pos - L:pos].copy(), t0, t0 + T, seed, rep0)
+
+
+def simulate_device(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_paths, device=None):
+    """THE LAW through pgl_simulate, a chunk of bins per launch -> Simulation"""
+    import torch
+    if not torch.cuda.is_available():
+        raise PglError("the device path of simulate() needs a ROCm GPU (torch.cuda.is_available() is False)")
+    lib = _lib.load()
+    Wm = np.ascontiguousarray(Wm, dtype=np.float64)
+    basis = np.ascontiguousarray(basis, dtype=np.float64)
+    N = Wm.shape[0]
+    L, B = basis.shape
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    Tc = chunk_bins(N, B, R)
+    with torch.cuda.device(dev):
+        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        f64 = dict(dtype=torch.float64, device=dev)
+        if keep_paths:
+            need = 8 * R * T * N
+            free = torch.cuda.mem_get_info(dev)[0]
+            if need > free:
+                raise PglError("simulate(keep_paths=True): the paths of %d replicates x %d bins x %d neurons need %d bytes of device memory, %d "
+                               "are free: simulate fewer replicates or bins per call, or pass keep_paths=False" % (R, T, N, need, free))
+        Wm_d = torch.from_numpy(Wm).to(dev)
+        bias_d = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float64).reshape(N)).to(dev)
+        basis_d = torch.from_numpy(basis).to(dev)
+        kind_d = torch.from_numpy(np.ascontiguousarray(kind, dtype=np.int32)).to(dev)
+        par_d = torch.from_numpy(np.ascontiguousarray(par, dtype=np.float64)).to(dev)
+        rows = (t0 - L + np.arange(L)) % L               # ring row t mod L = Y[t]
+        ring_h = np.empty((R, L, N))
+        ring_h[:, rows] = hist
+        ring = torch.from_numpy(ring_h).to(dev)
+        Y_d = torch.empty((R, T, N), **f64) if keep_paths else None
+        sum_d, sq_d = torch.zeros((R, N), **f64), torch.zeros((R, N), **f64)
+        work = torch.zeros(lib.pgl_simulate_work_bytes(N, B, R), dtype=torch.uint8, device=dev)
+        status = torch.zeros(4, dtype=torch.int32, device=dev)
+        status_h = torch.zeros(4, dtype=torch.int32).pin_memory()
+        for k0 in range(0, T, Tc):
+            n = min(Tc, T - k0)
+            call("pgl_simulate", ptr(Wm_d), ptr(bias_d), ptr(basis_d), N, B, L, ptr(kind_d), ptr(par_d), R, rep0, seed & (2 ** 64 - 1), ptr(ring),
+                 ptr(Y_d[0, k0:]) if keep_paths else None, T * N, ptr(sum_d), ptr(sq_d), t0 + k0, n, ptr(work), ptr(status), st)
+            status_h.copy_(status, non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()
+            code, sbin, srep, sneuron = (int(v) for v in status_h)
+            if code == 2:
+                _raise_cap(sbin, srep, sneuron)
+            if code:
+                raise PglError("pgl_simulate: a grid barrier timed out at bin %d (chunk of bins %d..%d)" % (sbin, t0 + k0, t0 + k0 + n - 1))
+        rows = (t0 + T - L + np.arange(L)) % L
+        return Simulation(Y_d.cpu().numpy() if keep_paths else None, sum_d.cpu().numpy(), sq_d.cpu().numpy(), ring.cpu().numpy()[:, rows],
+                          t0, t0 + T, seed, rep0)
+
+
+def simulate(Wm, bias, basis, kind, par, T, replicates=1, seed=0, first_replicate=0, history=None, keep_paths=True, t0=None, on_device=False,
+             device=None):
+    """R = `replicates` trajectories of T bins of the model (Wm = a*W as (N, N*B), bias, basis (L, B), per-neuron kind / par) -> Simulation;
+    on the device (pgl_simulate) or in NumPy.  What model.simulate() calls once it has read the model."""
+    N = np.shape(Wm)[0]
+    L = basis.shape[0]
+    T, R, rep0, seed = int(T), int(replicates), int(first_replicate), int(seed)
+    if T < 0 or R < 1 or rep0 < 0 or not 0 <= seed < 2 ** 64:
+        raise ValueError("simulate(): T >= 0, replicates >= 1, first_replicate >= 0 and 0 <= seed < 2^64 are required")
+    hist, t0 = _initial_history(history, R, L, N, t0)
+    if t0 + T >= 2 ** 31 or rep0 + R >= 2 ** 31:
+        raise ValueError("simulate(): time bins and replicate indices must stay below 2^31")
+    kind, par = np.asarray(kind, dtype=np.int32), np.asarray(par, dtype=np.float64)
+    if T == 0:
+        return Simulation(np.zeros((R, 0, N)) if keep_paths else None, np.zeros((R, N)), np.zeros((R, N)), hist, t0, t0, seed, rep0)
+    run = simulate_device if on_device else simulate_host
+    kw = dict(device=device) if on_device else {}
+    return run(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_paths, **kw)
+
+
+class PredictiveCheck(object):
+    """Posterior predictive check of the per-neuron firing rates and Fano factors of one data set (model.predictive_check()).
+
+        ppc = model.predictive_check(replicates=8, seed=0)
+        for it in range(n_sweeps):
+            model.resample_model()
+            if it >= burn:
+                ppc.collect()
+        ppc.pvalue("rate"), ppc.rate_quantiles([0.05, 0.5, 0.95])
+
+    collect() simulates `replicates` fresh trajectories of the data set's length from the model's current state (from silence, paths not
+    kept; the k-th call uses replicate indices k R ... k R + R - 1, so no two calls share a stream) and keeps their per-neuron rates and
+    Fano factors -- (S R, N) after S calls -- on the host."""
+
+    def __init__(self, model, replicates=8, seed=0, data=0, gpu=None):
+        self.model, self.R, self.seed, self.gpu = model, int(replicates), int(seed), gpu
+        Y = np.asarray(model.data_list[data][1], dtype=np.float64)
+        self.T = Y.shape[0]
+        self.observed = {"rate": Y.mean(axis=0), "fano": fano_factor(Y.sum(axis=0), (Y * Y).sum(axis=0), self.T)}
+        self.calls = 0
+        self._rate, self._fano = [], []
+
+    def collect(self):
+        sim = self.model.simulate(self.T, replicates=self.R, seed=self.seed, first_replicate=self.calls * self.R, keep_paths=False, gpu=self.gpu)
+        self.calls += 1
+        self._rate.append(sim.rate())
+        self._fano.append(sim.fano())
+
+    @property
+    def rates(self):
+        """(S R, N)"""
+        return np.concatenate(self._rate, axis=0)
+
+    @property
+    def fanos(self):
+        return np.concatenate(self._fano, axis=0)
+
+    def rate_quantiles(self, q):
+        return np.quantile(self.rates, q, axis=0)
+
+    def fano_quantiles(self, q):
+        """quantiles over the replicates whose Fano factor is defined (a silent replicate has none)"""
+        return np.nanquantile(self.fanos, q, axis=0)
+
+    def pvalue(self, stat="rate"):
+        """two-sided posterior predictive p-value of the observed statistic per neuron, (N,): with M replicated values (those that are
+        defined), p = min(1, 2 min(1 + #{rep >= obs}, 1 + #{rep <= obs}) / (M + 1)) -- the smallest attainable value is 2 / (M + 1).
+        NaN where the observed statistic is undefined."""
+        if stat not in ("rate", "fano"):
+            raise ValueError("pvalue(): stat is 'rate' or 'fano'")
+        rep = self.rates if stat == "rate" else self.fanos
+        obs = self.observed[stat]
+        ok = ~np.isnan(rep)
+        M = ok.sum(axis=0)
+        with np.errstate(invalid="ignore"):
+            ge = (ok & (rep >= obs)).sum(axis=0)
+            le = (ok & (rep <= obs)).sum(axis=0)
+        p = np.minimum(1.0, 2.0 * np.minimum(1 + ge, 1 + le) / (M + 1.0))
+        return np.where(np.isnan(obs), np.nan, p)
