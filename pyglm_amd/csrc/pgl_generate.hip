@@ -20,6 +20,15 @@
 // `spin_ticks` of the wall clock, or that sees another workgroup's failure, sets the status word {1, bin} and the kernel exits.
 // Residency: the grid is <= one workgroup per CU and launched cooperatively (the runtime checks it).  A model with N*N*B <=
 // PGL_GEN_ONE_WG_MAX runs as ONE workgroup: no grid barrier, the bins are separated by the workgroup barrier alone.
+//
+// Two kernels run this scheme, built from ONE set of pieces (history, row_dot, stage_x, wg_begin / wg_end, grid_sync; geometry, plan and
+// launch on the host), so the orders of addition that fix a trajectory's bits exist once: generate_kernel, one trajectory on the caller's
+// draws (pgl_generate), and simulate_kernel, R trajectories of the fitted model on the device's own stream (pgl_simulate, THE LAW below).
+// A kernel owns its bin loop and its draw.  For simulate_kernel a workgroup owns its neurons for EVERY replicate -- their ring rows
+// [R][L][N], their draws, their running sums of y and y^2, added by the owning lane in time order and carried in `sum` / `sumsq` from
+// launch to launch: no atomics -- and all R replicates meet at the ONE grid barrier per bin: the exchange buffer is [2][R][N*B].  Within a
+// bin the replicates are independent: with the rows of Wm in registers (N*B <= GEN_KR * 64) x_{r+1} is fetched into registers while the
+// dot products of x_r run out of LDS (two LDS buffers, one workgroup barrier per replicate).
 #include "pgl_common.h"
 #include "pgl_rng.h"
 #include "../../include/pyglm_hip.h"
@@ -100,184 +109,237 @@ __device__ bool grid_sync(const GenArgs& g, unsigned epoch, long bin, int* ok_ld
     return *ok_lds != 0;
 }
 
-// x_{tl+1}[m, :] for the workgroup's neurons m, from ring rows tl, tl-1, ..., tl-L+1 (rows of negative times are the ring's zeros) into
-// out[m*B + b] (the exchange buffer, or x_t in LDS when one workgroup runs the model).  Each (m, b) is a sum over L, split over lpp lanes
-// and added up by shuffles.  The ring (and the basis) are read from LDS when they fit there (rl / sb non-null), else from global memory.
-__device__ void own_history(const GenArgs& g, long tl, int n_lo, int nown, const double* rl, const double* sb, double* out) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+// ---- the pieces of a bin, written once: generate_kernel and simulate_kernel are built from these ----
+
+typedef __attribute__((address_space(3))) const double* LdsPtr;
+
+// x_{tl+1}[r][m, :] of the workgroup's neurons m for R replicates into out[r][m*B + b] (an exchange buffer, or x_t in LDS when ONE workgroup
+// runs generate), from ring rows tl, tl-1, ..., tl-L+1 (rows of negative times are the ring's zeros).  Each (m, b) is a sum over L, split
+// over lpp lanes -- lane gl adds l = gl, gl + lpp, ... in that order in ONE fma chain -- and added up by shuffles; the (replicate, neuron,
+// basis function) triples are spread over the workgroup together.  The order is set by the geometry alone, not by R: a path does not
+// depend on how many replicates share the launch.  ring0 / rs / rr: the workgroup's first ring row, the stride between rows and between
+// replicates -- in LDS or in global memory, like bas0 (the instances keep the loads of either address space apart)
+template <typename RingPtr, typename BasisPtr>
+__device__ __forceinline__ void history_from(const GenArgs& g, int R, long tl, int n_lo, int nown, RingPtr ring0, int rs, long rr, BasisPtr bas0,
+                                             double* out) {
+    int lane = threadIdx.x & 63;
+    // the lane's split and the starting values of the per-load indices below depend on the lane alone: formed here on every call, they
+    // would otherwise be hoisted out of the caller's bin loop and stay in registers across its dot products (9 VGPRs, and one wave per
+    // SIMD of register-limited occupancy, in generate_kernel<false, 0>)
+    asm volatile("" : "+v"(lane));
+    const int wave = threadIdx.x >> 6;
     const int lpp = g.lpp, gpw = 64 / lpp, grp = lane / lpp, gl = lane % lpp;
-    const int P = nown * g.B, L = g.L;
+    const int P = nown * g.B, L = g.L, items = R * P;
+    const long NB = (long)g.N * g.B;
     int r_top = (int)(tl % L);
     if (r_top < 0) r_top += L;
-    for (int r0 = 0; r0 < P; r0 += GEN_WAVES * gpw) {                 // wave-uniform trip count
-        const int p = r0 + wave * gpw + grp;
+    for (int i0 = 0; i0 < items; i0 += GEN_WAVES * gpw) {               // wave-uniform trip count
+        const int it = i0 + wave * gpw + grp;
+        const bool on = it < items;
+        const int r = on ? it / P : 0, p = on ? it % P : 0, ml = p / g.B, b = p % g.B;
+        const long ro = r * rr + ml;
         double acc = 0.0;
-        if (p < P) {
-            const int ml = p / g.B, b = p % g.B;
-            for (int l = gl; l < L; l += lpp) {
+        if (on) {
+            int l = gl;
+            for (; l + 3 * lpp < L; l += 4 * lpp) {                   // four loads in flight; the additions stay one chain in l
+                double y[4], w[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    int row = r_top - (l + q * lpp);
+                    if (row < 0) row += L;
+                    y[q] = ring0[ro + (long)row * rs];
+                    w[q] = bas0[(l + q * lpp) * g.B + b];
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc = fma(y[q], w[q], acc);
+            }
+            for (; l < L; l += lpp) {
                 int row = r_top - l;
                 if (row < 0) row += L;
-                const double y = rl ? rl[row * nown + ml] : g.ring[(long)row * g.N + n_lo + ml];
-                acc = fma(y, sb ? sb[l * g.B + b] : g.basis[l * g.B + b], acc);
+                acc = fma(ring0[ro + (long)row * rs], bas0[l * g.B + b], acc);
             }
         }
         for (int off = lpp >> 1; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-        if (p < P && gl == 0) out[(n_lo + p / g.B) * g.B + p % g.B] = acc;
+        if (on && gl == 0) out[(long)r * NB + (n_lo + ml) * g.B + b] = acc;
     }
 }
 
-// KR > 0: every lane keeps its <= KR elements of its neuron's row of Wm in registers for the whole launch (the workgroup's rows are read
-// from memory once per launch, not once per bin); KR = 0: the rows stream from memory every bin.  XLDS: x_t is read from LDS.
+// rl / sb: the rings [R][L][nown] / the basis in LDS, or null: read from global memory
+__device__ void history(const GenArgs& g, int R, long tl, int n_lo, int nown, const double* rl, const double* sb, double* out) {
+    if (rl && sb)
+        history_from(g, R, tl, n_lo, nown, (LdsPtr)rl, nown, (long)g.L * nown, (LdsPtr)sb, out);
+    else if (rl)
+        history_from(g, R, tl, n_lo, nown, (LdsPtr)rl, nown, (long)g.L * nown, g.basis, out);
+    else
+        history_from(g, R, tl, n_lo, nown, (const double*)(g.ring + n_lo), g.N, (long)g.L * g.N, sb ? sb : g.basis, out);
+}
+
+// Wm[n, :] . x for the neuron of the lane's group of lpn lanes (`on`: the group has one), the sum in every lane of the group.  KR > 0: the
+// row is wr[], lpn = 64 and x is readable (as zeros) beyond N*B up to KR*64; KR = 0: the row streams from w, eight loads in flight.  Four
+// partial sums by the element's index mod 4*lpn, folded (a0 + a1) + (a2 + a3), then the shuffle ladder: this order is psi's bits.
+template <int KR>
+__device__ __forceinline__ double row_dot(const double (&wr)[KR > 0 ? KR : 1], const double* w, const double* x, int NB, int gl, int lpn, bool on) {
+    double acc = 0.0;
+    if (on) {
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+        if (KR > 0) {
+#pragma unroll
+            for (int q = 0; q < (KR > 0 ? KR : 1); q += 4) {
+                a0 = fma(wr[q], x[gl + q * 64], a0);
+                if (q + 1 < KR) a1 = fma(wr[q + 1], x[gl + (q + 1) * 64], a1);
+                if (q + 2 < KR) a2 = fma(wr[q + 2], x[gl + (q + 2) * 64], a2);
+                if (q + 3 < KR) a3 = fma(wr[q + 3], x[gl + (q + 3) * 64], a3);
+            }
+        } else {
+            int j = gl;
+            for (; j + 7 * lpn < NB; j += 8 * lpn) {
+                double wv[8], xv[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) wv[q] = w[j + q * lpn];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) xv[q] = x[j + q * lpn];
+                a0 = fma(wv[0], xv[0], a0); a1 = fma(wv[1], xv[1], a1); a2 = fma(wv[2], xv[2], a2); a3 = fma(wv[3], xv[3], a3);
+                a0 = fma(wv[4], xv[4], a0); a1 = fma(wv[5], xv[5], a1); a2 = fma(wv[6], xv[6], a2); a3 = fma(wv[7], xv[7], a3);
+            }
+            for (; j < NB; j += lpn) a0 = fma(w[j], x[j], a0);
+        }
+        acc = (a0 + a1) + (a2 + a3);
+    }
+    for (int off = lpn >> 1; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    return acc;
+}
+
+// x (N*B doubles of an exchange buffer) into LDS by the whole workgroup, eight loads in flight; the caller places the barrier
+__device__ __forceinline__ void stage_x(double* xs, const double* x, int NB) {
+    int j = threadIdx.x;
+    for (; j + 7 * GEN_THREADS < NB; j += 8 * GEN_THREADS) {
+        double v[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] = x[j + q * GEN_THREADS];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) xs[j + q * GEN_THREADS] = v[q];
+    }
+    for (; j < NB; j += GEN_THREADS) xs[j] = x[j];
+}
+
+// what a thread keeps for the launch: the workgroup's dynamic LDS as the host laid it out, its neurons, the thread's place in the dot products
+struct Wg {
+    char* smem;              // [16 B: barrier verdict][x][rings: R x L x npw (ring_off > 0)][basis: L x B (basis_off > 0)][a kernel's own], 16-byte aligned
+    int* ok_lds; double* xs; double* rl; double* sb;
+    int n_lo, nown, NB;      // the workgroup owns neurons [n_lo, n_lo + nown)
+    int gpw, grp, gl;        // groups of lpn lanes per wave, the lane's group, the lane within it
+    // one round of neurons per wave (every lane keeps its neuron i1): its bias is loaded once
+    bool one_round, mine1; int i1; double bias1;
+};
+
+// the rings of R replicates between global memory ([R][L][N]) and the workgroup's LDS ([R][L][nown])
+template <bool IN>
+__device__ __forceinline__ void ring_copy(const GenArgs& g, int R, const Wg& w) {
+    const long ringN = (long)g.L * g.N, ringW = (long)g.L * w.nown;
+    for (long e = threadIdx.x; e < R * ringW; e += GEN_THREADS) {
+        const long r = e / ringW, q = e % ringW;
+        double* glob = g.ring + r * ringN + (q / w.nown) * g.N + w.n_lo + q % w.nown;
+        if (IN) w.rl[e] = *glob;
+        else *glob = w.rl[e];
+    }
+}
+
+// the prologue: the LDS pointers, the thread's place, rings and basis into LDS where the host gave them room.  The caller places the barrier.
+__device__ __forceinline__ Wg wg_begin(const GenArgs& g, int R) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    Wg w;
+    w.smem = smem;
+    w.ok_lds = reinterpret_cast<int*>(smem);
+    w.xs = reinterpret_cast<double*>(smem + 16);
+    w.rl = g.ring_off ? reinterpret_cast<double*>(smem + g.ring_off) : nullptr;
+    w.sb = g.basis_off ? reinterpret_cast<double*>(smem + g.basis_off) : nullptr;
+    w.n_lo = blockIdx.x * g.npw;
+    w.nown = min(g.N, w.n_lo + g.npw) - w.n_lo;
+    w.NB = g.N * g.B;
+    w.gpw = 64 / g.lpn; w.grp = lane / g.lpn; w.gl = lane % g.lpn;
+    w.one_round = w.nown <= GEN_WAVES * w.gpw;
+    w.i1 = wave * w.gpw + w.grp;
+    w.mine1 = w.one_round && w.i1 < w.nown && w.gl == 0;
+    w.bias1 = w.mine1 ? g.bias[w.n_lo + w.i1] : 0.0;
+    if (w.rl) ring_copy<true>(g, R, w);
+    if (w.sb)
+        for (int e = threadIdx.x; e < g.L * g.B; e += GEN_THREADS) w.sb[e] = g.basis[e];
+    return w;
+}
+
+// the lane's elements of its neuron's row of Wm into registers for the launch (KR > 0; the host picks KR only with one neuron per wave)
+template <int KR>
+__device__ __forceinline__ void load_row(const GenArgs& g, const Wg& w, double (&wr)[KR > 0 ? KR : 1]) {
+    if (KR > 0) {
+        const double* row = g.Wm + (long)(w.n_lo + (w.i1 < w.nown ? w.i1 : 0)) * w.NB;
+#pragma unroll
+        for (int q = 0; q < (KR > 0 ? KR : 1); ++q) {               // (every load is issued, from an element of the row that exists: no branches)
+            const int j = w.gl + q * 64;
+            const double v = row[j < w.NB ? j : 0];
+            wr[q] = (w.i1 < w.nown && j < w.NB) ? v : 0.0;
+        }
+    }
+}
+
+// the epilogue: rings in LDS go back for the next launch
+__device__ __forceinline__ void wg_end(const GenArgs& g, int R, const Wg& w) {
+    if (w.rl) {
+        __syncthreads();
+        ring_copy<false>(g, R, w);
+    }
+}
+
+// One trajectory on the caller's draws U.  KR > 0: every lane keeps its <= KR elements of its neuron's row of Wm in registers for the whole
+// launch (the workgroup's rows are read from memory once per launch, not once per bin); KR = 0: the rows stream from memory every bin.
+// XLDS: x_t is read from LDS.
 template <bool XLDS, int KR>
 __global__ __launch_bounds__(GEN_THREADS) void generate_kernel(GenArgs g) {
-    // dynamic LDS: [16 B: barrier verdict][x_t: N*B (XLDS)][ring: L x npw (ring_off > 0)][basis: L x B (basis_off > 0)], 16-byte aligned
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    int* ok_lds = reinterpret_cast<int*>(smem);
-    double* xs = reinterpret_cast<double*>(smem + 16);
-    double* rl = g.ring_off ? reinterpret_cast<double*>(smem + g.ring_off) : nullptr;
-    double* sb = g.basis_off ? reinterpret_cast<double*>(smem + g.basis_off) : nullptr;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n_lo = blockIdx.x * g.npw;
-    const int nown = min(g.N, n_lo + g.npw) - n_lo;
-    const int NB = g.N * g.B, L = g.L;
-    const int lpn = g.lpn, gpw = 64 / lpn, grp = lane / lpn, gl = lane % lpn;
+    const Wg w = wg_begin(g, 1);                                     // LDS x: N*B, or KR*64 of which those beyond N*B are zero
+    double wr[KR > 0 ? KR : 1];
+    load_row<KR>(g, w, wr);
+    const int wave = threadIdx.x >> 6, L = g.L;
     const bool direct = XLDS && gridDim.x == 1;                      // one workgroup: x goes straight into LDS, no exchange buffer
     unsigned epoch = 0;
-
-    if (rl)
-        for (int e = threadIdx.x; e < L * nown; e += GEN_THREADS) rl[e] = g.ring[(long)(e / nown) * g.N + n_lo + e % nown];
-    if (sb)
-        for (int e = threadIdx.x; e < L * g.B; e += GEN_THREADS) sb[e] = g.basis[e];
-    double wr[KR > 0 ? KR : 1];
-    if (KR > 0) {                                                    // (the host picks KR only with one neuron per wave)
-        const int i = wave * gpw + grp;
-        const double* w = g.Wm + (long)(n_lo + (i < nown ? i : 0)) * NB;
-#pragma unroll
-        for (int q = 0; q < (KR > 0 ? KR : 1); ++q) wr[q] = (i < nown && gl + q * 64 < NB) ? w[gl + q * 64] : 0.0;
-        for (int j = NB + threadIdx.x; j < KR * 64; j += GEN_THREADS) xs[j] = 0.0;
-    }
+    if (KR > 0)
+        for (int j = w.NB + threadIdx.x; j < KR * 64; j += GEN_THREADS) w.xs[j] = 0.0;
     __syncthreads();
 
-    // one round of neurons per wave (every lane keeps its neuron): its bias and the next bin's draw are loaded ahead of time
-    const bool one_round = nown <= GEN_WAVES * gpw;
-    const int i1 = wave * gpw + grp;
-    const bool mine1 = one_round && i1 < nown && gl == 0;
-    const double bias1 = mine1 ? g.bias[n_lo + i1] : 0.0;
-    double v_next = mine1 ? g.U[n_lo + i1] : 0.0;
-    own_history(g, g.t0 - 1, n_lo, nown, rl, sb, direct ? xs : g.xbuf + (g.t0 & 1) * (long)NB);      // x_{t0} from the ring
-    if (!grid_sync(g, ++epoch, g.t0, ok_lds)) return;
+    double v_next = w.mine1 ? g.U[w.n_lo + w.i1] : 0.0;              // with one round per wave the next bin's draw is loaded ahead of time
+    history(g, 1, g.t0 - 1, w.n_lo, w.nown, w.rl, w.sb, direct ? w.xs : g.xbuf + (g.t0 & 1) * (long)w.NB);      // x_{t0} from the ring
+    if (!grid_sync(g, ++epoch, g.t0, w.ok_lds)) return;
     for (int k = 0; k < g.Tc; ++k) {
         const long t = g.t0 + k;
-        const double* x = g.xbuf + (t & 1) * (long)NB;
+        const double* x = g.xbuf + (t & 1) * (long)w.NB;
         if (XLDS && !direct) {
-            int j = threadIdx.x;
-            for (; j + 7 * GEN_THREADS < NB; j += 8 * GEN_THREADS) {
-                double v[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) v[q] = x[j + q * GEN_THREADS];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) xs[j + q * GEN_THREADS] = v[q];
-            }
-            for (; j < NB; j += GEN_THREADS) xs[j] = x[j];
+            stage_x(w.xs, x, w.NB);
             __syncthreads();
         }
-        for (int r0 = 0; r0 < nown; r0 += GEN_WAVES * gpw) {         // wave-uniform trip count: the shuffles below see every lane
-            const int i = r0 + wave * gpw + grp;
-            const bool mine = i < nown && gl == 0;
-            const double v = one_round ? v_next : mine ? g.U[(long)k * g.N + n_lo + i] : 0.0;     // issued ahead of the dot product
-            if (mine1 && k + 1 < g.Tc) v_next = g.U[(long)(k + 1) * g.N + n_lo + i1];
-            double acc = 0.0;
-            if (i < nown) {
-                double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-                if (KR > 0) {                                        // lpn = 64; xs is zero beyond N*B up to KR*64
-#pragma unroll
-                    for (int q = 0; q < (KR > 0 ? KR : 1); q += 4) {
-                        a0 = fma(wr[q], xs[gl + q * 64], a0);
-                        if (q + 1 < KR) a1 = fma(wr[q + 1], xs[gl + (q + 1) * 64], a1);
-                        if (q + 2 < KR) a2 = fma(wr[q + 2], xs[gl + (q + 2) * 64], a2);
-                        if (q + 3 < KR) a3 = fma(wr[q + 3], xs[gl + (q + 3) * 64], a3);
-                    }
-                } else {
-                    const double* w = g.Wm + (long)(n_lo + i) * NB;
-                    int j = gl;
-                    for (; j + 7 * lpn < NB; j += 8 * lpn) {
-                        double wv[8], xv[8];
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) wv[q] = w[j + q * lpn];
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) xv[q] = XLDS ? xs[j + q * lpn] : x[j + q * lpn];
-                        a0 = fma(wv[0], xv[0], a0); a1 = fma(wv[1], xv[1], a1); a2 = fma(wv[2], xv[2], a2); a3 = fma(wv[3], xv[3], a3);
-                        a0 = fma(wv[4], xv[4], a0); a1 = fma(wv[5], xv[5], a1); a2 = fma(wv[6], xv[6], a2); a3 = fma(wv[7], xv[7], a3);
-                    }
-                    for (; j < NB; j += lpn) a0 = fma(w[j], XLDS ? xs[j] : x[j], a0);
-                }
-                acc = (a0 + a1) + (a2 + a3);
-            }
-            for (int off = lpn >> 1; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+        for (int r0 = 0; r0 < w.nown; r0 += GEN_WAVES * w.gpw) {     // wave-uniform trip count: the shuffles of row_dot see every lane
+            const int i = r0 + wave * w.gpw + w.grp;
+            const bool mine = i < w.nown && w.gl == 0;
+            const double v = w.one_round ? v_next : mine ? g.U[(long)k * g.N + w.n_lo + i] : 0.0;     // issued ahead of the dot product
+            if (w.mine1 && k + 1 < g.Tc) v_next = g.U[(long)(k + 1) * g.N + w.n_lo + w.i1];
+            const double acc = row_dot<KR>(wr, g.Wm + (long)(w.n_lo + (i < w.nown ? i : 0)) * w.NB, XLDS ? w.xs : x, w.NB, w.gl, g.lpn, i < w.nown);
             if (mine) {
-                const int n = n_lo + i;
-                const double psi = acc + (one_round ? bias1 : g.bias[n]);
+                const int n = w.n_lo + i;
+                const double psi = acc + (w.one_round ? w.bias1 : g.bias[n]);
                 double y;
                 if (g.obs == 0) y = v < 1.0 / (1.0 + exp(-psi)) ? 1.0 : 0.0;
                 else y = __dadd_rn(psi, __dmul_rn(g.scale, v));
                 g.Y[(long)k * g.N + n] = y;
                 const int row = (int)(t % L);
-                if (rl) rl[row * nown + i] = y;
+                if (w.rl) w.rl[row * w.nown + i] = y;
                 else g.ring[(long)row * g.N + n] = y;
             }
         }
         if (k + 1 == g.Tc) break;
-        if (!rl) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (a ring in global memory: this bin's row before it is read)
+        if (!w.rl) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // (a ring in global memory: this bin's row before it is read)
         __syncthreads();                                              // this bin's ring row is complete, and x_t is no longer read
-        own_history(g, t, n_lo, nown, rl, sb, direct ? xs : g.xbuf + ((t + 1) & 1) * (long)NB);
-        if (!grid_sync(g, ++epoch, t + 1, ok_lds)) return;
+        history(g, 1, t, w.n_lo, w.nown, w.rl, w.sb, direct ? w.xs : g.xbuf + ((t + 1) & 1) * (long)w.NB);
+        if (!grid_sync(g, ++epoch, t + 1, w.ok_lds)) return;
     }
-    if (rl) {                                                         // the ring goes back for the next launch
-        __syncthreads();
-        for (int e = threadIdx.x; e < L * nown; e += GEN_THREADS) g.ring[(long)(e / nown) * g.N + n_lo + e % nown] = rl[e];
-    }
-}
-
-struct GenGeometry { int G, npw, lpn, lpp; };
-
-GenGeometry geometry(int N, int B) {
-    GenGeometry q;
-    if ((long)N * N * B <= PGL_GEN_ONE_WG_MAX) q.G = 1;
-    else q.G = std::min(pgl_device_cus(pgl_device()), (N + 3) / 4);
-    q.npw = (N + q.G - 1) / q.G;
-    q.G = (N + q.npw - 1) / q.npw;                                     // no workgroup without neurons
-    int per_wave = (q.npw + GEN_WAVES - 1) / GEN_WAVES, gpw = 1;
-    while (gpw < per_wave && gpw < 64) gpw *= 2;
-    q.lpn = 64 / gpw;
-    // lanes per (neuron, basis function) sum of the history: as many as leave every pair of the workgroup a group in one round
-    const int pairs = q.npw * B;
-    q.lpp = 64;
-    while (q.lpp > 1 && pairs * q.lpp > GEN_THREADS) q.lpp /= 2;
-    return q;
-}
-
-template <bool XLDS, int KR>
-int launch(const GenArgs& a, int G, size_t lds, hipStream_t st) {
-    static PglPerDeviceSize lds_set;
-    int rc = pgl_grow_dynamic_lds(reinterpret_cast<const void*>(&generate_kernel<XLDS, KR>), lds, lds_set);
-    if (rc) return rc;
-    void* args[] = {const_cast<GenArgs*>(&a)};
-    hipError_t e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&generate_kernel<XLDS, KR>), dim3(G), dim3(GEN_THREADS), args, lds, st);
-    if (e != hipSuccess) { pgl_set_error("pgl_generate: cooperative launch of %d workgroups: %s", G, hipGetErrorString(e)); return PGL_ERR_HIP; }
-    PGL_CHECK_LAUNCH();
-    return PGL_OK;
-}
-
-long long wall_clock_khz(int dev) {
-    static std::atomic<long long> tick_khz[PGL_MAX_DEVICES];
-    long long khz = tick_khz[dev & (PGL_MAX_DEVICES - 1)].load(std::memory_order_relaxed);
-    if (khz <= 0) {
-        int r = 0;
-        if (hipDeviceGetAttribute(&r, hipDeviceAttributeWallClockRate, dev) != hipSuccess || r <= 0) r = 100000;
-        khz = r;
-        tick_khz[dev & (PGL_MAX_DEVICES - 1)].store(khz, std::memory_order_relaxed);
-    }
-    return khz;
+    wg_end(g, 1, w);
 }
 
 // =====================================================================================================================================
@@ -300,13 +362,6 @@ long long wall_clock_khz(int dev) {
 //                c = f, k = 0;  while u1 >= c and k < PGL_SIM_NEGBIN_CAP (65 535):  f = f * p * (k + xi) / (k + 1), k += 1, c = c + f.   y = k.
 //                A walk that reaches the cap sets the status word {2, bin, replicate, neuron}: an exploding count model ends as an error.
 //   Every fp64 operation of the walks is evaluated left to right as written, uncontracted, on both sides.
-//
-// Structure: as generate_kernel -- workgroup k owns its neurons for EVERY replicate (their ring rows [R][L][N], their draws, their running
-// sums of y and y^2, added by the owning lane in time order and carried in `sum` / `sumsq` from launch to launch: no atomics) -- with ONE
-// grid barrier per bin for all R replicates: the exchange buffer is [2][R][N*B].  Within a bin the replicates are independent: with the
-// rows of Wm in registers (N*B <= GEN_KR * 64) x_{r+1} is fetched into registers while the dot products of x_r run out of LDS (two LDS
-// buffers, one workgroup barrier per replicate).  The history sums of all R replicates are spread over the workgroup together; their
-// order of addition is that of own_history (set by the geometry, not by R).
 constexpr int SIM_NEGBIN_CAP = 65535;
 constexpr int SIM_PF = GEN_KR * 64 / GEN_THREADS;     // doubles of x per thread in the register-staged copy
 constexpr size_t SIM_RING_LDS_MAX = 64 * 1024;
@@ -371,117 +426,36 @@ __device__ double sim_draw(int kind, double par, double psi, PglPhilox& rng, boo
     return (double)k;
 }
 
-// x_{tl+1}[r][m, :] of the workgroup's neurons m for all R replicates into out[r][m*B + b]: own_history's sums (the same lanes per sum, the
-// same order of addition), the (replicate, neuron, basis function) triples spread over the workgroup together.  ring0 / rs / rr: the
-// workgroup's first ring row, the stride between rows and between replicates -- in LDS or in global memory, like bas0 (the caller picks:
-// the two instances keep the loads of either address space apart)
-template <typename RingPtr, typename BasisPtr>
-__device__ __forceinline__ void sim_history_from(const SimArgs& s, long tl, int n_lo, int nown, RingPtr ring0, int rs, long rr, BasisPtr bas0,
-                                                 double* out) {
-    const GenArgs& g = s.g;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lpp = g.lpp, gpw = 64 / lpp, grp = lane / lpp, gl = lane % lpp;
-    const int P = nown * g.B, L = g.L, items = s.R * P;
-    const long NB = (long)g.N * g.B;
-    int r_top = (int)(tl % L);
-    if (r_top < 0) r_top += L;
-    for (int i0 = 0; i0 < items; i0 += GEN_WAVES * gpw) {               // wave-uniform trip count
-        const int it = i0 + wave * gpw + grp;
-        const bool on = it < items;
-        const int r = on ? it / P : 0, p = on ? it % P : 0, ml = p / g.B, b = p % g.B;
-        RingPtr ring = ring0 + r * rr + ml;
-        BasisPtr bas = bas0 + b;
-        double acc = 0.0;
-        if (on) {
-            int l = gl;
-            for (; l + 3 * lpp < L; l += 4 * lpp) {                   // four loads in flight; the additions in own_history's order
-                double y[4], w[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    int row = r_top - (l + q * lpp);
-                    if (row < 0) row += L;
-                    y[q] = ring[(long)row * rs];
-                    w[q] = bas[(l + q * lpp) * g.B];
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc = fma(y[q], w[q], acc);
-            }
-            for (; l < L; l += lpp) {
-                int row = r_top - l;
-                if (row < 0) row += L;
-                acc = fma(ring[(long)row * rs], bas[l * g.B], acc);
-            }
-        }
-        for (int off = lpp >> 1; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-        if (on && gl == 0) out[(long)r * NB + (n_lo + ml) * g.B + b] = acc;
-    }
-}
-
-typedef __attribute__((address_space(3))) const double* LdsPtr;
-
-__device__ void sim_history(const SimArgs& s, long tl, int n_lo, int nown, const double* rl, const double* sb, double* out) {
-    const GenArgs& g = s.g;
-    if (rl && sb)
-        sim_history_from(s, tl, n_lo, nown, (LdsPtr)rl, nown, (long)g.L * nown, (LdsPtr)sb, out);
-    else if (rl)
-        sim_history_from(s, tl, n_lo, nown, (LdsPtr)rl, nown, (long)g.L * nown, g.basis, out);
-    else
-        sim_history_from(s, tl, n_lo, nown, (const double*)(g.ring + n_lo), g.N, (long)g.L * g.N, sb ? sb : g.basis, out);
-}
-
-// KR > 0: the rows of Wm in registers and x_r double-buffered in LDS; KR = 0, XLDS: x_r staged in LDS one replicate at a time; else x_r
-// read from the exchange buffer.  A bin runs in two phases per group of replicates: the dot products, one replicate after the other, leave
-// psi[r][n] in an LDS table; then the draws of ALL (replicate, neuron) pairs of the group run side by side, one lane each.  The pair a
-// thread takes first is the same in every bin: its model and its running sums stay in registers for the whole launch.
+// R trajectories on the device's Philox stream.  KR > 0: the rows of Wm in registers and x_r double-buffered in LDS; KR = 0, XLDS: x_r staged
+// in LDS one replicate at a time; else x_r read from the exchange buffer.  A bin runs in two phases per group of replicates: the dot
+// products, one replicate after the other, leave psi[r][n] in an LDS table; then the draws of ALL (replicate, neuron) pairs of the group run
+// side by side, one lane each.  The pair a thread takes first is the same in every bin: its model and its running sums stay in registers for
+// the whole launch.
 template <bool XLDS, int KR>
 __global__ __launch_bounds__(GEN_THREADS) void simulate_kernel(SimArgs s) {
-    // dynamic LDS: [16 B: barrier verdict][x: 2 * KR * 64 (KR > 0) or N*B (XLDS)][ring: R x L x npw (ring_off > 0)][basis (basis_off > 0)]
-    //              [psi: SIM_PSI_MAX]
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const GenArgs& g = s.g;
-    int* ok_lds = reinterpret_cast<int*>(smem);
-    double* xs = reinterpret_cast<double*>(smem + 16);
-    double* rl = g.ring_off ? reinterpret_cast<double*>(smem + g.ring_off) : nullptr;
-    double* sb = g.basis_off ? reinterpret_cast<double*>(smem + g.basis_off) : nullptr;
-    double* psi_l = reinterpret_cast<double*>(smem + s.psi_off);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n_lo = blockIdx.x * g.npw;
-    const int nown = min(g.N, n_lo + g.npw) - n_lo;
-    const int N = g.N, NB = g.N * g.B, L = g.L, R = s.R;
-    const int lpn = g.lpn, gpw = 64 / lpn, grp = lane / lpn, gl = lane % lpn;
+    const int R = s.R;
+    const Wg w = wg_begin(g, R);                                     // LDS x: 2 * KR * 64 (KR > 0) or N*B (XLDS); after the basis, psi: SIM_PSI_MAX
+    double wr[KR > 0 ? KR : 1];
+    load_row<KR>(g, w, wr);
+    double* xs = w.xs;
+    double* psi_l = reinterpret_cast<double*>(w.smem + s.psi_off);
+    const int wave = threadIdx.x >> 6;
+    const int n_lo = w.n_lo, nown = w.nown, N = g.N, NB = w.NB, L = g.L;
     const long ringN = (long)L * N, ringW = (long)L * nown;
     const int RB = SIM_PSI_MAX / g.npw;                              // replicates per group (the host checks npw <= SIM_PSI_MAX)
     unsigned epoch = 0;
-
-    if (rl)
-        for (long e = threadIdx.x; e < R * ringW; e += GEN_THREADS) {
-            const long r = e / ringW, q = e % ringW;
-            rl[e] = g.ring[r * ringN + (q / nown) * N + n_lo + q % nown];
-        }
-    if (sb)
-        for (int e = threadIdx.x; e < L * g.B; e += GEN_THREADS) sb[e] = g.basis[e];
-    double wr[KR > 0 ? KR : 1];
-    if (KR > 0) {                                                    // (the host picks KR only with one neuron per wave)
-        const int i = wave * gpw + grp;
-        const double* w = g.Wm + (long)(n_lo + (i < nown ? i : 0)) * NB;
-#pragma unroll
-        for (int q = 0; q < (KR > 0 ? KR : 1); ++q) wr[q] = (i < nown && gl + q * 64 < NB) ? w[gl + q * 64] : 0.0;
-    }
     __syncthreads();
 
-    const bool one_round = nown <= GEN_WAVES * gpw;
-    const int i1 = wave * gpw + grp;
-    const bool mine1 = one_round && i1 < nown && gl == 0;
-    const double bias1 = mine1 ? g.bias[n_lo + i1] : 0.0;
     // the thread's pair in the first group of replicates
     const bool own1 = (int)threadIdx.x < min(RB, R) * nown;
     const int r1 = own1 ? threadIdx.x / nown : 0, n1 = n_lo + (own1 ? threadIdx.x % nown : 0);
     const int kind1 = own1 ? s.kind[n1] : 0;
     const double par1 = own1 ? s.par[n1] : 0.0;
     double sum1 = own1 ? s.sum[(long)r1 * N + n1] : 0.0, sq1 = own1 ? s.sumsq[(long)r1 * N + n1] : 0.0;
-    sim_history(s, g.t0 - 1, n_lo, nown, rl, sb, g.xbuf + (g.t0 & 1) * (long)R * NB);                // x_{t0} from the rings
+    history(g, R, g.t0 - 1, n_lo, nown, w.rl, w.sb, g.xbuf + (g.t0 & 1) * (long)R * NB);             // x_{t0} from the rings
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (!grid_sync(g, ++epoch, g.t0, ok_lds)) return;
+    if (!grid_sync(g, ++epoch, g.t0, w.ok_lds)) return;
     for (int k = 0; k < g.Tc; ++k) {
         const long t = g.t0 + k;
         const double* xt = g.xbuf + (t & 1) * (long)R * NB;
@@ -507,40 +481,13 @@ __global__ __launch_bounds__(GEN_THREADS) void simulate_kernel(SimArgs s) {
                         for (int q = 0; q < SIM_PF; ++q) { const int j = threadIdx.x + q * GEN_THREADS; pf[q] = j < NB ? x[NB + j] : 0.0; }
                     }
                 } else if (XLDS) {
-                    for (int j = threadIdx.x; j < NB; j += GEN_THREADS) xs[j] = x[j];
+                    stage_x(xs, x, NB);
                     __syncthreads();
                 }
-                for (int r0 = 0; r0 < nown; r0 += GEN_WAVES * gpw) { // wave-uniform trip count: the shuffles below see every lane
-                    const int i = r0 + wave * gpw + grp;
-                    double acc = 0.0;
-                    if (i < nown) {
-                        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-                        if (KR > 0) {                                // lpn = 64; the buffer is zero beyond N*B up to KR*64
-#pragma unroll
-                            for (int q = 0; q < (KR > 0 ? KR : 1); q += 4) {
-                                a0 = fma(wr[q], xc[gl + q * 64], a0);
-                                if (q + 1 < KR) a1 = fma(wr[q + 1], xc[gl + (q + 1) * 64], a1);
-                                if (q + 2 < KR) a2 = fma(wr[q + 2], xc[gl + (q + 2) * 64], a2);
-                                if (q + 3 < KR) a3 = fma(wr[q + 3], xc[gl + (q + 3) * 64], a3);
-                            }
-                        } else {
-                            const double* w = g.Wm + (long)(n_lo + i) * NB;
-                            int j = gl;
-                            for (; j + 7 * lpn < NB; j += 8 * lpn) {
-                                double wv[8], xv[8];
-#pragma unroll
-                                for (int q = 0; q < 8; ++q) wv[q] = w[j + q * lpn];
-#pragma unroll
-                                for (int q = 0; q < 8; ++q) xv[q] = XLDS ? xs[j + q * lpn] : x[j + q * lpn];
-                                a0 = fma(wv[0], xv[0], a0); a1 = fma(wv[1], xv[1], a1); a2 = fma(wv[2], xv[2], a2); a3 = fma(wv[3], xv[3], a3);
-                                a0 = fma(wv[4], xv[4], a0); a1 = fma(wv[5], xv[5], a1); a2 = fma(wv[6], xv[6], a2); a3 = fma(wv[7], xv[7], a3);
-                            }
-                            for (; j < NB; j += lpn) a0 = fma(w[j], XLDS ? xs[j] : x[j], a0);
-                        }
-                        acc = (a0 + a1) + (a2 + a3);
-                    }
-                    for (int off = lpn >> 1; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-                    if (i < nown && gl == 0) psi_l[(r - rb) * nown + i] = acc + (one_round ? bias1 : g.bias[n_lo + i]);
+                for (int r0 = 0; r0 < nown; r0 += GEN_WAVES * w.gpw) { // wave-uniform trip count: the shuffles of row_dot see every lane
+                    const int i = r0 + wave * w.gpw + w.grp;
+                    const double acc = row_dot<KR>(wr, g.Wm + (long)(n_lo + (i < nown ? i : 0)) * NB, XLDS ? xc : x, NB, w.gl, g.lpn, i < nown);
+                    if (i < nown && w.gl == 0) psi_l[(r - rb) * nown + i] = acc + (w.one_round ? w.bias1 : g.bias[n_lo + i]);
                 }
                 if (KR > 0) {
                     if (r + 1 < R) {
@@ -563,7 +510,7 @@ __global__ __launch_bounds__(GEN_THREADS) void simulate_kernel(SimArgs s) {
                 const double y = sim_draw(first ? kind1 : s.kind[n], first ? par1 : s.par[n], psi_l[it], rng, cap);
                 if (cap) { sim_cap_fail(g.status, t, s.rep0 + r, n); capped = 1; }
                 if (s.Y) s.Y[(long)r * s.ldr + (long)k * N + n] = y;
-                if (rl) rl[r * ringW + (long)row * nown + i] = y;
+                if (w.rl) w.rl[r * ringW + (long)row * nown + i] = y;
                 else g.ring[r * ringN + (long)row * N + n] = y;
                 if (first) {
                     sum1 = __dadd_rn(sum1, y);
@@ -575,32 +522,101 @@ __global__ __launch_bounds__(GEN_THREADS) void simulate_kernel(SimArgs s) {
             }
             if (rb + RB < R) __syncthreads();                         // the table is free for the next group
         }
-        if (!rl) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (rings in global memory: this bin's rows before they are read)
+        if (!w.rl) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // (rings in global memory: this bin's rows before they are read)
         if (__syncthreads_or(capped)) return;                         // a capped walk ends the launch: the status word names it
         if (k + 1 == g.Tc) break;
-        sim_history(s, t, n_lo, nown, rl, sb, g.xbuf + ((t + 1) & 1) * (long)R * NB);
+        history(g, R, t, n_lo, nown, w.rl, w.sb, g.xbuf + ((t + 1) & 1) * (long)R * NB);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (!grid_sync(g, ++epoch, t + 1, ok_lds)) return;
+        if (!grid_sync(g, ++epoch, t + 1, w.ok_lds)) return;
     }
     if (own1) { s.sum[(long)r1 * N + n1] = sum1; s.sumsq[(long)r1 * N + n1] = sq1; }
-    if (rl) {                                                         // the rings go back for the next launch
-        __syncthreads();
-        for (long e = threadIdx.x; e < R * ringW; e += GEN_THREADS) {
-            const long r = e / ringW, q = e % ringW;
-            g.ring[r * ringN + (q / nown) * N + n_lo + q % nown] = rl[e];
-        }
-    }
+    wg_end(g, R, w);
 }
 
-template <bool XLDS, int KR>
-int launch_sim(const SimArgs& a, int G, size_t lds, hipStream_t st) {
+struct GenGeometry { int G, npw, lpn, lpp; };
+
+GenGeometry geometry(int N, int B) {
+    GenGeometry q;
+    if ((long)N * N * B <= PGL_GEN_ONE_WG_MAX) q.G = 1;
+    else q.G = std::min(pgl_device_cus(pgl_device()), (N + 3) / 4);
+    q.npw = (N + q.G - 1) / q.G;
+    q.G = (N + q.npw - 1) / q.npw;                                     // no workgroup without neurons
+    int per_wave = (q.npw + GEN_WAVES - 1) / GEN_WAVES, gpw = 1;
+    while (gpw < per_wave && gpw < 64) gpw *= 2;
+    q.lpn = 64 / gpw;
+    // lanes per (neuron, basis function) sum of the history: as many as leave every pair of the workgroup a group in one round
+    const int pairs = q.npw * B;
+    q.lpp = 64;
+    while (q.lpp > 1 && pairs * q.lpp > GEN_THREADS) q.lpp /= 2;
+    return q;
+}
+
+long long wall_clock_khz(int dev) {
+    static std::atomic<long long> tick_khz[PGL_MAX_DEVICES];
+    long long khz = tick_khz[dev & (PGL_MAX_DEVICES - 1)].load(std::memory_order_relaxed);
+    if (khz <= 0) {
+        int r = 0;
+        if (hipDeviceGetAttribute(&r, hipDeviceAttributeWallClockRate, dev) != hipSuccess || r <= 0) r = 100000;
+        khz = r;
+        tick_khz[dev & (PGL_MAX_DEVICES - 1)].store(khz, std::memory_order_relaxed);
+    }
+    return khz;
+}
+
+// zero the barrier block, give the kernel its dynamic LDS, launch it cooperatively
+template <auto Kernel, typename Args>
+int launch(const char* entry, const Args& a, void* work, int G, size_t lds, hipStream_t st) {
     static PglPerDeviceSize lds_set;
-    int rc = pgl_grow_dynamic_lds(reinterpret_cast<const void*>(&simulate_kernel<XLDS, KR>), lds, lds_set);
+    hipError_t e = hipMemsetAsync(work, 0, GEN_BAR_BYTES, st);
+    if (e != hipSuccess) { pgl_set_error("%s: hipMemsetAsync: %s", entry, hipGetErrorString(e)); return PGL_ERR_HIP; }
+    int rc = pgl_grow_dynamic_lds(reinterpret_cast<const void*>(Kernel), lds, lds_set);
     if (rc) return rc;
-    void* args[] = {const_cast<SimArgs*>(&a)};
-    hipError_t e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&simulate_kernel<XLDS, KR>), dim3(G), dim3(GEN_THREADS), args, lds, st);
-    if (e != hipSuccess) { pgl_set_error("pgl_simulate: cooperative launch of %d workgroups: %s", G, hipGetErrorString(e)); return PGL_ERR_HIP; }
+    void* args[] = {const_cast<Args*>(&a)};
+    e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(Kernel), dim3(G), dim3(GEN_THREADS), args, lds, st);
+    if (e != hipSuccess) { pgl_set_error("%s: cooperative launch of %d workgroups: %s", entry, G, hipGetErrorString(e)); return PGL_ERR_HIP; }
     PGL_CHECK_LAUNCH();
+    return PGL_OK;
+}
+
+// the launch's geometry, which kernel instance runs it and its dynamic LDS
+struct GenPlan { GenGeometry q; bool xlds, regs; size_t lds; };
+
+// what an entry point asks of the LDS layout: x double-buffered when the rows of Wm are in registers; the rings go into LDS when they are
+// at most ring_cap and the whole request -- with the basis and the `extra` bytes the kernel appends -- stays within lds_cap
+struct LdsPolicy { bool x_double; size_t ring_cap, lds_cap, extra; };
+// (pgl_generate: the ring's, the basis' and x's own caps keep the request at about 112 KiB, far below a CU's LDS: no test of the total)
+constexpr LdsPolicy GEN_LDS_POLICY = {false, GEN_RING_LDS_MAX, SIZE_MAX, 0};
+// (pgl_simulate: the rings go into LDS when they, the basis and the activation table still fit the CU's 160 KiB beside x)
+constexpr LdsPolicy SIM_LDS_POLICY = {true, SIM_RING_LDS_MAX, SIM_LDS_BYTES, SIM_PSI_MAX * sizeof(double)};
+
+// The plan of a launch of R trajectories, and the head of its argument block (what is not set here is the entry point's own).  x in LDS is
+// N*B doubles, or with the rows of Wm in registers GEN_KR * 64 (twice that when the kernel double-buffers x).
+int plan(int N, int B, int L, int R, const LdsPolicy& pol, const double* Wm, const double* bias, const double* basis, double* ring, long t0,
+         int Tc, void* work, int* status, GenArgs& a, GenPlan& p) {
+    PGL_CHECK_ARG((long)N * B <= (1L << 30) && (long)L * N <= (1L << 31) - 1);
+    const GenGeometry q = geometry(N, B);
+    const int NB = N * B;
+    auto al16 = [](size_t x) { return (x + 15) / 16 * 16; };
+    p.q = q;
+    p.xlds = NB <= GEN_XLDS_MAX;
+    // registers for the rows of Wm: one neuron per wave (npw <= 4, 64 lanes per neuron) and at most GEN_KR elements per lane
+    p.regs = p.xlds && q.npw <= GEN_WAVES && q.lpn == 64 && NB <= GEN_KR * 64;
+    size_t lds = 16 + (p.regs ? (pol.x_double ? 2 : 1) * (size_t)GEN_KR * 64 * sizeof(double) : p.xlds ? al16((size_t)NB * sizeof(double)) : 0);
+    const size_t ring_bytes = (size_t)R * L * q.npw * sizeof(double), basis_bytes = (size_t)L * B * sizeof(double);
+    const bool basis_lds = basis_bytes <= GEN_BASIS_LDS_MAX;
+    if (ring_bytes <= pol.ring_cap && lds + al16(ring_bytes) + (basis_lds ? al16(basis_bytes) : 0) + pol.extra <= pol.lds_cap) {
+        a.ring_off = (int)lds;
+        lds += al16(ring_bytes);
+    }
+    if (basis_lds) { a.basis_off = (int)lds; lds += al16(basis_bytes); }
+    p.lds = lds;
+    a.Wm = Wm; a.bias = bias; a.basis = basis; a.ring = ring;
+    a.bar = static_cast<unsigned*>(work);
+    a.xbuf = reinterpret_cast<double*>(static_cast<char*>(work) + GEN_BAR_BYTES);
+    a.status = status;
+    a.t0 = t0; a.Tc = Tc; a.N = N; a.B = B; a.L = L;
+    a.npw = q.npw; a.lpn = q.lpn; a.lpp = q.lpp;
+    a.spin_ticks = (unsigned long long)wall_clock_khz(pgl_device()) * 2000ULL;        // 2 s of the wall clock per barrier
     return PGL_OK;
 }
 
@@ -615,32 +631,15 @@ extern "C" int pgl_generate(const double* Wm, const double* bias, const double* 
                             const double* U, double* ring, double* Y, long t0, int Tc, void* work, int* status, void* hip_stream) {
     PGL_CHECK_ARG(Wm && bias && basis && U && ring && Y && work && status);
     PGL_CHECK_ARG(N > 0 && B > 0 && L > 0 && Tc > 0 && t0 >= 0 && (obs == 0 || obs == 1));
-    PGL_CHECK_ARG((long)N * B <= (1L << 30) && (long)L * N <= (1L << 31) - 1);
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    const GenGeometry q = geometry(N, B);
-    const long long khz = wall_clock_khz(pgl_device());
-    const int NB = N * B;
-    const bool xlds = NB <= GEN_XLDS_MAX;
-    auto al16 = [](size_t x) { return (x + 15) / 16 * 16; };
-    // registers for the rows of Wm: one neuron per wave (npw <= 4, 64 lanes per neuron) and at most GEN_KR elements per lane; x_t is then
-    // read as GEN_KR * 64 elements of which those beyond N*B are zero
-    const bool regs = xlds && q.npw <= GEN_WAVES && q.lpn == 64 && NB <= GEN_KR * 64;
-    size_t lds = 16 + (xlds ? al16((size_t)(regs ? GEN_KR * 64 : NB) * sizeof(double)) : 0);
     GenArgs a{};
-    if ((size_t)L * q.npw * sizeof(double) <= GEN_RING_LDS_MAX) { a.ring_off = (int)lds; lds += al16((size_t)L * q.npw * sizeof(double)); }
-    if ((size_t)L * B * sizeof(double) <= GEN_BASIS_LDS_MAX) { a.basis_off = (int)lds; lds += al16((size_t)L * B * sizeof(double)); }
-    a.Wm = Wm; a.bias = bias; a.basis = basis; a.U = U; a.ring = ring; a.Y = Y;
-    a.bar = static_cast<unsigned*>(work);
-    a.xbuf = reinterpret_cast<double*>(static_cast<char*>(work) + GEN_BAR_BYTES);
-    a.status = status;
-    a.t0 = t0; a.Tc = Tc; a.N = N; a.B = B; a.L = L; a.obs = obs; a.scale = noise_scale;
-    a.npw = q.npw; a.lpn = q.lpn; a.lpp = q.lpp;
-    a.spin_ticks = (unsigned long long)khz * 2000ULL;                 // 2 s of the wall clock per barrier
-    hipError_t e = hipMemsetAsync(work, 0, GEN_BAR_BYTES, st);
-    if (e != hipSuccess) { pgl_set_error("pgl_generate: hipMemsetAsync: %s", hipGetErrorString(e)); return PGL_ERR_HIP; }
-    if (regs) return launch<true, GEN_KR>(a, q.G, lds, st);
-    if (xlds) return launch<true, 0>(a, q.G, lds, st);
-    return launch<false, 0>(a, q.G, lds, st);
+    GenPlan p;
+    int rc = plan(N, B, L, 1, GEN_LDS_POLICY, Wm, bias, basis, ring, t0, Tc, work, status, a, p);
+    if (rc) return rc;
+    a.U = U; a.Y = Y; a.obs = obs; a.scale = noise_scale;
+    if (p.regs) return launch<generate_kernel<true, GEN_KR>>("pgl_generate", a, work, p.q.G, p.lds, st);
+    if (p.xlds) return launch<generate_kernel<true, 0>>("pgl_generate", a, work, p.q.G, p.lds, st);
+    return launch<generate_kernel<false, 0>>("pgl_generate", a, work, p.q.G, p.lds, st);
 }
 
 extern "C" size_t pgl_simulate_work_bytes(int N, int B, int R) {
@@ -654,37 +653,17 @@ extern "C" int pgl_simulate(const double* Wm, const double* bias, const double* 
     PGL_CHECK_ARG(Wm && bias && basis && kind && par && ring && sum && sumsq && work && status);
     PGL_CHECK_ARG(N > 0 && B > 0 && L > 0 && R > 0 && Tc > 0 && t0 >= 0 && rep0 >= 0);
     PGL_CHECK_ARG(t0 + Tc <= (1L << 31) - 1 && rep0 + R <= (1L << 31) - 1);           // the status word and the Philox counter hold them in 32 bits
-    PGL_CHECK_ARG((long)N * B <= (1L << 30) && (long)L * N <= (1L << 31) - 1);
     PGL_CHECK_ARG(!Y || ldr >= (long)Tc * N);
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    const GenGeometry q = geometry(N, B);
-    PGL_CHECK_ARG((long)R * q.npw * B <= (1L << 30) && (long)R * L * q.npw <= (1L << 30) && q.npw <= SIM_PSI_MAX);
-    const int NB = N * B;
-    const bool xlds = NB <= GEN_XLDS_MAX;
-    auto al16 = [](size_t x) { return (x + 15) / 16 * 16; };
-    const bool regs = xlds && q.npw <= GEN_WAVES && q.lpn == 64 && NB <= GEN_KR * 64;
-    size_t lds = 16 + (regs ? 2 * (size_t)GEN_KR * 64 * sizeof(double) : xlds ? al16((size_t)NB * sizeof(double)) : 0);
     SimArgs s{};
-    GenArgs& a = s.g;
-    // the rings go into LDS when they, the basis and the activation table still fit the CU's 160 KiB beside x
-    const size_t ring_bytes = (size_t)R * L * q.npw * sizeof(double), basis_bytes = (size_t)L * B * sizeof(double);
-    const bool basis_lds = basis_bytes <= GEN_BASIS_LDS_MAX;
-    const size_t rest = (basis_lds ? al16(basis_bytes) : 0) + SIM_PSI_MAX * sizeof(double);
-    if (ring_bytes <= SIM_RING_LDS_MAX && lds + al16(ring_bytes) + rest <= SIM_LDS_BYTES) { a.ring_off = (int)lds; lds += al16(ring_bytes); }
-    if (basis_lds) { a.basis_off = (int)lds; lds += al16(basis_bytes); }
-    a.Wm = Wm; a.bias = bias; a.basis = basis; a.ring = ring;
-    a.bar = static_cast<unsigned*>(work);
-    a.xbuf = reinterpret_cast<double*>(static_cast<char*>(work) + GEN_BAR_BYTES);
-    a.status = status;
-    a.t0 = t0; a.Tc = Tc; a.N = N; a.B = B; a.L = L;
-    a.npw = q.npw; a.lpn = q.lpn; a.lpp = q.lpp;
-    a.spin_ticks = (unsigned long long)wall_clock_khz(pgl_device()) * 2000ULL;        // 2 s of the wall clock per barrier
-    s.psi_off = (int)lds;
-    lds += SIM_PSI_MAX * sizeof(double);
+    GenPlan p;
+    int rc = plan(N, B, L, R, SIM_LDS_POLICY, Wm, bias, basis, ring, t0, Tc, work, status, s.g, p);
+    if (rc) return rc;
+    PGL_CHECK_ARG((long)R * p.q.npw * B <= (1L << 30) && (long)R * L * p.q.npw <= (1L << 30) && p.q.npw <= SIM_PSI_MAX);
+    s.psi_off = (int)p.lds;                                          // the activation table at the end
+    p.lds += SIM_PSI_MAX * sizeof(double);
     s.kind = kind; s.par = par; s.Y = Y; s.ldr = ldr; s.sum = sum; s.sumsq = sumsq; s.R = R; s.rep0 = rep0; s.seed = seed;
-    hipError_t e = hipMemsetAsync(work, 0, GEN_BAR_BYTES, st);
-    if (e != hipSuccess) { pgl_set_error("pgl_simulate: hipMemsetAsync: %s", hipGetErrorString(e)); return PGL_ERR_HIP; }
-    if (regs) return launch_sim<true, GEN_KR>(s, q.G, lds, st);
-    if (xlds) return launch_sim<true, 0>(s, q.G, lds, st);
-    return launch_sim<false, 0>(s, q.G, lds, st);
+    if (p.regs) return launch<simulate_kernel<true, GEN_KR>>("pgl_simulate", s, work, p.q.G, p.lds, st);
+    if (p.xlds) return launch<simulate_kernel<true, 0>>("pgl_simulate", s, work, p.q.G, p.lds, st);
+    return launch<simulate_kernel<false, 0>>("pgl_simulate", s, work, p.q.G, p.lds, st);
 }

@@ -31,28 +31,51 @@ def chunk_bins(N, B, R=1):
     return int(max(1, min(MAX_CHUNK_BINS, CHUNK_DRAWS // (N * R), CHUNK_MACS // (N * N * B * R))))
 
 
+def _device(what, device):
+    """what both device paths start with: the GPU check, the library, the device -> (dev, handle of its current stream)"""
+    import torch
+    if not torch.cuda.is_available():
+        raise PglError("the device path of %s() needs a ROCm GPU (torch.cuda.is_available() is False)" % what)
+    _lib.load()
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    return dev, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _upload(dev, Wm, bias, basis):
+    """the model on the device, float64 and contiguous -> (Wm_d (N, N*B), bias_d (N,), basis_d (L, B))"""
+    import torch
+    Wm_d, bias_d, basis_d = (torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(dev) for v in (Wm, bias, basis))
+    return Wm_d, bias_d.reshape(Wm_d.shape[0]), basis_d
+
+
+def _finish_launch(entry, dev, status, status_h, first_bin, last_bin, meanwhile=None):
+    """after the launch of bins first_bin..last_bin: run `meanwhile` (host work, -> its result) while it runs, wait, raise what its status reports"""
+    import torch
+    status_h.copy_(status, non_blocking=True)
+    result = meanwhile() if meanwhile else None
+    torch.cuda.current_stream(dev).synchronize()
+    code = int(status_h[0])
+    if code == 2:
+        _raise_cap(*(int(v) for v in status_h[1:4]))
+    if code:
+        raise PglError("%s: a grid barrier timed out at bin %d (chunk of bins %d..%d)" % (entry, int(status_h[1]), first_bin, last_bin))
+    return result
+
+
 def generate(Wm, bias, basis, T, obs, noise_scale=0.0, device=None, verbose=False, intvl=10, chunk=None):
     """(X (T, N, B), Y (T, N)) of the host loop at pyglm_amd/models.py (generate), from the current state of NumPy's global generator,
     which is left where that loop leaves it.  Wm (N, N*B), bias (N,), basis (L, B) as the model holds them (basis row 0 = previous bin);
     obs OBS_BERNOULLI or OBS_GAUSSIAN (noise_scale = sqrt(eta) of the regression whose rvs the loop calls)."""
     import torch
-    if not torch.cuda.is_available():
-        raise PglError("the device path of generate() needs a ROCm GPU (torch.cuda.is_available() is False)")
-    _lib.load()
-    Wm = np.ascontiguousarray(Wm, dtype=np.float64)
-    basis = np.ascontiguousarray(basis, dtype=np.float64)
-    N = Wm.shape[0]
-    L, B = basis.shape
-    assert Wm.shape == (N, N * B) and obs in (OBS_BERNOULLI, OBS_GAUSSIAN)
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev, st = _device("generate", device)
+    N = np.shape(Wm)[0]
+    L, B = np.shape(basis)
+    assert np.shape(Wm) == (N, N * B) and obs in (OBS_BERNOULLI, OBS_GAUSSIAN)
     Tc = int(chunk) if chunk else chunk_bins(N, B)
     draw = npr.rand if obs == OBS_BERNOULLI else npr.randn
     with torch.cuda.device(dev):
-        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         f64 = dict(dtype=torch.float64, device=dev)
-        Wm_d = torch.from_numpy(Wm).to(dev)
-        bias_d = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float64).reshape(N)).to(dev)
-        basis_d = torch.from_numpy(basis).to(dev)
+        Wm_d, bias_d, basis_d = _upload(dev, Wm, bias, basis)
         ring = torch.zeros((L, N), **f64)
         Y_d = torch.empty((T, N), **f64)
         work = torch.zeros(_lib.load().pgl_generate_work_bytes(N, B), dtype=torch.uint8, device=dev)
@@ -67,12 +90,8 @@ def generate(Wm, bias, basis, T, obs, noise_scale=0.0, device=None, verbose=Fals
             U_d[:n].copy_(U_h[:n], non_blocking=True)
             call("pgl_generate", ptr(Wm_d), ptr(bias_d), ptr(basis_d), N, B, L, obs, float(noise_scale), ptr(U_d), ptr(ring),
                  ptr(Y_d[t0:t0 + n]), t0, n, ptr(work), ptr(status), st)
-            status_h.copy_(status, non_blocking=True)
-            if t0 + n < T:
-                U = draw(min(Tc, T - t0 - n), N)            # the next chunk's draws, while this one runs
-            torch.cuda.current_stream(dev).synchronize()
-            if int(status_h[0]):
-                raise PglError("pgl_generate: a grid barrier timed out at bin %d (chunk of bins %d..%d)" % (int(status_h[1]), t0, t0 + n - 1))
+            more = min(Tc, T - t0 - n)                     # the next chunk's draws, while this one runs
+            U = _finish_launch("pgl_generate", dev, status, status_h, t0, t0 + n - 1, (lambda: draw(more, N)) if more > 0 else None)
             if verbose:
                 for t in range(L + t0, L + t0 + n):
                     if t % intvl == 0:
@@ -333,17 +352,11 @@ def simulate_host(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_p
 def simulate_device(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_paths, device=None):
     """THE LAW through pgl_simulate, a chunk of bins per launch -> Simulation"""
     import torch
-    if not torch.cuda.is_available():
-        raise PglError("the device path of simulate() needs a ROCm GPU (torch.cuda.is_available() is False)")
-    lib = _lib.load()
-    Wm = np.ascontiguousarray(Wm, dtype=np.float64)
-    basis = np.ascontiguousarray(basis, dtype=np.float64)
-    N = Wm.shape[0]
-    L, B = basis.shape
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev, st = _device("simulate", device)
+    N = np.shape(Wm)[0]
+    L, B = np.shape(basis)
     Tc = chunk_bins(N, B, R)
     with torch.cuda.device(dev):
-        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         f64 = dict(dtype=torch.float64, device=dev)
         if keep_paths:
             need = 8 * R * T * N
@@ -351,9 +364,7 @@ def simulate_device(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep
             if need > free:
                 raise PglError("simulate(keep_paths=True): the paths of %d replicates x %d bins x %d neurons need %d bytes of device memory, %d "
                                "are free: simulate fewer replicates or bins per call, or pass keep_paths=False" % (R, T, N, need, free))
-        Wm_d = torch.from_numpy(Wm).to(dev)
-        bias_d = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float64).reshape(N)).to(dev)
-        basis_d = torch.from_numpy(basis).to(dev)
+        Wm_d, bias_d, basis_d = _upload(dev, Wm, bias, basis)
         kind_d = torch.from_numpy(np.ascontiguousarray(kind, dtype=np.int32)).to(dev)
         par_d = torch.from_numpy(np.ascontiguousarray(par, dtype=np.float64)).to(dev)
         rows = (t0 - L + np.arange(L)) % L               # ring row t mod L = Y[t]
@@ -362,20 +373,14 @@ def simulate_device(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep
         ring = torch.from_numpy(ring_h).to(dev)
         Y_d = torch.empty((R, T, N), **f64) if keep_paths else None
         sum_d, sq_d = torch.zeros((R, N), **f64), torch.zeros((R, N), **f64)
-        work = torch.zeros(lib.pgl_simulate_work_bytes(N, B, R), dtype=torch.uint8, device=dev)
+        work = torch.zeros(_lib.load().pgl_simulate_work_bytes(N, B, R), dtype=torch.uint8, device=dev)
         status = torch.zeros(4, dtype=torch.int32, device=dev)
         status_h = torch.zeros(4, dtype=torch.int32).pin_memory()
         for k0 in range(0, T, Tc):
             n = min(Tc, T - k0)
             call("pgl_simulate", ptr(Wm_d), ptr(bias_d), ptr(basis_d), N, B, L, ptr(kind_d), ptr(par_d), R, rep0, seed & (2 ** 64 - 1), ptr(ring),
                  ptr(Y_d[0, k0:]) if keep_paths else None, T * N, ptr(sum_d), ptr(sq_d), t0 + k0, n, ptr(work), ptr(status), st)
-            status_h.copy_(status, non_blocking=True)
-            torch.cuda.current_stream(dev).synchronize()
-            code, sbin, srep, sneuron = (int(v) for v in status_h)
-            if code == 2:
-                _raise_cap(sbin, srep, sneuron)
-            if code:
-                raise PglError("pgl_simulate: a grid barrier timed out at bin %d (chunk of bins %d..%d)" % (sbin, t0 + k0, t0 + k0 + n - 1))
+            _finish_launch("pgl_simulate", dev, status, status_h, t0 + k0, t0 + k0 + n - 1)
         rows = (t0 + T - L + np.arange(L)) % L
         return Simulation(Y_d.cpu().numpy() if keep_paths else None, sum_d.cpu().numpy(), sq_d.cpu().numpy(), ring.cpu().numpy()[:, rows],
                           t0, t0 + T, seed, rep0)
