@@ -34,7 +34,7 @@ test_model.add_data(Y)
 
 N_samples = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 half = N_samples // 2
-ppc = test_model.predictive_check(replicates=8, seed=2)
+ppc = test_model.predictive_check(replicates=8, seed=2, lags=10)       # lags: the cross-correlogram, the statistic that sees the coupling
 for itr in range(N_samples):
     test_model.resample_model()
     if itr >= half:
@@ -50,5 +50,7 @@ print("p-value (rate)           ", ppc.pvalue("rate").round(3))
 print("observed Fano factor     ", ppc.observed["fano"].round(3))
 print("replicated Fano 50 %     ", ppc.fano_quantiles(0.5).round(3))
 print("p-value (Fano)           ", ppc.pvalue("fano").round(3))
+p_xc = ppc.pvalue("xcorr")                        # (lags, N, N): neuron i leading neuron j by l bins
+print("cross-correlogram: fraction of (lag, pair) cells with p < 0.05  %.3f" % np.mean(p_xc[~np.isnan(p_xc)] < 0.05))
 forecast = test_model.simulate(500, replicates=16, seed=3, history=Y[-L:], t0=T)
 print("forecast of the next 500 bins, mean rate over 16 replicates", forecast.rate().mean(axis=0).round(4))

@@ -404,6 +404,24 @@ int pgl_simulate(const double* Wm, const double* bias, const double* basis, int 
                  long rep0, unsigned long long seed, double* ring, double* Y, long ldr, double* sum, double* sumsq, long t0, int Tc,
                  void* work, int* status, void* hip_stream);
 
+/* ---- lagged cross products (pgl_xcorr.hip): the pairwise statistic of the posterior predictive check ---------------------------------- */
+/* This project's own statistic, as the count models are (the reference has no predictive check): the sums behind the lagged
+ * cross-correlogram of pyglm_amd/simulate.py,
+ *   S[r][l][i][j] (+)= sum over u < rows with u - l >= -prev of  Y_r[u - l][i] * Y_r[u][j],      l < K, "neuron i leads neuron j by l bins".
+ * Y_r = Y + r strideY points at the first of `rows` NEW rows (row length ldy >= N); the `prev` <= K - 1 rows before it are readable and hold
+ * the bins before the chunk, so calls on consecutive chunks of one buffer (accumulate = 1, prev = min(K - 1, rows so far)) add up to the
+ * sums of the whole series.  S: [R] blocks of [K][N][N] doubles, strideS apart.  1 <= K <= PGL_LAG_MAX.
+ *   PGL_LAG_I8   for integer Y in [-127, 127]: exact, on v_mfma_i32_16x16x64_i8.  Any other value sets status = {3, row (relative to the first
+ *                new row), replicate, neuron} (device int[4], zeroed by the caller) and S IS LEFT UNTOUCHED: the caller may repeat the call in the other mode.
+ *   PGL_LAG_F64  for any finite Y: one fp64-MFMA contraction (as pgl_contract_tn) per lag.  Leaves status alone.
+ * work: pgl_lagged_work_bytes(N, K, R, rows) bytes, 16-byte aligned, enough for either mode. */
+#define PGL_LAG_MAX 256
+#define PGL_LAG_I8 0
+#define PGL_LAG_F64 1
+size_t pgl_lagged_work_bytes(int N, int K, int R, int rows);
+int pgl_lagged_products(const double* Y, long ldy, long strideY, int rows, int prev, int N, int K, int R, double* S, long strideS, int accumulate,
+                        int mode, void* work, int* status, void* hip_stream);
+
 /* ---- box calibration (diagnostic; nothing on the sampling path calls it) ------------------------------------------------------- */
 /* What the matrix cores of the current device sustain right now: a register-only MFMA loop on every CU for ~`seconds` (a quarter of it
  * untimed first, so that clocks and the package power limiter settle), timed with HIP events on `stream`; WAITS for the stream.

@@ -492,7 +492,7 @@ class NonlinearAutoregressiveModel(object):
             self.add_data(Y[L:], X=X[L:])
         return X[L:], Y[L:]
 
-    def simulate(self, T, replicates=1, seed=0, first_replicate=0, history=None, keep_paths=True, gpu=None, t0=None):
+    def simulate(self, T, replicates=1, seed=0, first_replicate=0, history=None, keep_paths=True, gpu=None, t0=None, lags=0, lagged_on_device=False):
         """Posterior predictive simulation: `replicates` independent trajectories of T bins from the model's CURRENT state, every neuron
         drawing from its own regression's observation model (Bernoulli, Gaussian, negative binomial, binomial; mixed lists work).  Unlike
         generate() -- which stays the reference's loop, quirks included -- the activation is that of `means` and log_likelihood(),
@@ -509,6 +509,11 @@ class NonlinearAutoregressiveModel(object):
         follow the same law; a model with an engine_factory takes the NumPy path.  With keep_paths=True the device path checks that the
         paths fit into free device memory first and raises with the number of bytes needed.  A negative-binomial draw that reaches
         simulate.NEGBIN_CAP raises PglError naming bin, replicate and neuron.
+        lags = K > 0 (K <= simulate.PGL_LAG_MAX, K - 1 < T): the Simulation also carries `lagged` (R, K, N, N), lagged[r, l, i, j] =
+        sum_t Y_r[t, i] Y_r[t+l, j] over the T bins of this call (never pairing a bin with the initial history), and correlogram().  On the
+        device the sums are folded after every launch by pgl_lagged_products -- on the int8 matrix cores, exactly, when the neurons are
+        Bernoulli or binomial; negative-binomial neurons fall back to fp64 for the chunks in which a count passes 127; fp64 if a neuron is
+        Gaussian -- with keep_paths=False too; the memory they need is checked first.  lagged_on_device leaves `lagged` a torch tensor.
         On a sharded model every rank holds the gathered state: each rank computes the same result on its own device, with no collective."""
         from . import simulate as _sim
         from ._lib import PglError
@@ -529,14 +534,35 @@ class NonlinearAutoregressiveModel(object):
         Wm = (W * A[:, :, None]).reshape(self.N, self.N * self.B)
         return _sim.simulate(Wm, b.ravel(), np.asarray(self.basis, dtype=np.float64), kind, par, T, replicates=replicates, seed=seed,
                              first_replicate=first_replicate, history=history, keep_paths=keep_paths, t0=t0, on_device=bool(gpu),
-                             device=self._device)
+                             device=self._device, lags=lags, lagged_on_device=lagged_on_device)
 
-    def predictive_check(self, replicates=8, seed=0, data=0, gpu=None):
+    def cross_correlogram(self, data=0, lags=1, gpu=None):
+        """the observed lagged cross-correlogram of data set `data`, (lags, N, N): c[l, i, j] says whether neuron i firing at t predicts neuron j
+        firing l bins later (simulate.correlogram).  gpu as for simulate(); on the device the sums come from pgl_lagged_products, on the int8
+        matrix cores if the data are integers of [-127, 127]."""
+        from . import simulate as _sim
+        Y = np.asarray(self.data_list[data][1], dtype=np.float64)
+        K = _sim.check_lags(lags, Y.shape[0])
+        if K < 1:
+            raise ValueError("cross_correlogram(): lags >= 1 is required")
+        if self._engine_factory is not None:               # as simulate(): such a model stays on the host
+            gpu = False
+        if gpu is None or gpu:
+            import torch
+            if not torch.cuda.is_available():
+                if gpu:
+                    raise _sim.PglError("cross_correlogram(gpu=True) needs a ROCm GPU (torch.cuda.is_available() is False)")
+                gpu = False
+        S = _sim.lagged_products_device(Y, K, device=self._device) if gpu or gpu is None else _sim.lagged_products_host(Y, K)
+        return _sim.correlogram(S, Y.sum(axis=0), (Y * Y).sum(axis=0), Y.shape[0])
+
+    def predictive_check(self, replicates=8, seed=0, data=0, gpu=None, lags=0):
         """a posterior predictive check of data set `data` bound to this model (simulate.PredictiveCheck): call its collect() after every
         sweep to be kept -- it simulates `replicates` fresh trajectories of the data set's length from the current state --, read
-        rate_quantiles(q) / fano_quantiles(q) / pvalue("rate" | "fano") at the end.  Changes nothing in the chain."""
+        rate_quantiles(q) / fano_quantiles(q) / pvalue("rate" | "fano") at the end.  lags = K > 0 adds the lagged cross-correlogram, the
+        statistic that sees the coupling: pvalue("xcorr"), xcorr_mean, xcorr_std, each (K, N, N).  Changes nothing in the chain."""
         from .simulate import PredictiveCheck
-        return PredictiveCheck(self, replicates=replicates, seed=seed, data=data, gpu=gpu)
+        return PredictiveCheck(self, replicates=replicates, seed=seed, data=data, gpu=gpu, lags=lags)
 
     # ---- Gibbs
     def resample_model(self):

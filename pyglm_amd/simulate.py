@@ -138,6 +138,9 @@ KINDS = ("bernoulli", "gaussian", "negbin", "binomial")
 NEGBIN_CAP = 65535
 BINOMIAL_MAX_N = 64
 HOST_BLOCK_BINS = 4096          # bins the host path keeps in its rolling buffer when the paths are not kept
+PGL_LAG_MAX = 256               # lags of the cross-correlogram at most (include/pyglm_hip.h)
+LAG_I8, LAG_F64 = 0, 1          # modes of pgl_lagged_products: the counts on the int8 matrix cores (exact), any real Y through the fp64 contraction
+LAG_REDOS = 0                   # folds of simulate_device that the int8 mode refused (a count beyond 127) and the fp64 mode redid, since import
 
 _M32 = np.uint64(0xFFFFFFFF)
 
@@ -263,11 +266,20 @@ def host_draw(kind, par, psi, u1, u2):
 class Simulation(object):
     """what model.simulate() returns: Y (R, T, N) float64 or None (keep_paths=False); sum and sumsq (R, N), the sums of y and y^2 over the T
     bins, added in time order; history (R, L, N), the last L bins of every replicate in time order; t0 / t1, the first bin simulated and the
-    first bin not simulated; seed and first_replicate.  Passed as `history=` of the next call it continues the same trajectories."""
+    first bin not simulated; seed and first_replicate.  Passed as `history=` of the next call it continues the same trajectories.
+    With lags = K > 0: lagged (R, K, N, N), the lagged products of the T bins of this call (lagged_products_host states them; a device tensor
+    if the caller asked for that), and lag_redos, the folds that the int8 kernel refused and the fp64 one redid."""
 
-    def __init__(self, Y, sum, sumsq, history, t0, t1, seed, first_replicate):
+    def __init__(self, Y, sum, sumsq, history, t0, t1, seed, first_replicate, lagged=None, lag_redos=0):
         self.Y, self.sum, self.sumsq, self.history = Y, sum, sumsq, history
         self.t0, self.t1, self.seed, self.first_replicate = int(t0), int(t1), int(seed), int(first_replicate)
+        self.lagged, self.lag_redos = lagged, int(lag_redos)
+
+    def correlogram(self):
+        """the lagged cross-correlogram of every replicate, (R, K, N, N): correlogram() of `lagged`"""
+        if self.lagged is None:
+            raise ValueError("correlogram(): simulate(..., lags=K) with K > 0 collects the lagged products")
+        return correlogram(self.lagged, self.sum, self.sumsq, self.T)
 
     @property
     def T(self):
@@ -290,6 +302,122 @@ def fano_factor(s, ss, T):
     var = np.asarray(ss, dtype=np.float64) / T - mean * mean
     with np.errstate(divide="ignore", invalid="ignore"):
         return np.where(mean != 0.0, var / mean, np.nan)
+
+
+def check_lags(lags, T):
+    """K = int(lags) of a series of T bins: 0 <= K <= PGL_LAG_MAX and K - 1 < T, else ValueError"""
+    K = int(lags)
+    if K < 0 or K > PGL_LAG_MAX:
+        raise ValueError("lags = %d: 0 <= lags <= PGL_LAG_MAX = %d is required" % (K, PGL_LAG_MAX))
+    if K > 0 and K - 1 >= T:
+        raise ValueError("lags = %d needs more than %d bins, got T = %d" % (K, K - 1, T))
+    return K
+
+
+def lagged_products_host(Y, lags):
+    """THE DEFINITION of the lagged products of a series Y (T, N): S (K, N, N), S[l, i, j] = sum_{t = 0}^{T-1-l} Y[t, i] Y[t+l, j] -- neuron i
+    leads neuron j by l bins --, one matrix product per lag"""
+    Y = np.asarray(Y, dtype=np.float64)
+    T, N = Y.shape
+    K = check_lags(lags, T)
+    S = np.empty((K, N, N))
+    for l in range(K):
+        S[l] = Y[:T - l].T @ Y[l:]
+    return S
+
+
+def correlogram(S, sum, sumsq, T):
+    """the lagged cross-correlogram from the lagged products S (..., K, N, N) and the whole-series sums of y and y^2 (..., N) over T bins:
+    c[l, i, j] = (S[l, i, j] / (T - l) - m_i m_j) / sqrt(v_i v_j), m = sum / T, v = sumsq / T - m^2; NaN where v_i v_j <= 0.  NumPy arrays,
+    or torch tensors (every operand on the device of S): the same operations in the same order"""
+    K = S.shape[-3]
+    if isinstance(S, np.ndarray):
+        mean = np.asarray(sum, dtype=np.float64) / T
+        var = np.asarray(sumsq, dtype=np.float64) / T - mean * mean
+        cnt = (T - np.arange(K, dtype=np.float64))[:, None, None]
+        den = var[..., None, :, None] * var[..., None, None, :]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            c = (S / cnt - mean[..., None, :, None] * mean[..., None, None, :]) / np.sqrt(den)
+        return np.where(den > 0.0, c, np.nan)
+    import torch
+    mean = sum / T
+    var = sumsq / T - mean * mean
+    cnt = (T - torch.arange(K, dtype=torch.float64, device=S.device))[:, None, None]
+    den = var[..., None, :, None] * var[..., None, None, :]
+    c = (S / cnt - mean[..., None, :, None] * mean[..., None, None, :]) / torch.sqrt(den)
+    return torch.where(den > 0.0, c, torch.full_like(c, float("nan")))
+
+
+def _fold_host(S, buf, a, b, prev):
+    """S (R, K, N, N) += the lagged products of the new rows buf[:, a:b] with themselves and with the `prev` rows before them"""
+    for l in range(S.shape[1]):
+        u0 = max(0, l - prev)
+        if u0 < b - a:
+            S[:, l] += np.matmul(buf[:, a + u0 - l:b - l].transpose(0, 2, 1), buf[:, a + u0:b])
+
+
+def lag_mode_of(Y):
+    """LAG_I8 if every value of the array is an integer of [-127, 127] (the int8 kernel takes it), else LAG_F64"""
+    Y = np.asarray(Y)
+    return LAG_I8 if Y.size == 0 or (np.all(np.abs(Y) <= 127.0) and np.all(Y == np.rint(Y))) else LAG_F64
+
+
+def lagged_products_device(Y, lags, mode=None, device=None):
+    """lagged_products_host(Y, lags) of Y (T, N) through pgl_lagged_products, as one chunk; mode None: LAG_I8 where lag_mode_of(Y) allows it"""
+    import torch
+    dev, st = _device("cross_correlogram", device)
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    T, N = Y.shape
+    K = check_lags(lags, T)
+    mode = lag_mode_of(Y) if mode is None else mode
+    with torch.cuda.device(dev):
+        Y_d = torch.from_numpy(Y).to(dev)
+        S = torch.empty((K, N, N), dtype=torch.float64, device=dev)
+        work = torch.empty(_lib.load().pgl_lagged_work_bytes(N, K, 1, T), dtype=torch.uint8, device=dev)
+        status = torch.zeros(4, dtype=torch.int32, device=dev)
+        call("pgl_lagged_products", ptr(Y_d), N, T * N, T, 0, N, K, 1, ptr(S), K * N * N, 0, mode, ptr(work), ptr(status), st)
+        code = status.cpu().numpy()
+        if code[0]:
+            raise PglError("pgl_lagged_products: the value of neuron %d at row %d is no integer of [-127, 127]" % (code[3], code[1]))
+        return S.cpu().numpy()
+
+
+class _LagFold(object):
+    """the running lagged products of simulate_device: S (R, K, N, N) on the device, folded chunk by chunk through pgl_lagged_products.  The mode
+    is fp64 if a neuron is Gaussian, else int8; where counts can pass 127 (negative-binomial neurons) the status of every int8 fold is read,
+    and a refused fold -- S untouched, the chunk still in the buffer -- is redone in fp64."""
+
+    def __init__(self, dev, st, N, K, R, max_rows, kind):
+        import torch
+        self.dev, self.st, self.N, self.K, self.R = dev, st, N, K, R
+        self.S = torch.empty((R, K, N, N), dtype=torch.float64, device=dev)
+        self.work = torch.empty(_lib.load().pgl_lagged_work_bytes(N, K, R, max_rows), dtype=torch.uint8, device=dev)
+        self.status = torch.zeros(4, dtype=torch.int32, device=dev)
+        self.mode = LAG_F64 if np.any(kind == KIND_GAUSSIAN) else LAG_I8
+        self.unbounded = bool(np.any(kind == KIND_NEGBIN))
+        self.first, self.redos = True, 0
+
+    def _call(self, Y, strideY, rows, prev, mode):
+        call("pgl_lagged_products", ptr(Y), self.N, strideY, rows, prev, self.N, self.K, self.R, ptr(self.S), self.K * self.N * self.N,
+             0 if self.first else 1, mode, ptr(self.work), ptr(self.status), self.st)
+
+    def fold(self, Y, strideY, rows, prev):
+        """Y: the tensor that starts at the first new row of replicate 0"""
+        global LAG_REDOS
+        self._call(Y, strideY, rows, prev, self.mode)
+        if self.mode == LAG_I8 and self.unbounded and int(self.status[0]) == 3:      # (reading the status waits for the fold)
+            self.status.zero_()
+            self._call(Y, strideY, rows, prev, LAG_F64)
+            self.redos += 1
+            LAG_REDOS += 1
+        self.first = False
+
+    def finish(self):
+        code = self.status.cpu().numpy()
+        if code[0]:
+            raise PglError("pgl_lagged_products: neuron %d of replicate %d at row %d of its chunk is no integer of [-127, 127]"
+                           % (code[3], code[2], code[1]))
+        return self.S
 
 
 def _initial_history(history, R, L, N, t0):
@@ -319,23 +447,29 @@ def _raise_cap(t, rep, n):
                    "explodes at this state (the rate grows without bound)" % (n, rep, t, NEGBIN_CAP))
 
 
-def simulate_host(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_paths):
-    """THE LAW in NumPy, vectorised over (R, N) per bin -> Simulation"""
+def simulate_host(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_paths, lags=0):
+    """THE LAW in NumPy, vectorised over (R, N) per bin -> Simulation.  lags = K > 0: the lagged products of the T bins as well, folded block by
+    block from the rolling buffer, which then keeps max(L, K - 1) rows in front"""
     Wm = np.ascontiguousarray(Wm, dtype=np.float64)
     N = Wm.shape[0]
     L, B = basis.shape
     WmT = np.ascontiguousarray(Wm.T)
     bias = np.asarray(bias, dtype=np.float64).reshape(N)
     C = T if keep_paths else min(T, HOST_BLOCK_BINS)
-    buf = np.zeros((R, L + C, N))
-    buf[:, :L] = hist
+    K = int(lags)
+    H = max(L, K - 1)                                # rows in front of the block: the history, and the partners of the first K - 1 new bins
+    buf = np.zeros((R, H + C, N))
+    buf[:, H - L:H] = hist
     s, ss = np.zeros((R, N)), np.zeros((R, N))
+    S = np.zeros((R, K, N, N)) if K else None
     neurons, reps = np.arange(N), rep0 + np.arange(R)
-    pos = L                                          # buf[:, pos] receives bin t
+    pos = H                                          # buf[:, pos] receives bin t
     for t in range(t0, t0 + T):
-        if pos == L + C:
-            buf[:, :L] = buf[:, C:].copy()
-            pos = L
+        if pos == H + C:
+            if K:
+                _fold_host(S, buf, H, pos, min(K - 1, t - t0 - C))
+            buf[:, :H] = buf[:, C:].copy()
+            pos = H
         x = np.einsum("rlm,lb->rmb", buf[:, pos - L:pos][:, ::-1], basis)
         psi = x.reshape(R, N * B).dot(WmT) + bias
         u1, u2 = sim_uniforms(seed, t, neurons, reps)
@@ -346,18 +480,31 @@ def simulate_host(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_p
         s += y
         ss += y * y
         pos += 1
-    return Simulation(buf[:, L:L + T].copy() if keep_paths else None, s, ss, buf[:, pos - L:pos].copy(), t0, t0 + T, seed, rep0)
+    if K:
+        _fold_host(S, buf, H, pos, min(K - 1, T - (pos - H)))
+    return Simulation(buf[:, H:H + T].copy() if keep_paths else None, s, ss, buf[:, pos - L:pos].copy(), t0, t0 + T, seed, rep0, lagged=S)
 
 
-def simulate_device(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_paths, device=None):
-    """THE LAW through pgl_simulate, a chunk of bins per launch -> Simulation"""
+def simulate_device(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_paths, device=None, lags=0, lagged_on_device=False):
+    """THE LAW through pgl_simulate, a chunk of bins per launch -> Simulation.  lags = K > 0: every launch writes its bins behind the K - 1 bins
+    before them -- into the paths if they are kept, else into a buffer of K - 1 + chunk rows per replicate -- and pgl_lagged_products folds
+    them into the running sums (_LagFold); the sums come back as a device tensor if lagged_on_device"""
     import torch
     dev, st = _device("simulate", device)
     N = np.shape(Wm)[0]
     L, B = np.shape(basis)
     Tc = chunk_bins(N, B, R)
+    K = int(lags)
     with torch.cuda.device(dev):
         f64 = dict(dtype=torch.float64, device=dev)
+        if K:
+            Tb = K - 1 + min(Tc, T)                                  # rows of the path buffer
+            need = 8 * R * K * N * N + _lib.load().pgl_lagged_work_bytes(N, K, R, min(Tc, T)) + 8 * R * (T if keep_paths else Tb) * N
+            free = torch.cuda.mem_get_info(dev)[0]
+            if need > free:
+                raise PglError("simulate(lags=%d, replicates=%d): the lagged products of %d replicates x %d lags x %d x %d neuron pairs, their "
+                               "scratch and the paths need %d bytes of device memory, %d are free: ask for fewer lags or fewer replicates per "
+                               "call" % (K, R, R, K, N, N, need, free))
         if keep_paths:
             need = 8 * R * T * N
             free = torch.cuda.mem_get_info(dev)[0]
@@ -372,24 +519,35 @@ def simulate_device(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep
         ring_h[:, rows] = hist
         ring = torch.from_numpy(ring_h).to(dev)
         Y_d = torch.empty((R, T, N), **f64) if keep_paths else None
+        fold = _LagFold(dev, st, N, K, R, min(Tc, T), kind) if K else None
+        buf = torch.empty((R, Tb, N), **f64) if K and not keep_paths else None
         sum_d, sq_d = torch.zeros((R, N), **f64), torch.zeros((R, N), **f64)
         work = torch.zeros(_lib.load().pgl_simulate_work_bytes(N, B, R), dtype=torch.uint8, device=dev)
         status = torch.zeros(4, dtype=torch.int32, device=dev)
         status_h = torch.zeros(4, dtype=torch.int32).pin_memory()
         for k0 in range(0, T, Tc):
             n = min(Tc, T - k0)
+            out, ldr = (Y_d[0, k0:], T * N) if keep_paths else (buf[0, K - 1:], Tb * N) if K else (None, T * N)
             call("pgl_simulate", ptr(Wm_d), ptr(bias_d), ptr(basis_d), N, B, L, ptr(kind_d), ptr(par_d), R, rep0, seed & (2 ** 64 - 1), ptr(ring),
-                 ptr(Y_d[0, k0:]) if keep_paths else None, T * N, ptr(sum_d), ptr(sq_d), t0 + k0, n, ptr(work), ptr(status), st)
+                 ptr(out), ldr, ptr(sum_d), ptr(sq_d), t0 + k0, n, ptr(work), ptr(status), st)
             _finish_launch("pgl_simulate", dev, status, status_h, t0 + k0, t0 + k0 + n - 1)
+            if K:
+                fold.fold(out, ldr, n, min(K - 1, k0))
+                if not keep_paths and K > 1 and k0 + n < T:
+                    buf[:, :K - 1] = buf[:, n:n + K - 1].clone()     # the last K - 1 bins move to the front (the ranges overlap when n < K - 1)
         rows = (t0 + T - L + np.arange(L)) % L
+        lagged = fold.finish() if K else None
+        if K and not lagged_on_device:
+            lagged = lagged.cpu().numpy()
         return Simulation(Y_d.cpu().numpy() if keep_paths else None, sum_d.cpu().numpy(), sq_d.cpu().numpy(), ring.cpu().numpy()[:, rows],
-                          t0, t0 + T, seed, rep0)
+                          t0, t0 + T, seed, rep0, lagged=lagged, lag_redos=fold.redos if K else 0)
 
 
 def simulate(Wm, bias, basis, kind, par, T, replicates=1, seed=0, first_replicate=0, history=None, keep_paths=True, t0=None, on_device=False,
-             device=None):
+             device=None, lags=0, lagged_on_device=False):
     """R = `replicates` trajectories of T bins of the model (Wm = a*W as (N, N*B), bias, basis (L, B), per-neuron kind / par) -> Simulation;
-    on the device (pgl_simulate) or in NumPy.  What model.simulate() calls once it has read the model."""
+    on the device (pgl_simulate) or in NumPy.  What model.simulate() calls once it has read the model.  lags = K > 0 (K - 1 < T): the
+    Simulation carries the lagged products of its T bins (lagged_products_host) as well; lagged_on_device leaves them on the device."""
     N = np.shape(Wm)[0]
     L = basis.shape[0]
     T, R, rep0, seed = int(T), int(replicates), int(first_replicate), int(seed)
@@ -399,10 +557,13 @@ def simulate(Wm, bias, basis, kind, par, T, replicates=1, seed=0, first_replicat
     if t0 + T >= 2 ** 31 or rep0 + R >= 2 ** 31:
         raise ValueError("simulate(): time bins and replicate indices must stay below 2^31")
     kind, par = np.asarray(kind, dtype=np.int32), np.asarray(par, dtype=np.float64)
+    K = check_lags(lags, T)
     if T == 0:
         return Simulation(np.zeros((R, 0, N)) if keep_paths else None, np.zeros((R, N)), np.zeros((R, N)), hist, t0, t0, seed, rep0)
     run = simulate_device if on_device else simulate_host
     kw = dict(device=device) if on_device else {}
+    if K:
+        kw.update(dict(lags=K, lagged_on_device=lagged_on_device) if on_device else dict(lags=K))
     return run(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_paths, **kw)
 
 
@@ -418,21 +579,78 @@ class PredictiveCheck(object):
 
     collect() simulates `replicates` fresh trajectories of the data set's length from the model's current state (from silence, paths not
     kept; the k-th call uses replicate indices k R ... k R + R - 1, so no two calls share a stream) and keeps their per-neuron rates and
-    Fano factors -- (S R, N) after S calls -- on the host."""
+    Fano factors -- (S R, N) after S calls -- on the host.
 
-    def __init__(self, model, replicates=8, seed=0, data=0, gpu=None):
+    lags = K > 0 adds the pairwise statistic "xcorr", the lagged cross-correlogram (K, N, N) -- the one that sees the coupling: observed["xcorr"]
+    is the data's (model.cross_correlogram), and collect() folds every replicate's correlogram, cell by cell, into #{rep >= obs}, #{rep <= obs},
+    the number of replicates in which the cell is defined, and a Welford mean and M2 -- where the simulation ran (torch on the device, else
+    NumPy); the replicated correlograms themselves are never stacked.  pvalue("xcorr"), xcorr_mean and xcorr_std read them."""
+
+    def __init__(self, model, replicates=8, seed=0, data=0, gpu=None, lags=0):
         self.model, self.R, self.seed, self.gpu = model, int(replicates), int(seed), gpu
         Y = np.asarray(model.data_list[data][1], dtype=np.float64)
         self.T = Y.shape[0]
+        self.K = check_lags(lags, self.T)
         self.observed = {"rate": Y.mean(axis=0), "fano": fano_factor(Y.sum(axis=0), (Y * Y).sum(axis=0), self.T)}
+        if self.K:
+            self.observed["xcorr"] = model.cross_correlogram(data=data, lags=self.K, gpu=gpu)
         self.calls = 0
         self._rate, self._fano = [], []
+        self._xc = None                          # [obs, ge, le, n, mean, M2], each (K, N, N), on the device of the simulations or in NumPy
 
     def collect(self):
-        sim = self.model.simulate(self.T, replicates=self.R, seed=self.seed, first_replicate=self.calls * self.R, keep_paths=False, gpu=self.gpu)
+        sim = self.model.simulate(self.T, replicates=self.R, seed=self.seed, first_replicate=self.calls * self.R, keep_paths=False, gpu=self.gpu,
+                                  lags=self.K, lagged_on_device=True)
         self.calls += 1
         self._rate.append(sim.rate())
         self._fano.append(sim.fano())
+        if self.K:
+            self._collect_xcorr(sim)
+
+    def _collect_xcorr(self, sim):
+        S = sim.lagged
+        if isinstance(S, np.ndarray):
+            xp, s, ss = np, sim.sum, sim.sumsq
+            zeros = lambda dtype: np.zeros(S.shape[1:], dtype=dtype)
+            obs = self.observed["xcorr"]
+            i64, f64 = np.int64, np.float64
+        else:
+            import torch
+            xp = torch
+            s, ss = torch.from_numpy(sim.sum).to(S.device), torch.from_numpy(sim.sumsq).to(S.device)
+            zeros = lambda dtype: torch.zeros(S.shape[1:], dtype=dtype, device=S.device)
+            obs = torch.from_numpy(self.observed["xcorr"]).to(S.device)
+            i64, f64 = torch.int64, torch.float64
+        if self._xc is None:
+            self._xc = [obs, zeros(i64), zeros(i64), zeros(i64), zeros(f64), zeros(f64)]
+        obs, ge, le, n, mean, M2 = self._xc
+        for r in range(S.shape[0]):              # one replicate at a time: (K, N, N) temporaries, and Welford's order
+            c = correlogram(S[r], s[r], ss[r], self.T)
+            ok = ~xp.isnan(c)
+            ge += ok & (c >= obs)
+            le += ok & (c <= obs)
+            n += ok
+            d = xp.where(ok, c - mean, xp.zeros_like(c))
+            mean += d / xp.maximum(n, xp.ones_like(n))
+            M2 += d * xp.where(ok, c - mean, xp.zeros_like(c))
+
+    def _xcorr_state(self):
+        if not self.K or self._xc is None:
+            raise ValueError("the cross-correlogram needs predictive_check(lags=K) with K > 0 and at least one collect()")
+        return [v if isinstance(v, np.ndarray) else v.cpu().numpy() for v in self._xc]
+
+    @property
+    def xcorr_mean(self):
+        """mean of the replicated correlogram over the replicates in which the cell is defined, (K, N, N); NaN where it never is"""
+        _, _, _, n, mean, _ = self._xcorr_state()
+        return np.where(n > 0, mean, np.nan)
+
+    @property
+    def xcorr_std(self):
+        """its standard deviation (n - 1 in the denominator); NaN with fewer than two defined replicates"""
+        _, _, _, n, _, M2 = self._xcorr_state()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(n > 1, np.sqrt(M2 / (n - 1.0)), np.nan)
 
     @property
     def rates(self):
@@ -454,8 +672,12 @@ class PredictiveCheck(object):
         """two-sided posterior predictive p-value of the observed statistic per neuron, (N,): with M replicated values (those that are
         defined), p = min(1, 2 min(1 + #{rep >= obs}, 1 + #{rep <= obs}) / (M + 1)) -- the smallest attainable value is 2 / (M + 1).
         NaN where the observed statistic is undefined."""
+        if stat == "xcorr":                      # the same rule per cell (K, N, N), from the streamed counts
+            obs, ge, le, M, _, _ = self._xcorr_state()
+            p = np.minimum(1.0, 2.0 * np.minimum(1 + ge, 1 + le) / (M + 1.0))
+            return np.where(np.isnan(obs), np.nan, p)
         if stat not in ("rate", "fano"):
-            raise ValueError("pvalue(): stat is 'rate' or 'fano'")
+            raise ValueError("pvalue(): stat is 'rate', 'fano' or 'xcorr'")
         rep = self.rates if stat == "rate" else self.fanos
         obs = self.observed[stat]
         ok = ~np.isnan(rep)
