@@ -2,7 +2,13 @@
 the int8 mode bit for bit -- below a tile, across tiles, lags that are no multiples of 4 or 16, rows that are no multiple of 64, K close to
 rows, chunks that compose, sums beyond 2^31, the range check that leaves S alone --, the fp64 mode bit for bit on integers and within the
 a-priori bound of a sum of `rows` products on real data; then model.simulate(lags=K), its fp64 fallback for counts beyond 127, and
-PredictiveCheck(lags=K) against the NumPy path."""
+PredictiveCheck(lags=K) against the NumPy path.
+
+The shapes follow the launch plan that lag_i8 derives from them as well as the tile edges (DESIGN.md section 12 has the table): lag groups
+past the first (K > 64, up to PGL_LAG_MAX), a workgroup that walks several 512-bin slabs with the plain and with the atomic accumulate (R
+taken from the device's compute units, each test asserting that its shape still reaches the path), ldy > N, replicate blocks further apart
+than their rows, S blocks further apart than K N N, and first chunks shorter than a lag.  Every call through _device_products also checks
+that nothing was written behind `work` or between the blocks of S."""
 import functools
 
 import numpy as np
@@ -20,24 +26,49 @@ I8, F64 = simulate.LAG_I8, simulate.LAG_F64
 SHAPES = [(4, 1, 100), (12, 17, 1000), (20, 5, 333), (70, 33, 2049), (16, 64, 70)]      # (N, K, rows)
 
 
-def _device_products(Y, K, mode, cuts=None, S0=None):
+WORK_TAIL = 4096                  # bytes of 0xA5 behind the `work` of every call: they must survive it
+
+
+def _device_products(Y, K, mode, cuts=None, S0=None, ldy=None, pad_rows=(0, 0), col0=0, strideS=None, calls=None):
     """pgl_lagged_products on Y (R, T, N), as one call or cut into the chunks `cuts` (accumulate = 1 after the first, or from the start on a
-    given S0) -> (S (R, K, N, N), status (4,)) as NumPy arrays"""
+    given S0) -> (S (R, K, N, N), status (4,)) as NumPy arrays.  `calls`: stop after that many chunks.
+    ldy > N: Y is the column window [col0, col0 + N) of rows of ldy doubles; pad_rows = (a, b): every replicate block has a rows in front of
+    its T rows and b behind; the cells that are no part of Y hold 1e6.  strideS > K N N: the blocks of S lie that far apart, the gaps hold NaN
+    and are asserted to hold it afterwards, as the WORK_TAIL bytes behind every `work` are asserted to be unchanged."""
     import torch
     from pyglm_amd._lib import call, load, ptr
     R, T, N = Y.shape
-    Y_d = torch.from_numpy(np.array(Y, dtype=np.float64)).cuda()
-    S = torch.full((R, K, N, N), float("nan"), dtype=torch.float64, device="cuda") if S0 is None else torch.from_numpy(S0.copy()).cuda()
+    ldy = N if ldy is None else ldy
+    front, behind = pad_rows
+    if ldy == N and front == 0 and behind == 0:
+        Y_d = torch.from_numpy(np.array(Y, dtype=np.float64)).cuda()
+    else:
+        assert col0 + N <= ldy
+        wide = np.full((R, front + T + behind, ldy), 1e6)
+        wide[:, front:front + T, col0:col0 + N] = Y
+        Y_d = torch.from_numpy(wide).cuda()[:, front:front + T, col0:col0 + N]
+    strideY = (front + T + behind) * ldy
+    block = K * N * N
+    strideS = block if strideS is None else strideS
+    S_all = torch.full((R, strideS), float("nan"), dtype=torch.float64, device="cuda")
+    S = S_all[:, :block]
+    if S0 is not None:
+        S.copy_(torch.from_numpy(S0.reshape(R, block)))
     status = torch.zeros(4, dtype=torch.int32, device="cuda")
-    done = 0
-    for rows in (cuts or [T]):
-        work = torch.empty(load().pgl_lagged_work_bytes(N, K, R, rows), dtype=torch.uint8, device="cuda")
-        call("pgl_lagged_products", ptr(Y_d[0, done:]), N, T * N, rows, min(K - 1, done), N, K, R, ptr(S), K * N * N,
+    done, works = 0, []
+    for rows in (cuts or [T])[:calls]:
+        nbytes = load().pgl_lagged_work_bytes(N, K, R, rows)
+        work = torch.empty(nbytes + WORK_TAIL, dtype=torch.uint8, device="cuda")
+        work[nbytes:] = 0xA5
+        works.append(work[nbytes:])
+        call("pgl_lagged_products", ptr(Y_d[0, done:]), ldy, strideY, rows, min(K - 1, done), N, K, R, ptr(S_all), strideS,
              1 if (done or S0 is not None) else 0, mode, ptr(work), ptr(status), None)
         done += rows
-    assert done == T
+    assert done == T or calls is not None
     torch.cuda.synchronize()
-    return S.cpu().numpy(), status.cpu().numpy()
+    assert all(bool((tail == 0xA5).all()) for tail in works), "bytes behind `work` were written"
+    assert bool(torch.isnan(S_all[:, block:]).all()), "the gaps between the blocks of S were written"
+    return S.cpu().numpy().reshape(R, K, N, N), status.cpu().numpy()
 
 
 @functools.lru_cache(maxsize=None)
@@ -81,7 +112,7 @@ def test_int8_sums_beyond_the_int32_range_are_exact():
         assert all(int(v) == want and v == float(want) for v in S[0, l].ravel())
 
 
-@pytest.mark.parametrize("bad", [128.0, 0.5, -128.0, float("nan")])
+@pytest.mark.parametrize("bad", [128.0, 0.5, -128.0, float("nan"), float("inf"), float("-inf"), 1e300, -1e300, 127.00000000000001])
 def test_int8_mode_refuses_what_is_no_int8_and_leaves_S_alone(bad):
     N, K, rows, R = 20, 5, 333, 3
     Yc, ref = _int_case(N, K, rows, R)
@@ -98,6 +129,135 @@ def test_int8_mode_refuses_what_is_no_int8_and_leaves_S_alone(bad):
     if bad == 128.0 or bad == -128.0:
         S, status = _device_products(Y, K, F64)
         assert status[0] == 0 and np.array_equal(S, np.stack([simulate.lagged_products_host(Y[r], K) for r in range(R)]))
+
+
+def test_int8_mode_names_one_of_several_values_that_are_no_int8():
+    N, K, rows, R = 20, 5, 333, 3
+    Yc, ref = _int_case(N, K, rows, R)
+    Y = Yc.copy()
+    bad = {(0, 311, 19): 200.0, (1, 64, 0): -0.25, (2, 5, 16): float("nan")}          # (replicate, row, neuron)
+    for (r, t, n), v in bad.items():
+        Y[r, t, n] = v
+    S0 = np.random.default_rng(3).standard_normal(ref.shape)
+    for given in (S0, None):
+        S, status = _device_products(Y, K, I8, S0=given)
+        assert status[0] == 3 and (int(status[2]), int(status[1]), int(status[3])) in bad
+        assert np.array_equal(S, S0) if given is not None else np.all(np.isnan(S))
+
+
+# ---- lag groups past the first: K > 64 (L0 > 0, F = lag_front(K) > 64, `l < K` inside a wave's 16 lags, waves that only stage)
+LONG_LAGS = [(20, 65, 333, 1), (12, 100, 1000, 3), (16, 128, 300, 1), (20, 129, 700, 2), (8, 256, 600, 2), (4, 256, 256, 1)]   # (N, K, rows, R)
+LONG_CUTS = [(12, 100, 1000, 3, [40, 1, 200, 759]), (20, 129, 700, 2, [64, 65, 571])]      # `prev` takes 0, 40, 41, 99 / 0, 64, 128
+
+
+@pytest.mark.parametrize("N,K,rows,R", LONG_LAGS)
+def test_int8_mode_with_more_than_one_lag_group_is_the_definition_bit_for_bit(N, K, rows, R):
+    Y, ref = _int_case(N, K, rows, R)
+    S, status = _device_products(Y, K, I8)
+    assert status[0] == 0
+    assert np.array_equal(S, ref)
+
+
+@pytest.mark.parametrize("N,K,rows,R,cuts", LONG_CUTS)
+def test_int8_chunks_compose_with_more_than_one_lag_group(N, K, rows, R, cuts):
+    Y, ref = _int_case(N, K, rows, R)
+    assert sum(cuts) == rows
+    S, status = _device_products(Y, K, I8, cuts=cuts)
+    assert status[0] == 0 and np.array_equal(S, ref)
+    S0 = np.random.default_rng(K).integers(-1000, 1000, size=ref.shape).astype(np.float64)
+    S, status = _device_products(Y, K, I8, cuts=cuts, S0=S0)
+    assert status[0] == 0 and np.array_equal(S, S0 + ref)
+
+
+# ---- a workgroup that walks several slabs of 512 bins: what the plan does once pairs x lag groups x replicates fill the chip.  N = 64 is
+# 16 tile pairs, K = 70 two lag groups: 32 workgroups per replicate and time split; R follows the compute units of the device.
+def _compute_units():
+    import torch
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def test_int8_slab_loop_with_the_plain_accumulate_is_the_definition_bit_for_bit():
+    N, K, rows = 64, 70, 1100
+    C = _compute_units()
+    R = -(-2 * C // 32)
+    assert 16 * 2 * R >= 2 * C and rows > 2 * 512         # two workgroups per compute unit without a time split: slabs of 512, 512 and 128 bins
+    Y, ref = _int_case(N, K, rows, R)
+    S, status = _device_products(Y, K, I8)
+    assert status[0] == 0 and np.array_equal(S, ref)
+    S, status = _device_products(Y, K, I8, cuts=[600, 500])
+    assert status[0] == 0 and np.array_equal(S, ref)
+    S0 = np.random.default_rng(4).integers(-1000, 1000, size=ref.shape).astype(np.float64)
+    S, status = _device_products(Y, K, I8, S0=S0)
+    assert status[0] == 0 and np.array_equal(S, S0 + ref)
+
+
+def test_int8_slab_loop_with_atomic_adds_is_the_definition_bit_for_bit():
+    N, K, rows = 64, 70, 2500
+    C = _compute_units()
+    R = -(-C // 32)
+    rows64 = -(-rows // 64) * 64
+    assert -(-2 * C // (32 * R)) < -(-rows64 // 512)      # fewer time splits than slabs: a split spans several (two of 1280 bins at 256 units)
+    Y, ref = _int_case(N, K, rows, R)
+    S, status = _device_products(Y, K, I8)
+    assert status[0] == 0 and np.array_equal(S, ref)
+
+
+# ---- the layouts the ABI allows besides the packed one
+def _f64_int_case(N, K, rows, R):
+    """integers beyond the int8 range, whose lagged products the fp64 mode must give exactly, and these by the definition"""
+    Y = np.random.default_rng(rows + K).integers(-3000, 3000, size=(R, rows, N)).astype(np.float64)
+    return Y, np.stack([simulate.lagged_products_host(Y[r], K) for r in range(R)])
+
+
+STRIDED = [(20, 5, 333, 3), (20, 65, 333, 2)]               # (N, K, rows, R)
+
+
+@pytest.mark.parametrize("mode", [I8, F64])
+@pytest.mark.parametrize("N,K,rows,R", STRIDED)
+def test_rows_and_replicates_further_apart_than_packed(N, K, rows, R, mode):
+    # the window [3, 3 + N) of rows of N + 7 doubles, 5 more rows per replicate block (2 in front, 3 behind); every other cell holds 1e6: read
+    # by the int8 mode it would set status 3, by the fp64 mode it would spoil the sums
+    Y, ref = _int_case(N, K, rows, R) if mode == I8 else _f64_int_case(N, K, rows, R)
+    for cuts in (None, [100, 1, 232]):
+        S, status = _device_products(Y, K, mode, cuts=cuts, ldy=N + 7, pad_rows=(2, 3), col0=3)
+        assert list(status) == [0, 0, 0, 0] and np.array_equal(S, ref)
+
+
+@pytest.mark.parametrize("mode", [I8, F64])
+@pytest.mark.parametrize("N,K,rows,R", STRIDED)
+def test_blocks_of_S_further_apart_than_packed(N, K, rows, R, mode):
+    # (the helper asserts that the 11 doubles behind every block still hold their NaN)
+    Y, ref = _int_case(N, K, rows, R) if mode == I8 else _f64_int_case(N, K, rows, R)
+    strideS = K * N * N + 11
+    S, status = _device_products(Y, K, mode, strideS=strideS)
+    assert status[0] == 0 and np.array_equal(S, ref)
+    S0 = np.random.default_rng(5).integers(-1000, 1000, size=ref.shape).astype(np.float64)
+    S, status = _device_products(Y, K, mode, S0=S0, strideS=strideS)
+    assert status[0] == 0 and np.array_equal(S, S0 + ref)
+    S, status = _device_products(Y, K, mode, cuts=[100, 1, 232], strideS=strideS, ldy=N + 7, pad_rows=(2, 3), col0=3)
+    assert status[0] == 0 and np.array_equal(S, ref)
+    if mode == I8:                                            # refused: S and the gaps as they were
+        bad = Y.copy()
+        bad[R - 1, 300, 17] = 128.0
+        for given in (S0, None):
+            S, status = _device_products(bad, K, I8, S0=given, strideS=strideS)
+            assert list(status) == [3, 300, R - 1, 17]
+            assert np.array_equal(S, S0) if given is not None else np.all(np.isnan(S))
+
+
+# ---- a first chunk shorter than a lag
+SHORT_FIRST = [(12, 17, 1000), (21, 5, 333)]
+
+
+def _short_cuts(rows):
+    return [3, 1, 2, rows - 6]
+
+
+@pytest.mark.parametrize("N,K,rows", SHORT_FIRST)
+def test_int8_chunks_compose_from_a_first_chunk_shorter_than_a_lag(N, K, rows):
+    Y, ref = _int_case(N, K, rows, 2)
+    S, status = _device_products(Y, K, I8, cuts=_short_cuts(rows))
+    assert status[0] == 0 and np.array_equal(S, ref)
 
 
 @pytest.mark.parametrize("N,K,rows", [(12, 17, 1000), (21, 5, 333), (70, 33, 2049)])
@@ -138,6 +298,31 @@ def test_fp64_mode_on_real_data_is_within_the_summation_bound(N, K, rows):
     _assert_within_summation_bound(S[0], Y[0], K)
 
 
+@pytest.mark.parametrize("N,K,rows,cuts", [(N, K, rows, cuts) for N, K, rows, _, cuts in LONG_CUTS])
+def test_fp64_mode_is_exact_on_integers_with_more_than_64_lags(N, K, rows, cuts):
+    Y, ref = _f64_int_case(N, K, rows, 2)
+    S, status = _device_products(Y, K, F64)
+    assert status[0] == 0 and np.abs(Y).max() > 127 and np.array_equal(S, ref)
+    S, _ = _device_products(Y, K, F64, cuts=cuts)
+    assert np.array_equal(S, ref)
+
+
+@pytest.mark.parametrize("N,K,rows", SHORT_FIRST)
+def test_fp64_chunks_compose_from_a_first_chunk_shorter_than_a_lag(N, K, rows):
+    # rows = 3 < K and accumulate = 0: the lags l >= 3 have no product in the first call, and their blocks of S, NaN before it, must become zero
+    Y, ref = _f64_int_case(N, K, rows, 2)
+    cuts = _short_cuts(rows)
+    S, status = _device_products(Y, K, F64, cuts=cuts, calls=1)
+    assert status[0] == 0 and np.all(S[:, 3:] == 0.0)
+    assert np.array_equal(S[:, :3], np.stack([simulate.lagged_products_host(Y[r, :3], 3) for r in range(2)]))
+    S, status = _device_products(Y, K, F64, cuts=cuts)
+    assert status[0] == 0 and np.array_equal(S, ref)
+    Yr = np.random.default_rng(N + K).standard_normal((1, rows, N))
+    S, status = _device_products(Yr, K, F64, cuts=cuts)
+    assert status[0] == 0
+    _assert_within_summation_bound(S[0], Yr[0], K)
+
+
 # ---- the model
 _MAKE = {
     "bernoulli": lambda N, B, i: SparseBernoulliRegression(N, B, mu_b=-2.0, S_b=0.1),
@@ -162,7 +347,8 @@ def _model(N, B, L, kinds, seed, w_scale=None):
     return model
 
 
-MODELS = [(12, 3, 30, ("bernoulli", "binomial"), 3, 2000, 20), (64, 5, 100, ("bernoulli",), 8, 1500, 50)]
+MODELS = [(12, 3, 30, ("bernoulli", "binomial"), 3, 2000, 20), (64, 5, 100, ("bernoulli",), 8, 1500, 50),
+          (12, 3, 30, ("bernoulli", "binomial"), 3, 2000, 100)]                          # the last: two lag groups
 
 
 @functools.lru_cache(maxsize=None)
@@ -192,9 +378,9 @@ def test_simulate_on_the_device_folds_the_lagged_products_of_its_paths(case):
     assert plain.lagged is None and np.array_equal(plain.Y, host.Y)
 
 
-@pytest.mark.parametrize("case,chunk", [(0, 7), (0, 300), (1, 37), (1, 400)])
+@pytest.mark.parametrize("case,chunk", [(0, 7), (0, 300), (1, 37), (1, 400), (2, 37)])
 def test_simulate_folds_the_same_sums_whatever_the_chunks(case, chunk, monkeypatch):
-    # 7 < K - 1 = 19 and 37 < K - 1 = 49: a chunk shorter than the rows kept before it; none of the four divides T
+    # 7 < K - 1 = 19, 37 < K - 1 = 49 and 37 < K - 1 = 99: a chunk shorter than the rows kept before it; none of the five divides T
     N, B, L, kinds, R, T, K = MODELS[case]
     model, host = _model_case(case)
     assert T % chunk != 0
@@ -251,8 +437,15 @@ def test_cross_correlogram_of_a_data_set():
     assert d.shape == (15, 12, 12) and np.array_equal(d, h, equal_nan=True) and np.isfinite(d).any()
 
 
-def test_predictive_check_with_lags_matches_the_host_path():
-    N, R, K = 12, 4, 10
+def test_cross_correlogram_of_a_data_set_with_three_lag_groups():
+    model = _model(12, 3, 30, ("bernoulli", "binomial"), seed=51)
+    model.add_data(model.simulate(1200, seed=52, gpu=False).Y[0])
+    d, h = model.cross_correlogram(lags=130, gpu=True), model.cross_correlogram(lags=130, gpu=False)
+    assert d.shape == (130, 12, 12) and np.array_equal(d, h, equal_nan=True) and np.isfinite(d).any()
+
+
+def _predictive_check_matches_the_host_path(K):
+    N, R = 12, 4
     model = _model(N, 3, 30, ("bernoulli", "binomial"), seed=61)
     model.add_data(model.simulate(1000, seed=62, gpu=False).Y[0])
     out = []
@@ -270,3 +463,11 @@ def test_predictive_check_with_lags_matches_the_host_path():
     np.testing.assert_allclose(d.xcorr_std, h.xcorr_std, rtol=0, atol=1e-12)
     for stat in ("rate", "fano"):
         assert np.array_equal(d.pvalue(stat), h.pvalue(stat), equal_nan=True)
+
+
+def test_predictive_check_with_lags_matches_the_host_path():
+    _predictive_check_matches_the_host_path(10)
+
+
+def test_predictive_check_with_two_lag_groups_matches_the_host_path():
+    _predictive_check_matches_the_host_path(70)
