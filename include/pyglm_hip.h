@@ -422,6 +422,23 @@ size_t pgl_lagged_work_bytes(int N, int K, int R, int rows);
 int pgl_lagged_products(const double* Y, long ldy, long strideY, int rows, int prev, int N, int K, int R, double* S, long strideS, int accumulate,
                         int mode, void* work, int* status, void* hip_stream);
 
+/* ---- inter-spike intervals (pgl_isi.hip): the single-train statistic of the posterior predictive check ------------------------------------ */
+/* This project's own statistic; it replaces no reference call site.  An event of column (r, n) is a row with Y > 0 (a count above 1 is one
+ * event; NaN and negative values are none); an interval is the distance in rows between two consecutive events of a column.
+ *   hist[r][n][d - 1] (+)= intervals of length d < D, hist[r][n][D - 1] (+)= those of length >= D;   2 <= D <= PGL_ISI_MAX_BINS
+ *   moments[r][n] = (M, sum d, sum d^2) over all intervals, unclipped, exact
+ *   since[r][n] = rows from the column's last event to the end of the folded rows (0: an event in the last row; -1: no event so far)
+ * Y[r * strideY + u * ldy + n], u < rows.  accumulate = 0: hist and moments start from zero and since from -1, whatever they hold; 1: they
+ * continue -- the first event of a column at row u closes an interval of u + 1 + since rows when since >= 0 --, so calls on consecutive chunks
+ * add up to the intervals of the whole series.  rows = 0 is allowed.  Parallel in time: a workgroup owns pgl_isi_segment_rows() rows of 64
+ * columns; a second launch stitches the segments' records in work (pgl_isi_work_bytes(N, R, rows) bytes).  The total number of rows folded
+ * into one since stays below 2^31.  A refused argument returns PGL_ERR_ARG (1) and writes nothing. */
+#define PGL_ISI_MAX_BINS 256
+int pgl_isi_segment_rows(void);
+size_t pgl_isi_work_bytes(int N, int R, int rows);
+int pgl_isi_fold(const double* Y, long ldy, long strideY, int rows, int N, int R, int D, int* hist, long long* moments, int* since, int accumulate,
+                 void* work, void* hip_stream);
+
 /* ---- box calibration (diagnostic; nothing on the sampling path calls it) ------------------------------------------------------- */
 /* What the matrix cores of the current device sustain right now: a register-only MFMA loop on every CU for ~`seconds` (a quarter of it
  * untimed first, so that clocks and the package power limiter settle), timed with HIP events on `stream`; WAITS for the stream.

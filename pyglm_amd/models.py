@@ -492,7 +492,8 @@ class NonlinearAutoregressiveModel(object):
             self.add_data(Y[L:], X=X[L:])
         return X[L:], Y[L:]
 
-    def simulate(self, T, replicates=1, seed=0, first_replicate=0, history=None, keep_paths=True, gpu=None, t0=None, lags=0, lagged_on_device=False):
+    def simulate(self, T, replicates=1, seed=0, first_replicate=0, history=None, keep_paths=True, gpu=None, t0=None, lags=0, lagged_on_device=False,
+                 isi=0):
         """Posterior predictive simulation: `replicates` independent trajectories of T bins from the model's CURRENT state, every neuron
         drawing from its own regression's observation model (Bernoulli, Gaussian, negative binomial, binomial; mixed lists work).  Unlike
         generate() -- which stays the reference's loop, quirks included -- the activation is that of `means` and log_likelihood(),
@@ -514,11 +515,18 @@ class NonlinearAutoregressiveModel(object):
         device the sums are folded after every launch by pgl_lagged_products -- on the int8 matrix cores, exactly, when the neurons are
         Bernoulli or binomial; negative-binomial neurons fall back to fp64 for the chunks in which a count passes 127; fp64 if a neuron is
         Gaussian -- with keep_paths=False too; the memory they need is checked first.  lagged_on_device leaves `lagged` a torch tensor.
+        isi = D (2 <= D <= simulate.PGL_ISI_MAX_BINS): the Simulation also carries `isi` (R, N, D) and `isi_moments` (R, N, 3), the
+        inter-spike-interval histogram and (M, sum d, sum d^2) of every train (simulate.isi_host), and isi_density(), isi_mean(), isi_cv().
+        A bin with a positive count is one event, whatever the count; a Gaussian neuron has no events and is refused by name.  The
+        intervals are those between the events of the T bins of this call: continuing from a `history=` does not count the interval from
+        the history's last event.  On the device pgl_isi_fold folds them after every launch.
         On a sharded model every rank holds the gathered state: each rank computes the same result on its own device, with no collective."""
         from . import simulate as _sim
         from ._lib import PglError
         A, W, b = self._adopt_state()
         kind, par = _sim.observation_kinds(self.regressions)
+        if _sim.check_isi_bins(isi):
+            self._refuse_gaussian_intervals("simulate(isi=%d)" % isi)
         if self._engine_factory is not None:
             if gpu:
                 raise ValueError("simulate(gpu=True): a model with an engine_factory takes the NumPy path (gpu=None or False)")
@@ -534,7 +542,34 @@ class NonlinearAutoregressiveModel(object):
         Wm = (W * A[:, :, None]).reshape(self.N, self.N * self.B)
         return _sim.simulate(Wm, b.ravel(), np.asarray(self.basis, dtype=np.float64), kind, par, T, replicates=replicates, seed=seed,
                              first_replicate=first_replicate, history=history, keep_paths=keep_paths, t0=t0, on_device=bool(gpu),
-                             device=self._device, lags=lags, lagged_on_device=lagged_on_device)
+                             device=self._device, lags=lags, lagged_on_device=lagged_on_device, isi=isi)
+
+    def _refuse_gaussian_intervals(self, what):
+        from . import simulate as _sim
+        kind, _ = _sim.observation_kinds(self.regressions)
+        bad = np.flatnonzero(kind == _sim.KIND_GAUSSIAN)
+        if bad.size:
+            raise ValueError("%s: neuron %d is Gaussian; an inter-spike interval needs events, which a Gaussian neuron does not have"
+                             % (what, int(bad[0])))
+
+    def isi_histogram(self, data=0, bins=64, gpu=None):
+        """the inter-spike-interval statistics of data set `data` -> (hist (N, bins), moments (N, 3)), int64 (simulate.isi_host states them: a
+        bin with a positive count is one event).  gpu as for simulate(); on the device they come from one pgl_isi_fold call."""
+        from . import simulate as _sim
+        D = _sim.check_isi_bins(bins)
+        if D < 2:
+            raise ValueError("isi_histogram(): bins >= 2 is required")
+        self._refuse_gaussian_intervals("isi_histogram()")
+        Y = np.asarray(self.data_list[data][1], dtype=np.float64)
+        if self._engine_factory is not None:               # as simulate(): such a model stays on the host
+            gpu = False
+        if gpu is None or gpu:
+            import torch
+            if not torch.cuda.is_available():
+                if gpu:
+                    raise _sim.PglError("isi_histogram(gpu=True) needs a ROCm GPU (torch.cuda.is_available() is False)")
+                gpu = False
+        return _sim.isi_device(Y, D, device=self._device) if gpu or gpu is None else _sim.isi_host(Y, D)
 
     def cross_correlogram(self, data=0, lags=1, gpu=None):
         """the observed lagged cross-correlogram of data set `data`, (lags, N, N): c[l, i, j] says whether neuron i firing at t predicts neuron j
@@ -556,13 +591,17 @@ class NonlinearAutoregressiveModel(object):
         S = _sim.lagged_products_device(Y, K, device=self._device) if gpu or gpu is None else _sim.lagged_products_host(Y, K)
         return _sim.correlogram(S, Y.sum(axis=0), (Y * Y).sum(axis=0), Y.shape[0])
 
-    def predictive_check(self, replicates=8, seed=0, data=0, gpu=None, lags=0):
+    def predictive_check(self, replicates=8, seed=0, data=0, gpu=None, lags=0, isi=0):
         """a posterior predictive check of data set `data` bound to this model (simulate.PredictiveCheck): call its collect() after every
         sweep to be kept -- it simulates `replicates` fresh trajectories of the data set's length from the current state --, read
         rate_quantiles(q) / fano_quantiles(q) / pvalue("rate" | "fano") at the end.  lags = K > 0 adds the lagged cross-correlogram, the
-        statistic that sees the coupling: pvalue("xcorr"), xcorr_mean, xcorr_std, each (K, N, N).  Changes nothing in the chain."""
-        from .simulate import PredictiveCheck
-        return PredictiveCheck(self, replicates=replicates, seed=seed, data=data, gpu=gpu, lags=lags)
+        statistic that sees the coupling: pvalue("xcorr"), xcorr_mean, xcorr_std, each (K, N, N).  isi = D >= 2 adds the statistics of the
+        single train, which see refractoriness and bursting: pvalue("isi"), isi_mean, isi_std, each (N, D), and pvalue("cv"), cvs,
+        cv_quantiles(q); a Gaussian neuron is refused by name.  Changes nothing in the chain."""
+        from .simulate import PredictiveCheck, check_isi_bins
+        if check_isi_bins(isi):
+            self._refuse_gaussian_intervals("predictive_check(isi=%d)" % isi)
+        return PredictiveCheck(self, replicates=replicates, seed=seed, data=data, gpu=gpu, lags=lags, isi=isi)
 
     # ---- Gibbs
     def resample_model(self):

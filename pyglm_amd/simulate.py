@@ -141,6 +141,7 @@ HOST_BLOCK_BINS = 4096          # bins the host path keeps in its rolling buffer
 PGL_LAG_MAX = 256               # lags of the cross-correlogram at most (include/pyglm_hip.h)
 LAG_I8, LAG_F64 = 0, 1          # modes of pgl_lagged_products: the counts on the int8 matrix cores (exact), any real Y through the fp64 contraction
 LAG_REDOS = 0                   # folds of simulate_device that the int8 mode refused (a count beyond 127) and the fp64 mode redid, since import
+PGL_ISI_MAX_BINS = 256          # bins of the inter-spike-interval histogram at most (include/pyglm_hip.h)
 
 _M32 = np.uint64(0xFFFFFFFF)
 
@@ -268,12 +269,33 @@ class Simulation(object):
     bins, added in time order; history (R, L, N), the last L bins of every replicate in time order; t0 / t1, the first bin simulated and the
     first bin not simulated; seed and first_replicate.  Passed as `history=` of the next call it continues the same trajectories.
     With lags = K > 0: lagged (R, K, N, N), the lagged products of the T bins of this call (lagged_products_host states them; a device tensor
-    if the caller asked for that), and lag_redos, the folds that the int8 kernel refused and the fp64 one redid."""
+    if the caller asked for that), and lag_redos, the folds that the int8 kernel refused and the fp64 one redid.
+    With isi = D > 0: isi (R, N, D) and isi_moments (R, N, 3), int64, the inter-spike-interval histogram and (M, sum d, sum d^2) of every
+    replicate (isi_host states them) over the events of the T bins of THIS call only: a call that continues a `history=` does not count the
+    interval from the history's last event to its own first one."""
 
-    def __init__(self, Y, sum, sumsq, history, t0, t1, seed, first_replicate, lagged=None, lag_redos=0):
+    def __init__(self, Y, sum, sumsq, history, t0, t1, seed, first_replicate, lagged=None, lag_redos=0, isi=None, isi_moments=None):
         self.Y, self.sum, self.sumsq, self.history = Y, sum, sumsq, history
         self.t0, self.t1, self.seed, self.first_replicate = int(t0), int(t1), int(seed), int(first_replicate)
         self.lagged, self.lag_redos = lagged, int(lag_redos)
+        self.isi, self.isi_moments = isi, isi_moments
+
+    def _isi(self):
+        if self.isi is None:
+            raise ValueError("the interval statistics need simulate(..., isi=D) with D >= 2")
+        return self.isi, self.isi_moments
+
+    def isi_density(self):
+        """the interval histogram over the number of intervals, (R, N, D); NaN where a train has no interval"""
+        return isi_density(*self._isi())
+
+    def isi_mean(self):
+        """mean interval in bins, (R, N); NaN where a train has no interval"""
+        return isi_mean(self._isi()[1])
+
+    def isi_cv(self):
+        """coefficient of variation of the intervals, (R, N); NaN where a train has fewer than two"""
+        return isi_cv(self._isi()[1])
 
     def correlogram(self):
         """the lagged cross-correlogram of every replicate, (R, K, N, N): correlogram() of `lagged`"""
@@ -302,6 +324,113 @@ def fano_factor(s, ss, T):
     var = np.asarray(ss, dtype=np.float64) / T - mean * mean
     with np.errstate(divide="ignore", invalid="ignore"):
         return np.where(mean != 0.0, var / mean, np.nan)
+
+
+def check_isi_bins(bins):
+    """D = int(bins) of an inter-spike-interval histogram: 0 (none), or 2 <= D <= PGL_ISI_MAX_BINS, else ValueError"""
+    D = int(bins)
+    if D != 0 and not 2 <= D <= PGL_ISI_MAX_BINS:
+        raise ValueError("isi = %d: 0, or 2 <= isi <= PGL_ISI_MAX_BINS = %d bins, is required" % (D, PGL_ISI_MAX_BINS))
+    return D
+
+
+def isi_host(Y, bins):
+    """THE DEFINITION of the inter-spike-interval statistics of a series Y (T, N) -> (hist (N, D), moments (N, 3)), int64.  An event of neuron
+    n is a bin with Y[t, n] > 0 (a count above 1 is one event; NaN and negative values are none); an interval is the difference of the bin
+    indices of two consecutive events of a neuron -- the time before its first and after its last event is censored.  hist[n, d - 1] counts
+    the intervals of length d < D, hist[n, D - 1] those of length >= D; moments[n] = (M, sum d, sum d^2) over all of them, unclipped"""
+    Y = np.asarray(Y, dtype=np.float64)
+    D = check_isi_bins(bins)
+    if D == 0 or Y.ndim != 2:
+        raise ValueError("isi_host(): a series (T, N) and 2 <= bins <= %d are required" % PGL_ISI_MAX_BINS)
+    N = Y.shape[1]
+    hist, moments = np.zeros((N, D), dtype=np.int64), np.zeros((N, 3), dtype=np.int64)
+    for n in range(N):
+        d = np.diff(np.flatnonzero(Y[:, n] > 0)).astype(np.int64)
+        hist[n] = np.bincount(np.minimum(d, D) - 1, minlength=D)
+        moments[n] = d.size, d.sum(), (d * d).sum()
+    return hist, moments
+
+
+def _isi_fold_host(hist, moments, since, block):
+    """the running statistics hist (R, N, D), moments (R, N, 3), since (R, N) += the new rows block (R, rows, N).  since: bins from the train's
+    last event to the end of the rows folded so far, -1 before its first event: the first event of the block, at row u, closes an interval of
+    u + 1 + since bins"""
+    R, rows, N = block.shape
+    D = hist.shape[2]
+    for r in range(R):
+        for n in range(N):
+            ev = np.flatnonzero(block[r, :, n] > 0).astype(np.int64)
+            if ev.size == 0:
+                if since[r, n] >= 0:
+                    since[r, n] += rows
+                continue
+            d = np.diff(ev)
+            if since[r, n] >= 0:
+                d = np.concatenate(([ev[0] + 1 + since[r, n]], d))
+            hist[r, n] += np.bincount(np.minimum(d, D) - 1, minlength=D)
+            moments[r, n] += (d.size, d.sum(), (d * d).sum())
+            since[r, n] = rows - 1 - ev[-1]
+
+
+def isi_density(hist, moments):
+    """hist / M; NaN where M = 0"""
+    M = np.asarray(moments)[..., 0:1].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(M > 0, np.asarray(hist, dtype=np.float64) / M, np.nan)
+
+
+def isi_mean(moments):
+    m = np.asarray(moments, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(m[..., 0] > 0, m[..., 1] / m[..., 0], np.nan)
+
+
+def isi_cv(moments):
+    """sqrt(sum d^2 / M - mean^2) / mean; NaN where M < 2"""
+    m = np.asarray(moments, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = m[..., 1] / m[..., 0]
+        return np.where(m[..., 0] > 1, np.sqrt(np.maximum(m[..., 2] / m[..., 0] - mean * mean, 0.0)) / mean, np.nan)
+
+
+class _IsiFold(object):
+    """the running interval statistics on the device: hist (R, N, D) int32, moments (R, N, 3) int64, since (R, N) int32, folded chunk by chunk
+    through pgl_isi_fold"""
+
+    def __init__(self, dev, st, N, D, R, max_rows):
+        import torch
+        self.st, self.N, self.D, self.R = st, N, D, R
+        self.hist = torch.empty((R, N, D), dtype=torch.int32, device=dev)
+        self.moments = torch.empty((R, N, 3), dtype=torch.int64, device=dev)
+        self.since = torch.empty((R, N), dtype=torch.int32, device=dev)
+        self.work = torch.empty(_lib.load().pgl_isi_work_bytes(N, R, max_rows), dtype=torch.uint8, device=dev)
+        self.first = True
+
+    def fold(self, Y, ldy, strideY, rows):
+        """Y: the tensor that starts at the first new row of replicate 0"""
+        call("pgl_isi_fold", ptr(Y), ldy, strideY, rows, self.N, self.R, self.D, ptr(self.hist), ptr(self.moments), ptr(self.since),
+             0 if self.first else 1, ptr(self.work), self.st)
+        self.first = False
+
+    def finish(self):
+        return self.hist.cpu().numpy().astype(np.int64), self.moments.cpu().numpy()
+
+
+def isi_device(Y, bins, device=None):
+    """isi_host(Y, bins) of Y (T, N) through one pgl_isi_fold call"""
+    import torch
+    dev, st = _device("isi_histogram", device)
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    D = check_isi_bins(bins)
+    if D == 0 or Y.ndim != 2:
+        raise ValueError("isi_device(): a series (T, N) and 2 <= bins <= %d are required" % PGL_ISI_MAX_BINS)
+    T, N = Y.shape
+    with torch.cuda.device(dev):
+        fold = _IsiFold(dev, st, N, D, 1, T)
+        fold.fold(torch.from_numpy(Y).to(dev), N, T * N, T)
+        hist, moments = fold.finish()
+    return hist[0], moments[0]
 
 
 def check_lags(lags, T):
@@ -447,9 +576,10 @@ def _raise_cap(t, rep, n):
                    "explodes at this state (the rate grows without bound)" % (n, rep, t, NEGBIN_CAP))
 
 
-def simulate_host(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_paths, lags=0):
+def simulate_host(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_paths, lags=0, isi=0):
     """THE LAW in NumPy, vectorised over (R, N) per bin -> Simulation.  lags = K > 0: the lagged products of the T bins as well, folded block by
-    block from the rolling buffer, which then keeps max(L, K - 1) rows in front"""
+    block from the rolling buffer, which then keeps max(L, K - 1) rows in front.  isi = D > 0: the interval statistics, folded from the same
+    blocks with the `since` carry"""
     Wm = np.ascontiguousarray(Wm, dtype=np.float64)
     N = Wm.shape[0]
     L, B = basis.shape
@@ -462,12 +592,16 @@ def simulate_host(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_p
     buf[:, H - L:H] = hist
     s, ss = np.zeros((R, N)), np.zeros((R, N))
     S = np.zeros((R, K, N, N)) if K else None
+    D = int(isi)
+    ih, im, since = (np.zeros((R, N, D), dtype=np.int64), np.zeros((R, N, 3), dtype=np.int64), np.full((R, N), -1, dtype=np.int64)) if D else (None,) * 3
     neurons, reps = np.arange(N), rep0 + np.arange(R)
     pos = H                                          # buf[:, pos] receives bin t
     for t in range(t0, t0 + T):
         if pos == H + C:
             if K:
                 _fold_host(S, buf, H, pos, min(K - 1, t - t0 - C))
+            if D:
+                _isi_fold_host(ih, im, since, buf[:, H:pos])
             buf[:, :H] = buf[:, C:].copy()
             pos = H
         x = np.einsum("rlm,lb->rmb", buf[:, pos - L:pos][:, ::-1], basis)
@@ -482,19 +616,23 @@ def simulate_host(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_p
         pos += 1
     if K:
         _fold_host(S, buf, H, pos, min(K - 1, T - (pos - H)))
-    return Simulation(buf[:, H:H + T].copy() if keep_paths else None, s, ss, buf[:, pos - L:pos].copy(), t0, t0 + T, seed, rep0, lagged=S)
+    if D:
+        _isi_fold_host(ih, im, since, buf[:, H:pos])
+    return Simulation(buf[:, H:H + T].copy() if keep_paths else None, s, ss, buf[:, pos - L:pos].copy(), t0, t0 + T, seed, rep0, lagged=S,
+                      isi=ih, isi_moments=im)
 
 
-def simulate_device(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_paths, device=None, lags=0, lagged_on_device=False):
+def simulate_device(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_paths, device=None, lags=0, lagged_on_device=False, isi=0):
     """THE LAW through pgl_simulate, a chunk of bins per launch -> Simulation.  lags = K > 0: every launch writes its bins behind the K - 1 bins
     before them -- into the paths if they are kept, else into a buffer of K - 1 + chunk rows per replicate -- and pgl_lagged_products folds
-    them into the running sums (_LagFold); the sums come back as a device tensor if lagged_on_device"""
+    them into the running sums (_LagFold); the sums come back as a device tensor if lagged_on_device.  isi = D > 0: pgl_isi_fold folds the rows
+    of every launch as well (_IsiFold) -- from the paths, else from the lag buffer, else from a buffer of one chunk kept for this alone"""
     import torch
     dev, st = _device("simulate", device)
     N = np.shape(Wm)[0]
     L, B = np.shape(basis)
     Tc = chunk_bins(N, B, R)
-    K = int(lags)
+    K, D = int(lags), int(isi)
     with torch.cuda.device(dev):
         f64 = dict(dtype=torch.float64, device=dev)
         if K:
@@ -521,16 +659,21 @@ def simulate_device(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep
         Y_d = torch.empty((R, T, N), **f64) if keep_paths else None
         fold = _LagFold(dev, st, N, K, R, min(Tc, T), kind) if K else None
         buf = torch.empty((R, Tb, N), **f64) if K and not keep_paths else None
+        ifold = _IsiFold(dev, st, N, D, R, min(Tc, T)) if D else None
+        ibuf = torch.empty((R, min(Tc, T), N), **f64) if D and not K and not keep_paths else None
         sum_d, sq_d = torch.zeros((R, N), **f64), torch.zeros((R, N), **f64)
         work = torch.zeros(_lib.load().pgl_simulate_work_bytes(N, B, R), dtype=torch.uint8, device=dev)
         status = torch.zeros(4, dtype=torch.int32, device=dev)
         status_h = torch.zeros(4, dtype=torch.int32).pin_memory()
         for k0 in range(0, T, Tc):
             n = min(Tc, T - k0)
-            out, ldr = (Y_d[0, k0:], T * N) if keep_paths else (buf[0, K - 1:], Tb * N) if K else (None, T * N)
+            out, ldr = ((Y_d[0, k0:], T * N) if keep_paths else (buf[0, K - 1:], Tb * N) if K else (ibuf, min(Tc, T) * N) if D
+                        else (None, T * N))
             call("pgl_simulate", ptr(Wm_d), ptr(bias_d), ptr(basis_d), N, B, L, ptr(kind_d), ptr(par_d), R, rep0, seed & (2 ** 64 - 1), ptr(ring),
                  ptr(out), ldr, ptr(sum_d), ptr(sq_d), t0 + k0, n, ptr(work), ptr(status), st)
             _finish_launch("pgl_simulate", dev, status, status_h, t0 + k0, t0 + k0 + n - 1)
+            if D:
+                ifold.fold(out, N, ldr, n)
             if K:
                 fold.fold(out, ldr, n, min(K - 1, k0))
                 if not keep_paths and K > 1 and k0 + n < T:
@@ -539,15 +682,18 @@ def simulate_device(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep
         lagged = fold.finish() if K else None
         if K and not lagged_on_device:
             lagged = lagged.cpu().numpy()
+        ih, im = ifold.finish() if D else (None, None)
         return Simulation(Y_d.cpu().numpy() if keep_paths else None, sum_d.cpu().numpy(), sq_d.cpu().numpy(), ring.cpu().numpy()[:, rows],
-                          t0, t0 + T, seed, rep0, lagged=lagged, lag_redos=fold.redos if K else 0)
+                          t0, t0 + T, seed, rep0, lagged=lagged, lag_redos=fold.redos if K else 0, isi=ih, isi_moments=im)
 
 
 def simulate(Wm, bias, basis, kind, par, T, replicates=1, seed=0, first_replicate=0, history=None, keep_paths=True, t0=None, on_device=False,
-             device=None, lags=0, lagged_on_device=False):
+             device=None, lags=0, lagged_on_device=False, isi=0):
     """R = `replicates` trajectories of T bins of the model (Wm = a*W as (N, N*B), bias, basis (L, B), per-neuron kind / par) -> Simulation;
     on the device (pgl_simulate) or in NumPy.  What model.simulate() calls once it has read the model.  lags = K > 0 (K - 1 < T): the
-    Simulation carries the lagged products of its T bins (lagged_products_host) as well; lagged_on_device leaves them on the device."""
+    Simulation carries the lagged products of its T bins (lagged_products_host) as well; lagged_on_device leaves them on the device.
+    isi = D >= 2: it carries the interval histogram and moments of its T bins (isi_host) -- of the events of these bins alone, also when the
+    call continues a history."""
     N = np.shape(Wm)[0]
     L = basis.shape[0]
     T, R, rep0, seed = int(T), int(replicates), int(first_replicate), int(seed)
@@ -558,12 +704,16 @@ def simulate(Wm, bias, basis, kind, par, T, replicates=1, seed=0, first_replicat
         raise ValueError("simulate(): time bins and replicate indices must stay below 2^31")
     kind, par = np.asarray(kind, dtype=np.int32), np.asarray(par, dtype=np.float64)
     K = check_lags(lags, T)
+    D = check_isi_bins(isi)
     if T == 0:
-        return Simulation(np.zeros((R, 0, N)) if keep_paths else None, np.zeros((R, N)), np.zeros((R, N)), hist, t0, t0, seed, rep0)
+        return Simulation(np.zeros((R, 0, N)) if keep_paths else None, np.zeros((R, N)), np.zeros((R, N)), hist, t0, t0, seed, rep0,
+                          isi=np.zeros((R, N, D), dtype=np.int64) if D else None, isi_moments=np.zeros((R, N, 3), dtype=np.int64) if D else None)
     run = simulate_device if on_device else simulate_host
     kw = dict(device=device) if on_device else {}
     if K:
         kw.update(dict(lags=K, lagged_on_device=lagged_on_device) if on_device else dict(lags=K))
+    if D:
+        kw["isi"] = D
     return run(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_paths, **kw)
 
 
@@ -584,28 +734,87 @@ class PredictiveCheck(object):
     lags = K > 0 adds the pairwise statistic "xcorr", the lagged cross-correlogram (K, N, N) -- the one that sees the coupling: observed["xcorr"]
     is the data's (model.cross_correlogram), and collect() folds every replicate's correlogram, cell by cell, into #{rep >= obs}, #{rep <= obs},
     the number of replicates in which the cell is defined, and a Welford mean and M2 -- where the simulation ran (torch on the device, else
-    NumPy); the replicated correlograms themselves are never stacked.  pvalue("xcorr"), xcorr_mean and xcorr_std read them."""
+    NumPy); the replicated correlograms themselves are never stacked.  pvalue("xcorr"), xcorr_mean and xcorr_std read them.
 
-    def __init__(self, model, replicates=8, seed=0, data=0, gpu=None, lags=0):
+    isi = D >= 2 adds the statistics of the single spike train, the ones that see refractoriness and bursting: "isi", the inter-spike-interval
+    density (N, D) (isi_host; the last bin holds the intervals of D bins or more), and "cv", the coefficient of variation of the intervals
+    (N,).  observed["isi"] and observed["cv"] are the data's (model.isi_histogram); collect() keeps the cv per replicate, as the Fano factor,
+    and streams the density per cell by the rule of the correlogram, on the host ((N, D) is small).  pvalue("isi"), pvalue("cv"), isi_mean,
+    isi_std, cvs and cv_quantiles(q) read them."""
+
+    def __init__(self, model, replicates=8, seed=0, data=0, gpu=None, lags=0, isi=0):
         self.model, self.R, self.seed, self.gpu = model, int(replicates), int(seed), gpu
+        self.D = check_isi_bins(isi)
         Y = np.asarray(model.data_list[data][1], dtype=np.float64)
         self.T = Y.shape[0]
         self.K = check_lags(lags, self.T)
         self.observed = {"rate": Y.mean(axis=0), "fano": fano_factor(Y.sum(axis=0), (Y * Y).sum(axis=0), self.T)}
         if self.K:
             self.observed["xcorr"] = model.cross_correlogram(data=data, lags=self.K, gpu=gpu)
+        if self.D:
+            hist, moments = model.isi_histogram(data=data, bins=self.D, gpu=gpu)
+            self.observed["isi"], self.observed["cv"] = isi_density(hist, moments), isi_cv(moments)
         self.calls = 0
-        self._rate, self._fano = [], []
+        self._rate, self._fano, self._cv = [], [], []
+        self._isi = None                         # [ge, le, n, mean, M2], each (N, D), NumPy
         self._xc = None                          # [obs, ge, le, n, mean, M2], each (K, N, N), on the device of the simulations or in NumPy
 
     def collect(self):
         sim = self.model.simulate(self.T, replicates=self.R, seed=self.seed, first_replicate=self.calls * self.R, keep_paths=False, gpu=self.gpu,
-                                  lags=self.K, lagged_on_device=True)
+                                  lags=self.K, lagged_on_device=True, isi=self.D)
         self.calls += 1
         self._rate.append(sim.rate())
         self._fano.append(sim.fano())
         if self.K:
             self._collect_xcorr(sim)
+        if self.D:
+            self._cv.append(sim.isi_cv())
+            self._collect_isi(sim)
+
+    def _collect_isi(self, sim):
+        obs = self.observed["isi"]
+        if self._isi is None:
+            self._isi = [np.zeros(obs.shape, dtype=np.int64) for _ in range(3)] + [np.zeros(obs.shape) for _ in range(2)]
+        ge, le, n, mean, M2 = self._isi
+        dens = sim.isi_density()
+        with np.errstate(invalid="ignore"):
+            for r in range(dens.shape[0]):       # the rule of _collect_xcorr: one replicate at a time, Welford's order
+                c = dens[r]
+                ok = ~np.isnan(c)
+                ge += ok & (c >= obs)
+                le += ok & (c <= obs)
+                n += ok
+                d = np.where(ok, c - mean, 0.0)
+                mean += d / np.maximum(n, 1)
+                M2 += d * np.where(ok, c - mean, 0.0)
+
+    def _isi_state(self):
+        if not self.D or self._isi is None:
+            raise ValueError("the interval statistics need predictive_check(isi=D) with D >= 2 and at least one collect()")
+        return self._isi
+
+    @property
+    def isi_mean(self):
+        """mean of the replicated interval density over the replicates in which it is defined, (N, D); NaN where it never is"""
+        _, _, n, mean, _ = self._isi_state()
+        return np.where(n > 0, mean, np.nan)
+
+    @property
+    def isi_std(self):
+        """its standard deviation (n - 1 in the denominator); NaN with fewer than two defined replicates"""
+        _, _, n, _, M2 = self._isi_state()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(n > 1, np.sqrt(M2 / (n - 1.0)), np.nan)
+
+    @property
+    def cvs(self):
+        """(S R, N)"""
+        self._isi_state()
+        return np.concatenate(self._cv, axis=0)
+
+    def cv_quantiles(self, q):
+        """quantiles over the replicates whose coefficient of variation is defined (at least two intervals)"""
+        return np.nanquantile(self.cvs, q, axis=0)
 
     def _collect_xcorr(self, sim):
         S = sim.lagged
@@ -676,9 +885,13 @@ class PredictiveCheck(object):
             obs, ge, le, M, _, _ = self._xcorr_state()
             p = np.minimum(1.0, 2.0 * np.minimum(1 + ge, 1 + le) / (M + 1.0))
             return np.where(np.isnan(obs), np.nan, p)
-        if stat not in ("rate", "fano"):
-            raise ValueError("pvalue(): stat is 'rate', 'fano' or 'xcorr'")
-        rep = self.rates if stat == "rate" else self.fanos
+        if stat == "isi":                        # and per cell (N, D)
+            ge, le, M, _, _ = self._isi_state()
+            p = np.minimum(1.0, 2.0 * np.minimum(1 + ge, 1 + le) / (M + 1.0))
+            return np.where(np.isnan(self.observed["isi"]), np.nan, p)
+        if stat not in ("rate", "fano", "cv"):
+            raise ValueError("pvalue(): stat is 'rate', 'fano', 'xcorr', 'isi' or 'cv'")
+        rep = self.rates if stat == "rate" else self.fanos if stat == "fano" else self.cvs
         obs = self.observed[stat]
         ok = ~np.isnan(rep)
         M = ok.sum(axis=0)
