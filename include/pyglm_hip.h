@@ -439,6 +439,30 @@ size_t pgl_isi_work_bytes(int N, int R, int rows);
 int pgl_isi_fold(const double* Y, long ldy, long strideY, int rows, int N, int R, int D, int* hist, long long* moments, int* since, int accumulate,
                  void* work, void* hip_stream);
 
+/* ---- time-rescaling goodness of fit (pgl_rescale.hip): the recorded data against the fitted rates ---------------------------------------- */
+/* This project's own statistic; it replaces no reference call site.  For local column n, psi[t] = Psi[t * ldn + n] + bias[n] (bias NULL: 0),
+ * y[t] = Y[t * ldn + n], q[t] = par * log1p(exp(psi[t])) with par = qpar[n] (qpar NULL: qpar0) -- 1 Bernoulli, xi negative binomial, n
+ * binomial: -log P(y[t] = 0).  An event is a row with y > 0 (NaN and negative values are none).  For consecutive events at rows s < e
+ *   xi = sum_{s < t < e} q[t] + delta,  delta = -log1p(-r * (-expm1(-q[e]))),  z = -expm1(-xi),
+ * r the first uniform (words 0, 1) of Philox call `draw` of purpose 3, stream neuron0 + n, element elem0 + e.  The stretches in front of a
+ * column's first event and behind its last are dropped.
+ *   hist[n][min(D - 1, (int)(z D))] (+)= 1,   zsum[n] (+)= (sum z, sum z^2);   2 <= D <= PGL_RESCALE_MAX_BINS
+ * accumulate = 0: hist and zsum start from zero, whatever they hold; 1: a further data set of the same sample is added (no interval crosses
+ * data sets).  T = 0 is allowed and launches nothing.  Parallel in time: a workgroup owns pgl_rescale_segment_rows() rows of 64 columns; a
+ * second launch stitches the segments' records in work (pgl_rescale_work_bytes(nloc, T) bytes, 8-byte aligned).  No floating-point atomics:
+ * a column's result has the same bits whatever nloc, neuron0 or the shard.  A refused argument returns PGL_ERR_ARG (1) and writes nothing.
+ * pgl_rescale_ks, sample k (1-based): with M = sum_d hist[n][d] and C_d the count of bins 0 .. d - 1,
+ *   ks[n] = max_{d = 1 .. D - 1} |C_d D - d M| / (M D)  (the numerator in 64-bit integers; NaN where M = 0),
+ * a Welford step of ks into (ks_mean, ks_M2), exceed[n] += ks > coef / sqrt(M), hist_sum[n][d] += hist[n][d]. */
+#define PGL_RESCALE_MAX_BINS 256
+int pgl_rescale_segment_rows(void);
+size_t pgl_rescale_work_bytes(int nloc, int T);
+int pgl_rescale_fold(const double* Psi, long ldn, const double* bias, const double* Y, int T, int nloc, const double* qpar, double qpar0, int D,
+                     uint64_t seed, uint32_t draw, uint64_t neuron0, uint64_t elem0, int* hist, double* zsum, int accumulate, void* work,
+                     void* hip_stream);
+int pgl_rescale_ks(const int* hist, int nloc, int D, double coef, double* ks, double* ks_mean, double* ks_M2, int* exceed, long long* hist_sum, int k,
+                   void* hip_stream);
+
 /* ---- box calibration (diagnostic; nothing on the sampling path calls it) ------------------------------------------------------- */
 /* What the matrix cores of the current device sustain right now: a register-only MFMA loop on every CU for ~`seconds` (a quarter of it
  * untimed first, so that clocks and the package power limiter settle), timed with HIP events on `stream`; WAITS for the stream.

@@ -109,6 +109,10 @@ SIGNATURES = {
     "pgl_isi_segment_rows": [],
     "pgl_isi_work_bytes": [c_i, c_i, c_i],
     "pgl_isi_fold": [c_p, c_l, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p],
+    "pgl_rescale_segment_rows": [],
+    "pgl_rescale_work_bytes": [c_i, c_i],
+    "pgl_rescale_fold": [c_p, c_l, c_p, c_p, c_i, c_i, c_p, c_d, c_i, c_u64, c_u32, c_u64, c_u64, c_p, c_p, c_i, c_p, c_p],
+    "pgl_rescale_ks": [c_p, c_i, c_i, c_d, c_p, c_p, c_p, c_p, c_p, c_i, c_p],
 }
 
 ABI_VERSION = 11
@@ -134,7 +138,7 @@ def load():
     for name, args in SIGNATURES.items():
         fn = getattr(lib, name)     # AttributeError if the export is missing
         fn.argtypes = args
-        fn.restype = (ctypes.c_char_p if name in ("pgl_last_error", "pgl_stage_name") else ctypes.c_size_t if name in ("pgl_i8_plane_bytes", "pgl_i8_residue_bytes", "pgl_generate_work_bytes", "pgl_simulate_work_bytes", "pgl_lagged_work_bytes", "pgl_isi_work_bytes")
+        fn.restype = (ctypes.c_char_p if name in ("pgl_last_error", "pgl_stage_name") else ctypes.c_size_t if name in ("pgl_i8_plane_bytes", "pgl_i8_residue_bytes", "pgl_generate_work_bytes", "pgl_simulate_work_bytes", "pgl_lagged_work_bytes", "pgl_isi_work_bytes", "pgl_rescale_work_bytes")
                       else ctypes.c_double if name == "pgl_i8_norm_limit" else ctypes.c_int)
     if lib.pgl_abi_version() != ABI_VERSION:
         raise PglError("libpyglm_hip.so ABI version %d != %d (rebuild: make -C pyglm_amd/csrc)" % (lib.pgl_abi_version(), ABI_VERSION))

@@ -97,6 +97,11 @@ class _Summary(object):
     """device accumulators of one posterior summary (GibbsEngine.summary_alloc): rate / pw per data set, edge, w, b of the state"""
 
 
+class _Rescale(object):
+    """device accumulators of one time-rescaling test (GibbsEngine.rescale_alloc): hist / zsum / ks of the last sample, the running
+    ks_mean, ks_M2, exceed, hist_sum, and the fold's scratch"""
+
+
 class _I8Scratch(typing.NamedTuple):
     """the integer Gram's scratch (GibbsEngine._i8_reserve)"""
     bytes: int                           # held by the buffers below
@@ -753,6 +758,72 @@ class GibbsEngine(object):
             call("pgl_summary_colsum", ptr(V), self.ldn, ds.T, self.nloc, ptr(ds.llpart), ptr(out), int(i > 0), st)
             torch.cuda.current_stream(self.dev).synchronize()        # (V is released below; the launch must have read it)
         return out.cpu().numpy()
+
+    # ------------------------------------------------------------------ time-rescaling goodness of fit (pyglm_amd/rescale.py)
+    def rescale_bytes(self, bins):
+        """device bytes rescale_alloc takes: the segments' records of the longest data set, and per neuron the two histograms, (sum z, sum z^2),
+        the KS statistic with its moments, and the count of exceedances"""
+        T = max([ds.T for ds in self.datasets] or [0])
+        return _lib.load().pgl_rescale_work_bytes(self.nloc, T) + self.nloc * (12 * int(bins) + 16 + 24 + 4 + 8)
+
+    @_on_device
+    def rescale_alloc(self, bins, par, coef=1.36):
+        """zeroed accumulators of one time-rescaling test with `bins` bins for the data sets this engine holds now.  par: per local neuron
+        (or a scalar) the factor of log1p(exp(psi)) in -log P(y = 0 | psi) -- 1 Bernoulli, xi negative binomial, n binomial: taken from the
+        caller, not from the engine's observation model, so the hooks mode works.  coef: the band is coef / sqrt(M).  Checked against what
+        this engine may still take on its GPU (_free_bytes) BEFORE anything is allocated: MemoryError otherwise."""
+        D = int(bins)
+        need, free = self.rescale_bytes(D), self._free_bytes()
+        if need > free:
+            raise MemoryError("time rescaling: the accumulators need %d bytes, %d are free on %s" % (need, free, self.dev))
+        s = _Rescale()
+        s.D, s.coef, s.ndatasets = D, float(coef), len(self.datasets)
+        par = np.broadcast_to(np.asarray(par, dtype=np.float64).reshape(-1), (self.nloc,))
+        s.qpar0, s.qpar = float(par[0]), None
+        if np.any(par != par[0]):
+            s.qpar = torch.from_numpy(np.array(par)).to(self.dev)
+        s.hist = self._z(self.nloc, D, dtype=I32)
+        s.hist_sum = self._z(self.nloc, D, dtype=torch.int64)
+        s.zsum = self._z(self.nloc, 2)
+        s.ks, s.ks_mean, s.ks_M2 = self._z(self.nloc), self._z(self.nloc), self._z(self.nloc)
+        s.exceed = self._z(self.nloc, dtype=I32)
+        T = max([ds.T for ds in self.datasets] or [0])
+        s.work = torch.empty(_lib.load().pgl_rescale_work_bytes(self.nloc, T), dtype=torch.uint8, device=self.dev)
+        return s
+
+    @_on_device
+    def rescale_reset(self, s):
+        for t in (s.hist, s.hist_sum, s.zsum, s.ks, s.ks_mean, s.ks_M2, s.exceed):
+            t.zero_()
+
+    @_on_device
+    def rescale_fold(self, s, a, W, b, k, seed, only=None):
+        """sample k (1-based) of the state (a, W, b) into the accumulators s: one upload of the weights, per data set ONE activation and ONE
+        pgl_rescale_fold (Philox call k - 1 of `seed`; the data sets behind the first add to the sample's histogram), then pgl_rescale_ks.
+        only = i: data set i alone."""
+        if len(self.datasets) != s.ndatasets:
+            raise RuntimeError("data was added after the time-rescaling test was allocated: its scratch covers %d data sets, the engine "
+                               "holds %d (build a new one)" % (s.ndatasets, len(self.datasets)))
+        self._upload_weights(a, W, b)
+        st = self._st()
+        more = 0
+        for i, ds in enumerate(self.datasets):
+            if only is not None and i != only:
+                continue
+            self._activation(ds, st)
+            h = self._tic("rescale_fold", float(ds.T) * self.nloc)
+            call("pgl_rescale_fold", ptr(ds.Psi), self.ldn, ptr(self.bias), ptr(ds.Y), ds.T, self.nloc, ptr(s.qpar), s.qpar0, s.D,
+                 int(seed) & (2 ** 64 - 1), (int(k) - 1) & 0xFFFFFFFF, self.n0, ds.elem0, ptr(s.hist), ptr(s.zsum), more, ptr(s.work), st)
+            self._toc(h)
+            more = 1
+        call("pgl_rescale_ks", ptr(s.hist), self.nloc, s.D, s.coef, ptr(s.ks), ptr(s.ks_mean), ptr(s.ks_M2), ptr(s.exceed), ptr(s.hist_sum), int(k), st)
+
+    @_on_device
+    def rescale_read(self, s):
+        """-> host dict: hist (nloc, D) and zsum (nloc, 2) of the last sample, ks of it, ks_mean, ks_M2, exceed over the samples, hist_sum"""
+        host = lambda t: t.cpu().numpy()
+        return dict(hist=host(s.hist).astype(np.int64), zsum=host(s.zsum), ks=host(s.ks), ks_mean=host(s.ks_mean), ks_M2=host(s.ks_M2),
+                    exceed=host(s.exceed).astype(np.int64), hist_sum=host(s.hist_sum))
 
     # ------------------------------------------------------------------ one Gibbs sweep of the shard's regressions
     def _sweep_args(self, ovs=None):

@@ -603,6 +603,45 @@ class NonlinearAutoregressiveModel(object):
             self._refuse_gaussian_intervals("predictive_check(isi=%d)" % isi)
         return PredictiveCheck(self, replicates=replicates, seed=seed, data=data, gpu=gpu, lags=lags, isi=isi)
 
+    def time_rescaling(self, bins=64, seed=0, coef=1.36, datas=None):
+        """the time-rescaling goodness-of-fit test of the data under this model's chain (pyglm_amd/rescale.py: TimeRescaling): call its
+        collect() after every sweep to be kept -- it reads the recorded data against the current rates, no replicate is simulated --, read
+        ks_mean / band / exceed_fraction / failing() at the end.  bins: of the histogram of the rescaled z per neuron, whose binned
+        Kolmogorov-Smirnov distance from the uniform law is the statistic; coef / sqrt(M) is the band (1.36: 95 %).  datas: as for
+        summarize -- None: the stored data; a list: held-out recordings.  A Gaussian neuron is refused by name.  Changes nothing in the
+        chain."""
+        from .rescale import TimeRescaling
+        return TimeRescaling(self, bins=bins, seed=seed, coef=coef, datas=datas)
+
+    def rescaled_intervals(self, data=0, bins=64, seed=0, gpu=None):
+        """the rescaled intervals of data set `data` at the CURRENT state -> (hist (N, bins) int64, zsum (N, 2) = (sum z, sum z^2))
+        (rescale.rescale_host states them; Philox call 0 of `seed`).  gpu=None: through pgl_rescale_fold when there is a GPU, else the NumPy
+        path from engine.psi; True: the device or a PglError; False: NumPy.  A model with an engine_factory takes the NumPy path."""
+        from . import rescale as _rs
+        D = _rs.check_bins(bins)
+        par = _rs.interval_par(self.regressions)[self.n0:self.n1]
+        data = range(len(self.data_list))[data]
+        eng = self.engine
+        if self._engine_factory is not None or not hasattr(eng, "rescale_alloc"):
+            gpu = False
+        if gpu is None or gpu:
+            import torch
+            if not torch.cuda.is_available():
+                if gpu:
+                    raise _rs._sim.PglError("rescaled_intervals(gpu=True) needs a ROCm GPU (torch.cuda.is_available() is False)")
+                gpu = False
+        a, W, b = self._local_state()
+        if gpu or gpu is None:
+            buf = eng.rescale_alloc(D, par)
+            eng.rescale_fold(buf, a, W, b, 1, seed, only=data)
+            out = eng.rescale_read(buf)
+            hist, zsum = out["hist"], out["zsum"]
+        else:
+            Y = np.asarray(self.data_list[data][1], dtype=np.float64)[:, self.n0:self.n1]
+            elem0 = sum(d[1].shape[0] for d in self.data_list[:data])
+            hist, zsum, _ = _rs.rescale_host(np.asarray(eng.psi(a, W, b, data), dtype=np.float64), Y, par, D, seed, 0, self.n0, elem0)
+        return self._gather_rows(np.ascontiguousarray(hist)), self._gather_rows(np.ascontiguousarray(zsum))
+
     # ---- Gibbs
     def resample_model(self):
         self.resample_regressions()
