@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr
+from .regression import MODELS, OBS_NEGBIN, OBS_GAUSSIAN, OBS_BINOMIAL, OBS_HOOKS
 
 F64 = torch.float64
 I32 = torch.int32
@@ -119,7 +120,8 @@ class _I8Scratch(typing.NamedTuple):
 class GibbsEngine(object):
     # observation models (include/pyglm_hip.h, pgl_pg_loglik_ex): the built-in Bernoulli, negative-binomial, Gaussian and binomial regressions,
     # and "hooks" -- any other Polya-gamma model, its a(y), b(y), log c(y) evaluated on the host and kept next to the data (add_data obs_terms)
-    OBS = {"bernoulli": 0, "negbin": 1, "gaussian": 2, "binomial": 3, "hooks": 4}
+    OBS = dict([(m.name, m.device) for m in MODELS.values()] + [("hooks", OBS_HOOKS)])
+    _LINK = dict([(m.device, m.link) for m in MODELS.values()] + [(OBS_HOOKS, 0)])     # link0 of pgl_summary_fold (hooks: per neuron, summary_alloc)
 
     def __init__(self, N, B, n0=0, n1=None, device=None, obs="bernoulli", xi=1.0, batch=None, mem_budget_bytes=None,
                  design_only=False, visit_order=True, gram=None, likelihood_only=False, planes=None, i8_group=None, i8_slice=None,
@@ -211,9 +213,9 @@ class GibbsEngine(object):
             elif v.size != self.nloc:
                 raise ValueError("xi: %d values for a model of %d neurons (shard of %d)" % (v.size, self.N, self.nloc))
             vals, out = v, (1.0, torch.from_numpy(np.ascontiguousarray(v)).to(self.dev))
-        if self.obs == 1 and not np.all(vals > 0):
+        if self.obs == OBS_NEGBIN and not np.all(vals > 0):
             raise ValueError("negative binomial: xi must be > 0")
-        if self.obs == 3 and not np.all((vals >= 0) & (vals == np.floor(vals))):
+        if self.obs == OBS_BINOMIAL and not np.all((vals >= 0) & (vals == np.floor(vals))):
             raise ValueError("binomial: the number of trials n must be an integer >= 0")
         return out
 
@@ -311,7 +313,7 @@ class GibbsEngine(object):
         self.Wt = self._z(self.Dp, self.ldn)          # k-major weights for the activation contraction
         self.bias = self._z(nl)
         self.border = self._z(2 * self.ldn, self.Dp)
-        if self.obs == 2:
+        if self.obs == OBS_GAUSSIAN:
             # Gaussian observations: omega = 1/eta is constant in t, so X'X is formed once per dataset (add_data) and scaled per sweep
             self.G0 = self._z(self.ldj, self.ldj)
             self.inv_eta = torch.ones(nl, dtype=F64, device=self.dev)
@@ -369,7 +371,7 @@ class GibbsEngine(object):
         Y = np.ascontiguousarray(Y, dtype=np.float64)
         T = Y.shape[0]
         assert Y.shape == (T, self.N)
-        if (obs_terms is not None) != (self.obs == 4) and not self.design_only:
+        if (obs_terms is not None) != (self.obs == OBS_HOOKS) and not self.design_only:
             raise ValueError("obs_terms are the data of the hooks observation model: required with obs='hooks', and only there")
         if obs_terms is not None:
             terms = [np.broadcast_to(np.asarray(v, dtype=np.float64), (T, self.nloc)) for v in obs_terms]
@@ -436,7 +438,7 @@ class GibbsEngine(object):
                 call("pgl_i8_planes_t", ptr(ds.Xt), ds.Tp, None, 0, ptr(ds.sA), ptr(ds.PA), T, self.D, 1, ds.planes, 0, st)
             self._i8_reserve(T, plan)
             torch.cuda.synchronize(self.dev)
-        if self.obs == 2:
+        if self.obs == OBS_GAUSSIAN:
             ones = self._z(ds.Tp, 2)
             ones[:T, 0] = 1.0
             call("pgl_weighted_gram", ptr(ds.X), self.Dp, self.Dp, ptr(ones), 2, ds.Tp, self.D, 1, ptr(self.G0), self.ldj, self.ldj * self.ldj,
@@ -491,7 +493,7 @@ class GibbsEngine(object):
         a few tiles (_i8_rounds); if a whole data set's planes do not fit (BASELINE configs[4]: 86 GB of planes per neuron), the product
         runs in time slices that add up in the residues (pgl_sweep_t.i8_slice), and only if not even a short slice fits does the data set
         fall back to the fp64 kernel (with a warning)."""
-        if self.obs == 2 or self.design_only or self.likelihood_only or self.gram == "fp64":
+        if self.obs == OBS_GAUSSIAN or self.design_only or self.likelihood_only or self.gram == "fp64":
             return None
         if self.gram != "int8" and (T < self.I8_MIN_T or (self.D < self.I8_MIN_D and not self._i8_pays(T, self.planes or 13))):
             return None
@@ -594,7 +596,7 @@ class GibbsEngine(object):
     @_on_device
     def set_noise(self, eta):
         """noise variances eta (nloc,) of the Gaussian observation model (regression.py:380-398)"""
-        assert self.obs == 2
+        assert self.obs == OBS_GAUSSIAN
         self.eta = np.asarray(eta, dtype=np.float64).reshape(self.nloc).copy()
         self.inv_eta.copy_(torch.from_numpy(1.0 / self.eta))
 
@@ -627,7 +629,7 @@ class GibbsEngine(object):
             h = self._tic("pg_loglik", float(ds.T) * self.nloc)
             om = ds.OK if draw else None
             kp = ctypes.c_void_p(ds.OK.data_ptr() + 8 * self.ldn) if draw else None
-            if self.obs == 2:      # self.ll then holds the sums of squared residuals
+            if self.obs == OBS_GAUSSIAN:      # self.ll then holds the sums of squared residuals
                 call("pgl_gaussian_stats", ptr(ds.Psi), self.ldn, ptr(self.bias), ptr(ds.Y), self.ldn, ptr(self.inv_eta), ptr(om), 2 * self.ldn,
                      kp, 2 * self.ldn, ptr(ds.llpart), ptr(self.ll), int(i > 0), ds.T, self.nloc, st)
             else:
@@ -647,7 +649,7 @@ class GibbsEngine(object):
         return self._ll_host_np(ll_dev.cpu().numpy().copy())
 
     def _ll_host_np(self, ll):
-        if self.obs == 2:          # regression.py:399-403 summed over t: -T/2 log(2 pi eta) - sse / (2 eta)
+        if self.obs == OBS_GAUSSIAN:          # regression.py:399-403 summed over t: -T/2 log(2 pi eta) - sse / (2 eta)
             T = sum(ds.T for ds in self.datasets)
             ll = -0.5 * T * np.log(2 * np.pi * self.eta) - 0.5 * ll / self.eta
         return ll
@@ -655,7 +657,7 @@ class GibbsEngine(object):
     @_on_device
     def sse(self, a, W, b):
         """sum_t (y - mean)^2 per local neuron, the statistic of _resample_eta (regression.py:433-445)"""
-        assert self.obs == 2
+        assert self.obs == OBS_GAUSSIAN
         self._upload_weights(a, W, b)
         return self._psi_pass(False, 0, 0).cpu().numpy().copy()
 
@@ -685,8 +687,8 @@ class GibbsEngine(object):
             raise MemoryError("posterior summary: the accumulators need %d bytes, %d are free on %s" % (need, free, self.dev))
         s = _Summary()
         s.ndatasets = len(self.datasets)
-        s.link0, s.link_par0, s.link, s.link_par = {0: 0, 1: 2, 2: 1, 3: 3, 4: 0}[self.obs], float(self.xi), None, self.obs_param
-        if self.obs == 4:
+        s.link0, s.link_par0, s.link, s.link_par = self._LINK[self.obs], float(self.xi), None, self.obs_param
+        if self.obs == OBS_HOOKS:
             s.link_par = None
             if rates:
                 if link is None:
@@ -723,7 +725,7 @@ class GibbsEngine(object):
             h = self._tic("summary_fold", float(ds.T) * self.nloc)
             r, p = s.rate[i] if s.rate else none2, s.pw[i] if s.pw else none4
             call("pgl_summary_fold", ptr(ds.Psi), self.ldn, ptr(self.bias), ptr(ds.Y), ptr(ds.llpart), ptr(self.ll), int(i > 0), ds.T, self.nloc,
-                 self.obs, self.xi, ptr(self.obs_param), ptr(ds.hooks), self.ldn, ptr(self.inv_eta) if self.obs == 2 else None, ptr(r[0]), ptr(r[1]),
+                 self.obs, self.xi, ptr(self.obs_param), ptr(ds.hooks), self.ldn, ptr(self.inv_eta) if self.obs == OBS_GAUSSIAN else None, ptr(r[0]), ptr(r[1]),
                  ptr(s.link), s.link0, ptr(s.link_par), s.link_par0, ptr(p[0]), ptr(p[1]), ptr(p[2]), ptr(p[3]), int(k), st)
             self._toc(h)
         call("pgl_summary_state", ptr(s.a), ptr(self.Wt), self.ldn, ptr(self.bias), ptr(s.edge), ptr(s.w[0]), ptr(s.w[1]), ptr(s.b[0]), ptr(s.b[1]),
@@ -998,7 +1000,7 @@ class GibbsEngine(object):
         p = torch.zeros((nl, rb), dtype=torch.uint8, device=self.dev)
         p[:, :ob] = self.W_dev.view(torch.uint8).view(nl, ob)
         p[:, ob:oe] = self.b_dev.view(torch.uint8).view(nl, 8)
-        if self.obs != 2:
+        if self.obs != OBS_GAUSSIAN:
             # the slot of the Gaussian model's noise variance carries the sweep's status flags here (0 = fine): after the gather EVERY rank sees
             # every neuron's flag and raises the same LinAlgError in the same sweep, instead of one rank leaving the others at a collective
             p[:, oe:os_] = self.status.to(F64).view(torch.uint8).view(nl, 8)

@@ -16,7 +16,6 @@ import numpy.random as npr
 
 from . import networks as _networks
 from . import regression as _regression
-from .utils.utils import logistic
 
 
 def _dist():
@@ -404,35 +403,14 @@ class NonlinearAutoregressiveModel(object):
     def means(self):
         """(models.py:153-163) E[y | X] per dataset, (T, N): per neuron, from its own observation model"""
         a, W, b = self._local_state()
-        mode = self._engine_mode if self._engine is not None else _regression.device_obs(self.regressions)
-        obs, par = mode
+        obs, par = self._engine_mode if self._engine is not None else _regression.device_obs(self.regressions)
         regs = self.regressions[self.n0:self.n1]
-        par_loc = np.asarray(par, dtype=np.float64)
-        if par_loc.ndim:
-            par_loc = par_loc[self.n0:self.n1]
+        if np.ndim(par):
+            par = np.asarray(par, dtype=np.float64)[self.n0:self.n1]
         mus = []
         for i in range(len(self.data_list)):
             psi = self.engine.psi(a, W, b, i)
-            if obs == "bernoulli":
-                mu = logistic(psi)
-            elif obs == "gaussian":
-                mu = psi
-            elif obs == "negbin":
-                mu = (par if par_loc.ndim == 0 else par_loc) * np.exp(psi)
-            elif obs == "binomial":
-                mu = par_loc * logistic(psi)
-            else:
-                # hooks: each regression's own mean -- from psi where it is a built-in one, else its mean(X) on the data set's design matrix
-                mu = np.empty_like(psi)
-                Xi = None
-                for j, r in enumerate(regs):
-                    f = None if "mean" in vars(r) else _MEAN_OF_PSI.get(type(r).mean)
-                    if f is not None:
-                        mu[:, j] = f(r, psi[:, j])
-                    else:
-                        if Xi is None:
-                            Xi = np.asarray(self.data_list[i][0])
-                        mu[:, j] = r.mean(Xi)
+            mu = _regression.means_of_psi(regs, (obs, par), psi, X=lambda: np.asarray(self.data_list[i][0]))
             mus.append(self._gather_rows(np.ascontiguousarray(mu.T)).T)
         return mus
 
@@ -442,10 +420,9 @@ class NonlinearAutoregressiveModel(object):
         according to the values it draws; a user's override) keeps the host loop, and so does a model with an engine_factory"""
         if gpu is False:
             return None
-        from . import simulate
         reg = self.regressions[0]
-        kinds = {_regression.SparseBernoulliRegression.rvs: simulate.OBS_BERNOULLI, _regression.SparseGaussianRegression.rvs: simulate.OBS_GAUSSIAN}
-        obs = None if "rvs" in vars(reg) else kinds.get(type(reg).rvs)
+        model = _regression.builtin_model(reg, "rvs")
+        obs = None if model is None else model.generate
         if obs is None or self._engine_factory is not None:
             if gpu:
                 raise ValueError("generate(gpu=True): the device path simulates the built-in Bernoulli and Gaussian observations of a model "
@@ -522,35 +499,35 @@ class NonlinearAutoregressiveModel(object):
         the history's last event.  On the device pgl_isi_fold folds them after every launch.
         On a sharded model every rank holds the gathered state: each rank computes the same result on its own device, with no collective."""
         from . import simulate as _sim
-        from ._lib import PglError
         A, W, b = self._adopt_state()
         kind, par = _sim.observation_kinds(self.regressions)
         if _sim.check_isi_bins(isi):
             self._refuse_gaussian_intervals("simulate(isi=%d)" % isi)
-        if self._engine_factory is not None:
-            if gpu:
-                raise ValueError("simulate(gpu=True): a model with an engine_factory takes the NumPy path (gpu=None or False)")
-            gpu = False
-        if gpu is None or gpu:
-            import torch
-            if not torch.cuda.is_available():
-                if gpu:
-                    raise PglError("simulate(gpu=True) needs a ROCm GPU (torch.cuda.is_available() is False)")
-                gpu = False
-            else:
-                gpu = True
+        if self._engine_factory is not None and gpu:
+            raise ValueError("simulate(gpu=True): a model with an engine_factory takes the NumPy path (gpu=None or False)")
         Wm = (W * A[:, :, None]).reshape(self.N, self.N * self.B)
         return _sim.simulate(Wm, b.ravel(), np.asarray(self.basis, dtype=np.float64), kind, par, T, replicates=replicates, seed=seed,
-                             first_replicate=first_replicate, history=history, keep_paths=keep_paths, t0=t0, on_device=bool(gpu),
+                             first_replicate=first_replicate, history=history, keep_paths=keep_paths, t0=t0, on_device=self._on_gpu(gpu, "simulate"),
                              device=self._device, lags=lags, lagged_on_device=lagged_on_device, isi=isi)
 
     def _refuse_gaussian_intervals(self, what):
         from . import simulate as _sim
-        kind, _ = _sim.observation_kinds(self.regressions)
-        bad = np.flatnonzero(kind == _sim.KIND_GAUSSIAN)
-        if bad.size:
-            raise ValueError("%s: neuron %d is Gaussian; an inter-spike interval needs events, which a Gaussian neuron does not have"
-                             % (what, int(bad[0])))
+        bad = _sim.first_without_events(_sim.observation_models(self.regressions))
+        if bad is not None:
+            raise ValueError("%s: neuron %d is Gaussian; an inter-spike interval needs events, which a Gaussian neuron does not have" % (what, bad))
+
+    def _on_gpu(self, gpu, method, host_only=False):
+        """the tri-state gpu= of `method` -> bool.  A model with an engine_factory (or host_only) stays on the host; None: the GPU if there is
+        one; True: the GPU or a PglError"""
+        if self._engine_factory is not None or host_only or not (gpu is None or gpu):
+            return False
+        import torch
+        if not torch.cuda.is_available():
+            if gpu:
+                from ._lib import PglError
+                raise PglError("%s(gpu=True) needs a ROCm GPU (torch.cuda.is_available() is False)" % method)
+            return False
+        return True
 
     def isi_histogram(self, data=0, bins=64, gpu=None):
         """the inter-spike-interval statistics of data set `data` -> (hist (N, bins), moments (N, 3)), int64 (simulate.isi_host states them: a
@@ -561,15 +538,7 @@ class NonlinearAutoregressiveModel(object):
             raise ValueError("isi_histogram(): bins >= 2 is required")
         self._refuse_gaussian_intervals("isi_histogram()")
         Y = np.asarray(self.data_list[data][1], dtype=np.float64)
-        if self._engine_factory is not None:               # as simulate(): such a model stays on the host
-            gpu = False
-        if gpu is None or gpu:
-            import torch
-            if not torch.cuda.is_available():
-                if gpu:
-                    raise _sim.PglError("isi_histogram(gpu=True) needs a ROCm GPU (torch.cuda.is_available() is False)")
-                gpu = False
-        return _sim.isi_device(Y, D, device=self._device) if gpu or gpu is None else _sim.isi_host(Y, D)
+        return _sim.isi_device(Y, D, device=self._device) if self._on_gpu(gpu, "isi_histogram") else _sim.isi_host(Y, D)
 
     def cross_correlogram(self, data=0, lags=1, gpu=None):
         """the observed lagged cross-correlogram of data set `data`, (lags, N, N): c[l, i, j] says whether neuron i firing at t predicts neuron j
@@ -580,15 +549,7 @@ class NonlinearAutoregressiveModel(object):
         K = _sim.check_lags(lags, Y.shape[0])
         if K < 1:
             raise ValueError("cross_correlogram(): lags >= 1 is required")
-        if self._engine_factory is not None:               # as simulate(): such a model stays on the host
-            gpu = False
-        if gpu is None or gpu:
-            import torch
-            if not torch.cuda.is_available():
-                if gpu:
-                    raise _sim.PglError("cross_correlogram(gpu=True) needs a ROCm GPU (torch.cuda.is_available() is False)")
-                gpu = False
-        S = _sim.lagged_products_device(Y, K, device=self._device) if gpu or gpu is None else _sim.lagged_products_host(Y, K)
+        S = _sim.lagged_products_device(Y, K, device=self._device) if self._on_gpu(gpu, "cross_correlogram") else _sim.lagged_products_host(Y, K)
         return _sim.correlogram(S, Y.sum(axis=0), (Y * Y).sum(axis=0), Y.shape[0])
 
     def predictive_check(self, replicates=8, seed=0, data=0, gpu=None, lags=0, isi=0):
@@ -622,16 +583,8 @@ class NonlinearAutoregressiveModel(object):
         par = _rs.interval_par(self.regressions)[self.n0:self.n1]
         data = range(len(self.data_list))[data]
         eng = self.engine
-        if self._engine_factory is not None or not hasattr(eng, "rescale_alloc"):
-            gpu = False
-        if gpu is None or gpu:
-            import torch
-            if not torch.cuda.is_available():
-                if gpu:
-                    raise _rs._sim.PglError("rescaled_intervals(gpu=True) needs a ROCm GPU (torch.cuda.is_available() is False)")
-                gpu = False
         a, W, b = self._local_state()
-        if gpu or gpu is None:
+        if self._on_gpu(gpu, "rescaled_intervals", host_only=not hasattr(eng, "rescale_alloc")):
             buf = eng.rescale_alloc(D, par)
             eng.rescale_fold(buf, a, W, b, 1, seed, only=data)
             out = eng.rescale_read(buf)
@@ -799,17 +752,6 @@ class NonlinearAutoregressiveModel(object):
 
     def plot(self, *args, **kwargs):
         raise NotImplementedError("plotting is outside the scope of the MI355X hot path (SURVEY.md section 2, row 8)")
-
-
-# E[y | psi] of the built-in Polya-gamma regressions, for means() in hooks mode (a regression whose `mean` is one of these)
-_MEAN_OF_PSI = {_regression.SparseBernoulliRegression.mean: lambda r, psi: logistic(psi),
-                _regression.SparseNegativeBinomialRegression.mean: lambda r, psi: r.xi * np.exp(psi),
-                _regression.SparseBinomialRegression.mean: lambda r, psi: r.n * logistic(psi)}
-
-
-# the same models as link codes of pgl_summary_fold: (code, attribute that holds the link's parameter)
-_LINK_OF_MEAN = {_regression.SparseBernoulliRegression.mean: (0, None), _regression.SparseNegativeBinomialRegression.mean: (2, "xi"),
-                 _regression.SparseBinomialRegression.mean: (3, "n")}
 
 
 class _LazyX(object):

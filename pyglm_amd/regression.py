@@ -6,6 +6,7 @@ path runs on the GPU: a population model batches its regressions through `pyglm_
 stand-alone regression (examples/bernoulli_regression.py style) builds a one-neuron engine on demand.
 """
 import ctypes
+import typing
 
 import numpy as np
 import numpy.random as npr
@@ -462,36 +463,78 @@ class BinomialRegression(SparseBinomialRegression):
         super(BinomialRegression, self).__init__(N, B, **kwargs)
 
 
-# ---------------------------------------------------------------------------------------------------- the device's observation model
+# ---------------------------------------------------------------------------------------------------- the observation models
+class ObsModel(typing.NamedTuple):
+    """one built-in observation model: every fact the package dispatches on (the codes are those of include/pyglm_hip.h)"""
+    name: str
+    cls: type                           # the class that defines the model's a_func / b_func / c_func, rvs and mean
+    device: int                         # pgl_sweep_t.obs / pgl_pg_loglik_ex
+    sim_kind: int                       # kind[] of pgl_simulate
+    link: int                           # link code of pgl_summary_fold
+    generate: typing.Optional[int]      # obs of pgl_generate; None: generate() keeps the host loop
+    param: typing.Optional[str]         # attribute that holds the model's parameter
+    sim_par: typing.Callable            # regression -> par[] of pgl_simulate
+    mean: typing.Callable               # (psi, par) -> E[y | psi]
+    events: bool                        # -log P(y = 0 | psi) = par * log1p(exp(psi)); False: the model has no events
+
+    def par(self, reg):
+        """the model's parameter of `reg` (1 where it has none): of the device model, of `mean`, the factor of log1p(exp(psi))"""
+        return 1.0 if self.param is None else float(getattr(reg, self.param))
+
+
+MODELS = {m.name: m for m in (
+    ObsModel("bernoulli", SparseBernoulliRegression, 0, 0, 0, 0, None, lambda r: 0.0, lambda psi, par: logistic(psi), True),
+    ObsModel("negbin", SparseNegativeBinomialRegression, 1, 2, 2, None, "xi", lambda r: float(r.xi), lambda psi, par: par * np.exp(psi), True),
+    ObsModel("gaussian", SparseGaussianRegression, 2, 1, 1, 1, None, lambda r: np.sqrt(float(r.eta)), lambda psi, par: psi, False),
+    ObsModel("binomial", SparseBinomialRegression, 3, 3, 3, None, "n", lambda r: float(r.n), lambda psi, par: par * logistic(psi), True))}
+OBS_BERNOULLI, OBS_NEGBIN, OBS_GAUSSIAN, OBS_BINOMIAL = (MODELS[k].device for k in ("bernoulli", "negbin", "gaussian", "binomial"))
+OBS_HOOKS = 4                           # a mode of the engine, not a model: a(y), b(y), log c(y) evaluated on the host (obs_terms)
 _HOOKS = ("a_func", "b_func", "c_func")
-_BUILTIN = {"bernoulli": (SparseBernoulliRegression, None), "negbin": (SparseNegativeBinomialRegression, "xi"),
-            "binomial": (SparseBinomialRegression, "n")}
 _class_kind = {}
 
 
-def _kind(reg):
-    """"gaussian", a built-in PG model's name, or "hooks" for any other Polya-gamma regression; raises for a type the device cannot run"""
-    cls = type(reg)
+def _on_instance(reg, methods):
+    return not vars(reg).keys().isdisjoint(methods)
+
+
+def _in_class(cls, model, methods):
+    return all(hasattr(model.cls, m) and getattr(cls, m, None) is getattr(model.cls, m) for m in methods)
+
+
+def is_builtin(reg, model, *methods):
+    """are `methods` of `reg` the ones the built-in model's class defines: not overridden in reg's class (_in_class), not set on the
+    instance (_on_instance)?  _kind asks the two halves apart: the class's answer is cached, the instance's is asked before every sweep"""
+    return not _on_instance(reg, methods) and _in_class(type(reg), model, methods)
+
+
+def builtin_model(reg, method):
+    """the built-in model whose `method` reg uses as it is, or None"""
+    return next((model for model in MODELS.values() if is_builtin(reg, model, method)), None)
+
+
+def _kind_of_class(cls):
+    """_kind's answer for a class none of whose instances sets a hook of its own, cached per class"""
     kind = _class_kind.get(cls)
     if kind is None:
         if issubclass(cls, SparseGaussianRegression):
             kind = "gaussian"
         elif issubclass(cls, _SparsePGRegressionBase):
             kind = "hooks"
-            b = _BUILTIN.get(getattr(cls, "_obs", None))
-            # built in: an instance of the class that defines the model, with every hook the one that class defines (the same test as
-            # _generate_obs makes for rvs)
-            if b is not None and issubclass(cls, b[0]) and all(getattr(cls, h, None) is getattr(b[0], h) for h in _HOOKS):
+            model = MODELS.get(getattr(cls, "_obs", None))
+            # built in: an instance of the class that defines the model, with every hook the one that class defines
+            if model is not None and issubclass(cls, model.cls) and _in_class(cls, model, _HOOKS):
                 kind = cls._obs
         else:
             raise TypeError("%s: the device runs Gaussian regressions and subclasses of _SparsePGRegressionBase (a_func / b_func / c_func)"
                             % cls.__name__)
         _class_kind[cls] = kind
-    if kind not in ("gaussian", "hooks"):
-        d = reg.__dict__
-        if "a_func" in d or "b_func" in d or "c_func" in d:       # a hook set on the instance
-            return "hooks"
     return kind
+
+
+def _kind(reg):
+    """"gaussian", a built-in PG model's name, or "hooks" for any other Polya-gamma regression; raises for a type the device cannot run"""
+    kind = _kind_of_class(type(reg))
+    return "hooks" if kind != "gaussian" and _on_instance(reg, _HOOKS) else kind
 
 
 def device_obs(regressions):
@@ -500,19 +543,36 @@ def device_obs(regressions):
     regression.  Built-in binomial: ("binomial", n), likewise.  Gaussian: ("gaussian", 1.0).  Any other mix of Polya-gamma regressions, or a
     hook overridden in a class or on an instance: ("hooks", 1.0) -- their a/b/c are evaluated on the host (obs_terms).  Gaussian mixed with
     a Polya-gamma model raises ValueError; a regression type the device cannot run raises TypeError."""
-    kinds = set(_kind(r) for r in regressions)
+    # (this runs over all N regressions before every sweep: the classes' answers once per distinct class, in the list's order)
+    kinds = set(map(_kind_of_class, dict.fromkeys(map(type, regressions))))
     if "gaussian" in kinds:
         if len(kinds) > 1:
-            raise ValueError("a Gaussian regression cannot share a model with Polya-gamma regressions (%s)" % sorted(kinds))
+            raise ValueError("a Gaussian regression cannot share a model with Polya-gamma regressions (%s)" % sorted(set(map(_kind, regressions))))
         return "gaussian", 1.0
-    if len(kinds) != 1 or "hooks" in kinds:
+    if len(kinds) != 1 or "hooks" in kinds or any(_on_instance(r, _HOOKS) for r in regressions):
         return "hooks", 1.0
     kind = kinds.pop()
-    attr = _BUILTIN[kind][1]
+    attr = MODELS[kind].param
     if attr is None:
         return kind, 1.0
     vals = np.array([float(getattr(r, attr)) for r in regressions])
     return kind, (float(vals[0]) if np.all(vals == vals[0]) else vals)
+
+
+def means_of_psi(regressions, mode, psi, X=None):
+    """E[y | psi] (T, n) of `regressions` under the device_obs result `mode` = (obs, par), par a scalar or one value per regression: the
+    model's mean for a built-in mode; in hooks mode per column, from psi where the regression's `mean` is a built-in one, else its own
+    mean(X()) on the design matrix"""
+    obs, par = mode
+    if obs != "hooks":
+        return MODELS[obs].mean(psi, par)
+    mu, Xi = np.empty_like(psi), None
+    for j, r in enumerate(regressions):
+        model = builtin_model(r, "mean")
+        if model is None and Xi is None:
+            Xi = X()
+        mu[:, j] = r.mean(Xi) if model is None else model.mean(psi[:, j], model.par(r))
+    return mu
 
 
 def same_obs(m1, m2):

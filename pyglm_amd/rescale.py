@@ -39,13 +39,13 @@ def check_bins(bins):
 
 
 def interval_par(regressions):
-    """(N,) the factor of log1p(exp(psi)) in -log P(y = 0 | psi) per neuron, from its own observation model (simulate.observation_kinds):
+    """(N,) the factor of log1p(exp(psi)) in -log P(y = 0 | psi) per neuron, from its own observation model (simulate.observation_models):
     1 Bernoulli, xi negative binomial, n binomial; ValueError for a Gaussian neuron, which has no events"""
-    kind, par = _sim.observation_kinds(regressions)
-    bad = np.flatnonzero(kind == _sim.KIND_GAUSSIAN)
-    if bad.size:
-        raise ValueError("time rescaling: neuron %d is Gaussian; a rescaled interval needs events, which a Gaussian neuron does not have" % int(bad[0]))
-    return np.where(kind == _sim.KIND_BERNOULLI, 1.0, par).astype(np.float64)
+    models = _sim.observation_models(regressions)
+    bad = _sim.first_without_events(models)
+    if bad is not None:
+        raise ValueError("time rescaling: neuron %d is Gaussian; a rescaled interval needs events, which a Gaussian neuron does not have" % bad)
+    return np.array([m.par(r) for m, r in zip(models, regressions)], dtype=np.float64)
 
 
 def event_uniforms(seed, draw, stream, elems):

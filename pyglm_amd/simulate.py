@@ -17,9 +17,10 @@ import numpy as np
 import numpy.random as npr
 
 from . import _lib
+from . import regression as _reg
 from ._lib import PglError, call, ptr
 
-OBS_BERNOULLI, OBS_GAUSSIAN = 0, 1
+OBS_BERNOULLI, OBS_GAUSSIAN = _reg.MODELS["bernoulli"].generate, _reg.MODELS["gaussian"].generate      # obs of pgl_generate
 MAX_CHUNK_BINS = 16384          # bins per launch at most
 CHUNK_DRAWS = 1 << 22           # host draws per chunk (N * bins): 32 MiB of U
 CHUNK_MACS = 1 << 33            # multiply-adds per launch (N * N * B * bins): no single launch runs for long
@@ -133,8 +134,8 @@ def generate(Wm, bias, basis, T, obs, noise_scale=0.0, device=None, verbose=Fals
 #                names bin, replicate and neuron (an exploding count model)
 #   Every fp64 operation of the walks is evaluated left to right as written.
 PURPOSE_SIM = 2
-KIND_BERNOULLI, KIND_GAUSSIAN, KIND_NEGBIN, KIND_BINOMIAL = 0, 1, 2, 3
-KINDS = ("bernoulli", "gaussian", "negbin", "binomial")
+KINDS = tuple(sorted(_reg.MODELS, key=lambda name: _reg.MODELS[name].sim_kind))          # KINDS[kind[n]]: the model's name
+KIND_BERNOULLI, KIND_GAUSSIAN, KIND_NEGBIN, KIND_BINOMIAL = (_reg.MODELS[name].sim_kind for name in KINDS)
 NEGBIN_CAP = 65535
 BINOMIAL_MAX_N = 64
 HOST_BLOCK_BINS = 4096          # bins the host path keeps in its rolling buffer when the paths are not kept
@@ -177,33 +178,34 @@ def sim_uniforms(seed, t, neurons, replicates):
     return _unit(o[0], o[1]), _unit(o[2], o[3])
 
 
-def observation_kinds(regressions):
-    """-> (kind (N,) int32, par (N,) float64) of the regressions, each from its own model; ValueError for a regression whose rvs is not one
-    of the four built-in ones (an override in a class, an attribute of the instance, a subclass that changes the hooks but not rvs)"""
-    from . import regression as _reg
-    table = {_reg.SparseBernoulliRegression.rvs: ("bernoulli", KIND_BERNOULLI), _reg.SparseGaussianRegression.rvs: ("gaussian", KIND_GAUSSIAN),
-             _reg.SparseNegativeBinomialRegression.rvs: ("negbin", KIND_NEGBIN), _reg.SparseBinomialRegression.rvs: ("binomial", KIND_BINOMIAL)}
-    kind = np.zeros(len(regressions), dtype=np.int32)
-    par = np.zeros(len(regressions))
+def observation_models(regressions):
+    """-> [regression.ObsModel] of the regressions, each from its own model; ValueError for a regression whose rvs is not one of the four
+    built-in ones (an override in a class, an attribute of the instance, a subclass that changes the hooks but not rvs)"""
+    models = []
     for i, r in enumerate(regressions):
-        entry = None if "rvs" in vars(r) else table.get(getattr(type(r), "rvs", None))
         try:
-            model = _reg._kind(r)
+            model = _reg.MODELS.get(_reg._kind(r))
         except TypeError:
             model = None
-        if entry is None or model != entry[0]:
+        if model is None or not _reg.is_builtin(r, model, "rvs"):
             raise ValueError("simulate(): regression %d (%s) does not draw from one of the built-in observation models (%s); a user-defined rvs "
                              "or observation model cannot be simulated" % (i, type(r).__name__, ", ".join(KINDS)))
-        kind[i] = entry[1]
-        if entry[1] == KIND_GAUSSIAN:
-            par[i] = np.sqrt(float(r.eta))
-        elif entry[1] == KIND_NEGBIN:
-            par[i] = float(r.xi)
-        elif entry[1] == KIND_BINOMIAL:
-            if r.n > BINOMIAL_MAX_N:
-                raise ValueError("simulate(): regression %d is Binomial with n = %d; the sampler supports n <= %d" % (i, r.n, BINOMIAL_MAX_N))
-            par[i] = float(r.n)
-    return kind, par
+        if model.sim_kind == KIND_BINOMIAL and r.n > BINOMIAL_MAX_N:
+            raise ValueError("simulate(): regression %d is Binomial with n = %d; the sampler supports n <= %d" % (i, r.n, BINOMIAL_MAX_N))
+        models.append(model)
+    return models
+
+
+def observation_kinds(regressions):
+    """-> (kind (N,) int32, par (N,) float64) of pgl_simulate, of observation_models(regressions)"""
+    models = observation_models(regressions)
+    return (np.array([m.sim_kind for m in models], dtype=np.int32),
+            np.array([m.sim_par(r) for m, r in zip(models, regressions)], dtype=np.float64))
+
+
+def first_without_events(models):
+    """index of the first of `models` that has no events (Gaussian: no inter-spike or rescaled intervals), or None"""
+    return next((i for i, m in enumerate(models) if not m.events), None)
 
 
 def host_draw(kind, par, psi, u1, u2):

@@ -18,7 +18,6 @@ formulas of the kernels written in NumPy (_HostAccumulators) -- their specificat
 import numpy as np
 
 from . import regression as _regression
-from .utils.utils import logistic
 
 
 def _welford(mean, M2, x, k):
@@ -48,18 +47,11 @@ class _HostAccumulators(object):
         self.pw = [tuple(z(Y.shape) for _ in range(4)) for Y in self.Y] if s.pointwise else None
 
     def _rate(self, psi):
-        s, m = self.s, self.s.model
+        m = self.s.model
         regs = m.regressions[m.n0:m.n1]
-        if s.obs == "bernoulli":
-            return logistic(psi)
-        if s.obs == "gaussian":
-            return psi
-        if s.obs == "negbin":
-            return np.array([r.xi for r in regs]) * np.exp(psi)
-        if s.obs == "binomial":
-            return np.array([float(r.n) for r in regs]) * logistic(psi)
-        from .models import _MEAN_OF_PSI
-        return np.column_stack([_MEAN_OF_PSI[type(r).mean](r, psi[:, j]) for j, r in enumerate(regs)])
+        model = _regression.MODELS.get(self.s.obs)
+        par = None if model is None else np.array([model.par(r) for r in regs])
+        return _regression.means_of_psi(regs, (self.s.obs, par), psi)
 
     def fold(self, eng, a, W, b, k):
         s, m = self.s, self.s.model
@@ -142,14 +134,13 @@ class PosteriorSummary(object):
         regs = model.regressions[model.n0:model.n1]
         link = link_par = None
         if self.obs == "hooks" and self.rates:
-            from .models import _MEAN_OF_PSI, _LINK_OF_MEAN
-            for j, r in enumerate(regs):
-                if "mean" in vars(r) or type(r).mean not in _MEAN_OF_PSI:
-                    raise ValueError("regression %d (%s) has a mean of its own, which the accumulator cannot form from psi: the rates of the "
-                                     "hooks mode need one of the built-in means; summarize(rates=False) works" % (model.n0 + j, type(r).__name__))
-            codes = [_LINK_OF_MEAN[type(r).mean] for r in regs]
-            link = [c for c, _ in codes]
-            link_par = [1.0 if attr is None else float(getattr(r, attr)) for r, (_, attr) in zip(regs, codes)]
+            models = [_regression.builtin_model(r, "mean") for r in regs]
+            if None in models:
+                j = models.index(None)
+                raise ValueError("regression %d (%s) has a mean of its own, which the accumulator cannot form from psi: the rates of the "
+                                 "hooks mode need one of the built-in means; summarize(rates=False) works" % (model.n0 + j, type(regs[j]).__name__))
+            link = [m.link for m in models]
+            link_par = [m.par(r) for m, r in zip(models, regs)]
         if self.heldout:
             self._eng = model._heldout_engine(datas)         # held on to: the model's cache keeps one held-out engine only
             Ys = [np.asarray(d[1] if isinstance(d, tuple) else d) for d in datas]
