@@ -3,32 +3,28 @@
 // the model, so z = 1 - exp(-xi) is uniform; the fold leaves the histogram of z on [0, 1) and (sum z, sum z^2) per neuron, pgl_rescale_ks the
 // binned Kolmogorov-Smirnov statistic (pyglm_amd/rescale.py: rescale_host and ks_binned state the definition).  DESIGN.md section 14.
 //
-// A segmented floating-point sum along time, cut at every event, parallel in time as the inter-spike intervals are (pgl_isi.hip):
-//   rescale_scan_kernel    one workgroup = RS_SEG rows of time of 64 columns; lane = column, so a wave reads 512 contiguous bytes of Psi and
-//                          of Y per row.  Each of the 4 waves walks its RS_WAVE_ROWS rows in time order, eight rows' loads in flight: q of the
+// A segmented floating-point sum along time, cut at every event, parallel in time as the inter-spike intervals are (pgl_isi.hip), on the
+// split, the LDS histogram and the records of pgl_timescan.h:
+//   rescale_scan_kernel    one workgroup = TS_SEG rows of time of 64 columns; lane = column, so a wave reads 512 contiguous bytes of Psi and
+//                          of Y per row.  Each of the 4 waves walks its TS_WAVE_ROWS rows in time order, eight rows' loads in flight: q of the
 //                          eight rows and the running sum in front of each come branch-free; then the lanes that have events in those
 //                          rows take them one at a time (the loop runs as often as the busiest lane has events, not once per row): the
 //                          uniform of the event's cell (Philox, evaluated at event cells only), delta, and -- unless it is the wave's first
-//                          event -- the interval's z, which goes to the workgroup's histogram in LDS ([column][D | 1] ints: the lanes of a
-//                          wave fall in different banks) and to the lane's sum z, sum z^2.  Behind the barrier wave 0 closes the intervals
-//                          that cross the waves and writes the segment's record to `work`, [5][segments][nloc] doubles: first-event row or
-//                          -1; the sum up to and including delta of the first event (without an event: the segment's whole sum); the sum
-//                          behind the last event; sum z, sum z^2.  The workgroup then adds its histogram to hist with integer atomics.
-//   rescale_stitch_kernel  one thread per column walks the records in time order, eight segments' loads in flight, closes the intervals that
-//                          cross segments (through any number of segments without an event; the eight expm1 of a batch side by side) and
-//                          alone writes zsum.
+//                          event -- the interval's z, which goes to the workgroup's histogram in LDS and to the lane's sum z, sum z^2.
+//                          Behind the barrier wave 0 closes the intervals that cross the waves and writes the segment's record to `work`,
+//                          doubles: first-event row or -1; the sum up to and including delta of the first event (without an event: the
+//                          segment's whole sum); the sum behind the last event; sum z, sum z^2.  The workgroup then adds its histogram to
+//                          hist.
+//   rescale_stitch_kernel  one thread per column walks the records in time order, closes the intervals that cross segments (through any
+//                          number of segments without an event; the eight expm1 of a batch side by side) and alone writes zsum.
 // No floating-point atomics: every floating sum is formed by one thread in an order fixed by T and the split, so a column's result has the
 // same bits whatever nloc, neuron0 or the shard; the histogram adds integers only.
-#include "pgl_common.h"
+#include "pgl_timescan.h"
 #include "pgl_rng.h"
 
 namespace {
 
-constexpr int RS_WAVES = 4;
-constexpr int RS_WAVE_ROWS = 64;                      // rows of time one wave walks
-constexpr int RS_SEG = RS_WAVES * RS_WAVE_ROWS;       // rows of time one workgroup owns
-constexpr int RS_REC = 5;                             // first, head, tail, sum z, sum z^2
-constexpr int RS_BATCH = 8;                           // rows whose loads are in flight together
+// a record: first, head, tail, sum z, sum z^2
 
 struct RsArgs {
     const double* Psi; long ldn; const double* bias; const double* Y;
@@ -62,32 +58,30 @@ __device__ __forceinline__ double rs_delta(const RsArgs& a, double q, int n, int
 }
 
 __global__ __launch_bounds__(256) void rescale_scan_kernel(RsArgs a, int* __restrict__ hist, double* __restrict__ rec, long recStride) {
-    extern __shared__ int hs[];                                    // [64][Dp]
-    __shared__ double wrec[RS_REC][RS_WAVES][64];
+    extern __shared__ int hs[];
+    __shared__ TsWaveRecs<double> wrec;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int seg = blockIdx.x, n0 = blockIdx.y * 64;
-    const int n = n0 + lane, D = a.D, Dp = D | 1;
-    for (int i = tid; i < 64 * Dp; i += 256) hs[i] = 0;
-    __syncthreads();
-    int* h = hs + lane * Dp;
+    const int n = n0 + lane, D = a.D;
+    int* h = ts_hist_begin(hs, D);
     double run = 0.0, head = 0.0, sz = 0.0, sz2 = 0.0;             // run: the sum since the column's last event (or the wave's first row)
     int first = -1;
-    const int u0 = seg * RS_SEG + wave * RS_WAVE_ROWS, u1 = min(a.T, u0 + RS_WAVE_ROWS);
+    const int u0 = seg * TS_SEG + wave * TS_WAVE_ROWS, u1 = min(a.T, u0 + TS_WAVE_ROWS);
     if (n < a.nloc) {
         const double bn = a.bias ? a.bias[n] : 0.0, par = a.qpar ? a.qpar[n] : a.qpar0;
         const double* pp = a.Psi + n;
         const double* py = a.Y + n;
-        for (int u = u0; u < u1; u += RS_BATCH) {
-            double q[RS_BATCH], pre[RS_BATCH];
+        for (int u = u0; u < u1; u += TS_BATCH) {
+            double q[TS_BATCH], pre[TS_BATCH];
             unsigned ev = 0;
 #pragma unroll
-            for (int k = 0; k < RS_BATCH; ++k) {
+            for (int k = 0; k < TS_BATCH; ++k) {
                 const bool in = u + k < u1;
                 q[k] = in ? pp[(long)(u + k) * a.ldn] : 0.0;
                 pre[k] = in ? py[(long)(u + k) * a.ldn] : 0.0;
             }
 #pragma unroll
-            for (int k = 0; k < RS_BATCH; ++k) {
+            for (int k = 0; k < TS_BATCH; ++k) {
                 const bool in = u + k < u1, e = pre[k] > 0.0;      // (NaN and negative values compare false; rows past the end hold 0)
                 q[k] = in ? par * log1p(exp(q[k] + bn)) : 0.0;
                 ev |= e ? 1u << k : 0u;
@@ -99,7 +93,7 @@ __global__ __launch_bounds__(256) void rescale_scan_kernel(RsArgs a, int* __rest
                 ev &= ev - 1;
                 double qe = q[0], pe = pre[0];
 #pragma unroll
-                for (int j = 1; j < RS_BATCH; ++j) { qe = k == j ? q[j] : qe; pe = k == j ? pre[j] : pe; }
+                for (int j = 1; j < TS_BATCH; ++j) { qe = k == j ? q[j] : qe; pe = k == j ? pre[j] : pe; }
                 const double x = pe + rs_delta(a, qe, n, u + k);
                 if (first >= 0) rs_close(x, h, D, true, sz, sz2);
                 else { first = u + k; head = x; }
@@ -107,30 +101,25 @@ __global__ __launch_bounds__(256) void rescale_scan_kernel(RsArgs a, int* __rest
         }
         if (first < 0) head = run;
     }
-    wrec[0][wave][lane] = (double)first; wrec[1][wave][lane] = head; wrec[2][wave][lane] = run; wrec[3][wave][lane] = sz; wrec[4][wave][lane] = sz2;
+    wrec.put(wave, lane, (double)first, head, run, sz, sz2);
     __syncthreads();
     if (wave == 0 && n < a.nloc) {                                 // the other waves add nothing to hs any more
         double acc = 0.0, shead = 0.0, ssz = 0.0, ssz2 = 0.0;
         int sfirst = -1;
-        for (int w = 0; w < RS_WAVES; ++w) {
-            const double f = wrec[0][w][lane], hd = wrec[1][w][lane];
+        for (int w = 0; w < TS_WAVES; ++w) {
+            const double f = wrec.v[0][w][lane], hd = wrec.v[1][w][lane];
             if (f < 0.0) { acc += hd; continue; }
             const double x = acc + hd;
             if (sfirst >= 0) rs_close(x, h, D, false, ssz, ssz2);
             else { sfirst = (int)f; shead = x; }
-            ssz += wrec[3][w][lane]; ssz2 += wrec[4][w][lane];
-            acc = wrec[2][w][lane];
+            ssz += wrec.v[3][w][lane]; ssz2 += wrec.v[4][w][lane];
+            acc = wrec.v[2][w][lane];
         }
         if (sfirst < 0) shead = acc;
-        double* r = rec + (long)seg * a.nloc + n;
-        r[0] = (double)sfirst; r[recStride] = shead; r[2 * recStride] = acc; r[3 * recStride] = ssz; r[4 * recStride] = ssz2;
+        ts_put_record(rec, recStride, seg, a.nloc, n, (double)sfirst, shead, acc, ssz, ssz2);
     }
     __syncthreads();
-    for (int i = tid; i < 64 * D; i += 256) {
-        const int col = i / D, d = i - col * D;
-        const int cnt = hs[col * Dp + d];
-        if (cnt != 0 && n0 + col < a.nloc) atomicAdd(hist + (long)(n0 + col) * D + d, cnt);
-    }
+    ts_hist_flush(hs, D, hist + (long)n0 * D, a.nloc - n0);
 }
 
 __global__ __launch_bounds__(256) void rescale_stitch_kernel(const double* __restrict__ rec, long recStride, int nseg, int nloc, int D,
@@ -140,17 +129,14 @@ __global__ __launch_bounds__(256) void rescale_stitch_kernel(const double* __res
     double acc = 0.0, Z1 = 0.0, Z2 = 0.0;
     bool has = false;
     int* h = hist + (long)i * D;
-    for (int s0 = 0; s0 < nseg; s0 += 8) {
-        double v[RS_REC][8];                                       // the records of eight segments, all their loads in flight together
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-#pragma unroll
-            for (int j = 0; j < RS_REC; ++j) v[j][k] = s0 + k < nseg ? rec[j * recStride + (long)(s0 + k) * nloc + i] : (j == 0 ? -1.0 : 0.0);
+    for (int s0 = 0; s0 < nseg; s0 += TS_BATCH) {
+        double v[TS_REC][TS_BATCH];
+        ts_get_records(rec, recStride, s0, nseg, nloc, i, v);
         // the walk proper is a few adds per segment; the eight expm1 behind it do not depend on each other and are evaluated side by side
-        double x[8];
+        double x[TS_BATCH];
         unsigned ev = 0, cl = 0;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
+        for (int k = 0; k < TS_BATCH; ++k) {
             const bool e = !(v[0][k] < 0.0);
             x[k] = acc + v[1][k];                                  // without an event: the segment's whole sum joins (past the end: + 0)
             ev |= e ? 1u << k : 0u;
@@ -159,9 +145,9 @@ __global__ __launch_bounds__(256) void rescale_stitch_kernel(const double* __res
             acc = e ? v[2][k] : x[k];
         }
 #pragma unroll
-        for (int k = 0; k < 8; ++k) x[k] = -expm1(-x[k]);
+        for (int k = 0; k < TS_BATCH; ++k) x[k] = -expm1(-x[k]);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
+        for (int k = 0; k < TS_BATCH; ++k) {
             if (cl >> k & 1u) {
                 atomicAdd(h + rs_bin(x[k], D), 1);                 // (no value comes back: the walk does not wait for it)
                 Z1 += x[k]; Z2 += x[k] * x[k];
@@ -197,18 +183,15 @@ __global__ __launch_bounds__(256) void rescale_ks_kernel(const int* __restrict__
     if (M > 0 && x > coef / sqrt((double)M)) exceed[n] += 1;
 }
 
-inline long rs_segments(int T) { return ((long)T + RS_SEG - 1) / RS_SEG; }
-
 PglPerDeviceSize rs_lds_set;
 
 }  // namespace
 
-int pgl_rescale_segment_rows(void) { return RS_SEG; }
+int pgl_rescale_segment_rows(void) { return TS_SEG; }
 
 size_t pgl_rescale_work_bytes(int nloc, int T) {
     if (nloc < 1 || T < 0) return 0;
-    const size_t bytes = (size_t)RS_REC * (size_t)rs_segments(T) * (size_t)nloc * sizeof(double);
-    return bytes < 16 ? 16 : (bytes + 15) & ~(size_t)15;
+    return ts_work_bytes(sizeof(double), nloc, T);
 }
 
 int pgl_rescale_fold(const double* Psi, long ldn, const double* bias, const double* Y, int T, int nloc, const double* qpar, double qpar0, int D,
@@ -217,7 +200,7 @@ int pgl_rescale_fold(const double* Psi, long ldn, const double* bias, const doub
     PGL_CHECK_ARG(D >= 2 && D <= PGL_RESCALE_MAX_BINS && nloc >= 1 && T >= 0 && ldn >= nloc && hist && zsum);
     PGL_CHECK_ARG(accumulate == 0 || accumulate == 1);
     PGL_CHECK_ARG(T == 0 || (Psi && Y && work && ((uintptr_t)work % 8) == 0));
-    PGL_CHECK_ARG(((long)nloc + 63) / 64 <= 65535 && T <= 2147483647 - RS_SEG);
+    PGL_CHECK_ARG(((long)nloc + 63) / 64 <= 65535 && T <= 2147483647 - TS_SEG);
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     if (!accumulate && (hipMemsetAsync(hist, 0, (size_t)nloc * D * sizeof(int), st) != hipSuccess ||
                         (T == 0 && hipMemsetAsync(zsum, 0, (size_t)nloc * 2 * sizeof(double), st) != hipSuccess))) {
@@ -229,9 +212,9 @@ int pgl_rescale_fold(const double* Psi, long ldn, const double* bias, const doub
     a.Psi = Psi; a.ldn = ldn; a.bias = bias; a.Y = Y; a.T = T; a.nloc = nloc; a.qpar = qpar; a.qpar0 = qpar0; a.D = D;
     a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.c0 = (draw & 0xFFFFFFu) | (PGL_PURPOSE_RESCALE << 24);
     a.neuron0 = neuron0; a.elem0 = elem0;
-    const long nseg = rs_segments(T), recStride = nseg * nloc;
+    const long nseg = ts_segments(T), recStride = nseg * nloc;
     double* rec = static_cast<double*>(work);
-    const size_t lds = (size_t)64 * (D | 1) * sizeof(int);
+    const size_t lds = ts_hist_lds_bytes(D);
     if (int rc = pgl_grow_dynamic_lds(reinterpret_cast<const void*>(rescale_scan_kernel), lds, rs_lds_set)) return rc;
     hipLaunchKernelGGL(rescale_scan_kernel, dim3((unsigned)nseg, (unsigned)((nloc + 63) / 64)), dim3(256), lds, st, a, hist, rec, recStride);
     PGL_CHECK_LAUNCH();

@@ -139,7 +139,7 @@ def test_chunks_of_one_row_and_a_chunk_without_an_event():
 
 
 @pytest.mark.parametrize("N", [1, 64, 65, 129])
-@pytest.mark.parametrize("D", [2, 256])
+@pytest.mark.parametrize("D", [2, 3, 255, 256])
 def test_layouts(N, D):
     # R = 3, rows of N + 7 doubles, replicate blocks 5 rows longer than T, 1e6 in every unused cell: read, it would be an event
     Bt = _bt()
