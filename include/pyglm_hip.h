@@ -404,6 +404,26 @@ int pgl_simulate(const double* Wm, const double* bias, const double* basis, int 
                  long rep0, unsigned long long seed, double* ring, double* Y, long ldr, double* sum, double* sumsq, long t0, int Tc,
                  void* work, int* status, void* hip_stream);
 
+/* Conditional simulation: bins [t0, t0 + Tc) of R replicate trajectories of F FREE neurons of the fitted model, every other neuron clamped to
+ * a recording.  It extends the same call site, the loop of pyglm/models.py:98-151 (generate: :129-144), to the question that loop cannot
+ * ask: some columns of Y are data, the others are drawn.  The activation of free neuron j (global index neuron[j]) splits into
+ *   psi_r[t][j] = base[t][j] + sum_{d < F*B} Wff[j][d] x_r[t][d],   x_r[t][k][:] = sum_{l < L} Y_r[t-1-l][k] basis[l][:]  (free neurons k only),
+ * where base [Tc][ldb] (row k = bin t0 + k) holds the bias and the clamped neurons' part -- parallel in time, formed by the caller with
+ * pgl_activation -- and Wff [F][F*B] is the free block of a*W.  Only the second term is serial in t, and replicates do not interact: ONE
+ * workgroup per replicate walks its bins in a plain launch, with no grid barrier and nothing to wait for.  Draws: those of pgl_simulate --
+ * kind / par [F] of the free neurons, stream = ((rep0 + r) << 32) | neuron[j] (the GLOBAL index), element = t --, so a free neuron sees the
+ * uniforms it sees in pgl_simulate.  Path r depends on (seed, rep0 + r, Wff, base, its initial history) only.
+ * ring [R][L][F] (row t mod L of replicate r = Y_r[t] of the free neurons): read and updated.  Y, Psi: [R] blocks of [Tc][F] at strides ldr / ldp
+ * doubles, or NULL.  sum, sumsq [R][F]: running sums, updated in time order.  status [4] (device int, zeroed by the caller): {2, bin, replicate,
+ * neuron[j]} a negative-binomial walk reached its cap; it ends that replicate's workgroup alone.  1 <= F <= PGL_COND_MAX_FREE (=
+ * pgl_conditional_max_free()), F*B <= 8192 (x_t lives in LDS), t0 + Tc and rep0 + R < 2^31.  A refused argument returns PGL_ERR_ARG (1) and
+ * launches nothing. */
+#define PGL_COND_MAX_FREE 256
+int pgl_conditional_max_free(void);
+int pgl_conditional_simulate(const double* Wff, const double* base, long ldb, const double* basis, int F, int B, int L, const int* kind,
+                             const double* par, const int* neuron, int R, long rep0, unsigned long long seed, double* ring, double* Y, long ldr,
+                             double* Psi, long ldp, double* sum, double* sumsq, long t0, int Tc, int* status, void* hip_stream);
+
 /* ---- lagged cross products (pgl_xcorr.hip): the pairwise statistic of the posterior predictive check ---------------------------------- */
 /* This project's own statistic, as the count models are (the reference has no predictive check): the sums behind the lagged
  * cross-correlogram of pyglm_amd/simulate.py,

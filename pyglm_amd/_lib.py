@@ -104,6 +104,8 @@ SIGNATURES = {
     "pgl_generate": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_d, c_p, c_p, c_p, c_l, c_i, c_p, c_p, c_p],
     "pgl_simulate_work_bytes": [c_i, c_i, c_i],
     "pgl_simulate": [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_l, c_u64, c_p, c_p, c_l, c_p, c_p, c_l, c_i, c_p, c_p, c_p],
+    "pgl_conditional_max_free": [],
+    "pgl_conditional_simulate": [c_p, c_p, c_l, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_l, c_u64, c_p, c_p, c_l, c_p, c_l, c_p, c_p, c_l, c_i, c_p, c_p],
     "pgl_lagged_work_bytes": [c_i, c_i, c_i, c_i],
     "pgl_lagged_products": [c_p, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_p, c_l, c_i, c_i, c_p, c_p, c_p],
     "pgl_isi_segment_rows": [],

@@ -29,6 +29,8 @@
 // launch to launch: no atomics -- and all R replicates meet at the ONE grid barrier per bin: the exchange buffer is [2][R][N*B].  Within a
 // bin the replicates are independent: with the rows of Wm in registers (N*B <= GEN_KR * 64) x_{r+1} is fetched into registers while the
 // dot products of x_r run out of LDS (two LDS buffers, one workgroup barrier per replicate).
+// A third kernel, conditional_kernel (pgl_conditional_simulate), is the one-workgroup form of the scheme run once per replicate on the free
+// neurons of a model whose other neurons are clamped to a recording: the same pieces, and no grid barrier at all.
 #include "pgl_common.h"
 #include "pgl_rng.h"
 #include "../../include/pyglm_hip.h"
@@ -245,7 +247,8 @@ __device__ __forceinline__ void ring_copy(const GenArgs& g, int R, const Wg& w) 
 }
 
 // the prologue: the LDS pointers, the thread's place, rings and basis into LDS where the host gave them room.  The caller places the barrier.
-__device__ __forceinline__ Wg wg_begin(const GenArgs& g, int R) {
+// owner: which block of npw neurons the workgroup owns (blockIdx.x on a grid that splits the neurons; 0 where a workgroup owns them all)
+__device__ __forceinline__ Wg wg_begin(const GenArgs& g, int R, int owner) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     Wg w;
@@ -254,7 +257,7 @@ __device__ __forceinline__ Wg wg_begin(const GenArgs& g, int R) {
     w.xs = reinterpret_cast<double*>(smem + 16);
     w.rl = g.ring_off ? reinterpret_cast<double*>(smem + g.ring_off) : nullptr;
     w.sb = g.basis_off ? reinterpret_cast<double*>(smem + g.basis_off) : nullptr;
-    w.n_lo = blockIdx.x * g.npw;
+    w.n_lo = owner * g.npw;
     w.nown = min(g.N, w.n_lo + g.npw) - w.n_lo;
     w.NB = g.N * g.B;
     w.gpw = 64 / g.lpn; w.grp = lane / g.lpn; w.gl = lane % g.lpn;
@@ -295,7 +298,7 @@ __device__ __forceinline__ void wg_end(const GenArgs& g, int R, const Wg& w) {
 // XLDS: x_t is read from LDS.
 template <bool XLDS, int KR>
 __global__ __launch_bounds__(GEN_THREADS) void generate_kernel(GenArgs g) {
-    const Wg w = wg_begin(g, 1);                                     // LDS x: N*B, or KR*64 of which those beyond N*B are zero
+    const Wg w = wg_begin(g, 1, blockIdx.x);                         // LDS x: N*B, or KR*64 of which those beyond N*B are zero
     double wr[KR > 0 ? KR : 1];
     load_row<KR>(g, w, wr);
     const int wave = threadIdx.x >> 6, L = g.L;
@@ -435,7 +438,7 @@ template <bool XLDS, int KR>
 __global__ __launch_bounds__(GEN_THREADS) void simulate_kernel(SimArgs s) {
     const GenArgs& g = s.g;
     const int R = s.R;
-    const Wg w = wg_begin(g, R);                                     // LDS x: 2 * KR * 64 (KR > 0) or N*B (XLDS); after the basis, psi: SIM_PSI_MAX
+    const Wg w = wg_begin(g, R, blockIdx.x);                         // LDS x: 2 * KR * 64 (KR > 0) or N*B (XLDS); after the basis, psi: SIM_PSI_MAX
     double wr[KR > 0 ? KR : 1];
     load_row<KR>(g, w, wr);
     double* xs = w.xs;
@@ -533,14 +536,86 @@ __global__ __launch_bounds__(GEN_THREADS) void simulate_kernel(SimArgs s) {
     wg_end(g, R, w);
 }
 
+// =====================================================================================================================================
+// pgl_conditional_simulate: R replicate trajectories of F FREE neurons of the fitted model, the other neurons clamped to a recording.
+//
+// The law is stated once, in the docstring of conditional_host in pyglm_amd/simulate.py ("THE CONDITIONAL LAW"); in short
+//   psi_r[t, j] = base[t, j] + Wff[j, :] . x_r[t],   x_r[t][k, :] = sum_l y_r[t-1-l, k] basis[l, :]   over the free neurons k alone,
+// base -- the bias and everything the clamped neurons contribute, parallel in time -- being an INPUT, and y_r[t, j] sim_draw's draw of the
+// free neuron's own model on the stream of pgl_simulate: stream = (replicate << 32) | neuron[j], the GLOBAL index, element = t.
+//
+// Only the F x (F*B) block is serial in t and the replicates do not interact: workgroup r walks the bins of replicate r by itself, in a plain
+// launch -- no exchange buffer, no grid barrier, nothing a workgroup waits for but its own two barriers per bin (x_t complete; the ring row
+// of y_t complete and x_t no longer read).  It is the one-workgroup form of the scheme above on an F-neuron model, from the same pieces:
+// history writes x_t straight into LDS, row_dot folds it with the row of Wff in the order that is psi's bits, sim_draw draws.  The lanes
+// split as lane_split decides for a workgroup that owns F neurons; F <= PGL_COND_MAX_FREE = GEN_THREADS makes that ONE round: lane 0 of a
+// group keeps its neuron, its model and its running sums for the whole launch.  Residency by size (the host's plan): the ring [L][F] and the
+// basis in LDS or in global memory as for pgl_simulate; Wff in LDS when it fits behind them, else streamed from L2.
+struct CondArgs {
+    GenArgs g;               // Wm = Wff, bias = base (only read by wg_begin), basis, ring ([R][L][F]), status ([4]), t0, Tc, N = npw = F, B, L, lpn, lpp, offsets
+    const double* base; long ldb;            // [Tc][ldb], row k = bin t0 + k
+    const int* kind; const double* par;      // [F], of the free neurons
+    const int* neuron;                       // [F] global indices
+    double* Y; long ldr;                     // [R][Tc][F], replicate stride ldr; or null
+    double* Psi; long ldp;                   // likewise
+    double* sum; double* sumsq;              // [R][F]
+    long rep0; unsigned long long seed;
+    int wff_off;                             // byte offset of Wff in LDS (0: streamed)
+};
+
+__global__ __launch_bounds__(GEN_THREADS) void conditional_kernel(CondArgs c) {
+    const int r = blockIdx.x;
+    GenArgs g = c.g;
+    g.ring += (long)r * g.L * g.N;                                   // the workgroup's replicate is the whole "model" of the pieces
+    const Wg w = wg_begin(g, 1, 0);                                   // LDS x: F*B
+    const int F = g.N, NB = w.NB, L = g.L;
+    const double* wff = g.Wm;
+    if (c.wff_off) {
+        double* wl = reinterpret_cast<double*>(w.smem + c.wff_off);
+        for (int e = threadIdx.x; e < F * NB; e += GEN_THREADS) wl[e] = g.Wm[e];
+        wff = wl;
+    }
+    const int j = w.i1;                                              // the host checks F <= GEN_WAVES * gpw: one round
+    const bool mine = w.mine1;
+    const double* row = wff + (long)(j < F ? j : 0) * NB;
+    const int n = mine ? c.neuron[j] : 0, kind = mine ? c.kind[j] : 0;
+    const double par = mine ? c.par[j] : 0.0;
+    double sum1 = mine ? c.sum[(long)r * F + j] : 0.0, sq1 = mine ? c.sumsq[(long)r * F + j] : 0.0;
+    const double wr[1] = {0.0};
+    __syncthreads();
+    for (int k = 0; k < g.Tc; ++k) {
+        const long t = g.t0 + k;
+        history(g, 1, t - 1, 0, F, w.rl, w.sb, w.xs);                // x_t from the ring
+        __syncthreads();
+        const double bt = mine ? c.base[(long)k * c.ldb + j] : 0.0;  // issued ahead of the dot product
+        const double acc = row_dot<0>(wr, row, w.xs, NB, w.gl, g.lpn, j < F);
+        int capped = 0;
+        if (mine) {
+            const double psi = bt + acc;
+            PglPhilox rng;
+            pgl_rng_init(rng, c.seed, ((uint64_t)(c.rep0 + r) << 32) | (uint32_t)n, (uint64_t)t, PGL_PURPOSE_SIM);
+            bool cap = false;
+            const double y = sim_draw(kind, par, psi, rng, cap);
+            if (cap) { sim_cap_fail(g.status, t, c.rep0 + r, n); capped = 1; }
+            if (c.Y) c.Y[(long)r * c.ldr + (long)k * F + j] = y;
+            if (c.Psi) c.Psi[(long)r * c.ldp + (long)k * F + j] = psi;
+            const int rw = (int)(t % L);
+            if (w.rl) w.rl[rw * F + j] = y;
+            else g.ring[(long)rw * F + j] = y;
+            sum1 = __dadd_rn(sum1, y);
+            sq1 = __dadd_rn(sq1, __dmul_rn(y, y));
+        }
+        if (!w.rl) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // (a ring in global memory: this bin's row before it is read)
+        if (__syncthreads_or(capped)) return;                         // a capped walk ends THIS workgroup: the status word names it
+    }
+    if (mine) { c.sum[(long)r * F + j] = sum1; c.sumsq[(long)r * F + j] = sq1; }
+    wg_end(g, 1, w);
+}
+
 struct GenGeometry { int G, npw, lpn, lpp; };
 
-GenGeometry geometry(int N, int B) {
-    GenGeometry q;
-    if ((long)N * N * B <= PGL_GEN_ONE_WG_MAX) q.G = 1;
-    else q.G = std::min(pgl_device_cus(pgl_device()), (N + 3) / 4);
-    q.npw = (N + q.G - 1) / q.G;
-    q.G = (N + q.npw - 1) / q.npw;                                     // no workgroup without neurons
+// the lanes of a workgroup that owns q.npw neurons: lpn per neuron in the dot products, lpp per (neuron, basis function) in the history sums
+void lane_split(GenGeometry& q, int B) {
     int per_wave = (q.npw + GEN_WAVES - 1) / GEN_WAVES, gpw = 1;
     while (gpw < per_wave && gpw < 64) gpw *= 2;
     q.lpn = 64 / gpw;
@@ -548,6 +623,15 @@ GenGeometry geometry(int N, int B) {
     const int pairs = q.npw * B;
     q.lpp = 64;
     while (q.lpp > 1 && pairs * q.lpp > GEN_THREADS) q.lpp /= 2;
+}
+
+GenGeometry geometry(int N, int B) {
+    GenGeometry q;
+    if ((long)N * N * B <= PGL_GEN_ONE_WG_MAX) q.G = 1;
+    else q.G = std::min(pgl_device_cus(pgl_device()), (N + 3) / 4);
+    q.npw = (N + q.G - 1) / q.G;
+    q.G = (N + q.npw - 1) / q.npw;                                     // no workgroup without neurons
+    lane_split(q, B);
     return q;
 }
 
@@ -581,26 +665,29 @@ int launch(const char* entry, const Args& a, void* work, int G, size_t lds, hipS
 // the launch's geometry, which kernel instance runs it and its dynamic LDS
 struct GenPlan { GenGeometry q; bool xlds, regs; size_t lds; };
 
-// what an entry point asks of the LDS layout: x double-buffered when the rows of Wm are in registers; the rings go into LDS when they are
-// at most ring_cap and the whole request -- with the basis and the `extra` bytes the kernel appends -- stays within lds_cap
-struct LdsPolicy { bool x_double; size_t ring_cap, lds_cap, extra; };
+// what an entry point asks of the LDS layout: row_regs, its kernel has an instance that keeps the rows of Wm in registers, and x is
+// double-buffered there with x_double; the rings go into LDS when they are at most ring_cap and the whole request -- with the basis and the
+// `extra` bytes the kernel appends -- stays within lds_cap
+struct LdsPolicy { bool row_regs, x_double; size_t ring_cap, lds_cap, extra; };
 // (pgl_generate: the ring's, the basis' and x's own caps keep the request at about 112 KiB, far below a CU's LDS: no test of the total)
-constexpr LdsPolicy GEN_LDS_POLICY = {false, GEN_RING_LDS_MAX, SIZE_MAX, 0};
+constexpr LdsPolicy GEN_LDS_POLICY = {true, false, GEN_RING_LDS_MAX, SIZE_MAX, 0};
 // (pgl_simulate: the rings go into LDS when they, the basis and the activation table still fit the CU's 160 KiB beside x)
-constexpr LdsPolicy SIM_LDS_POLICY = {true, SIM_RING_LDS_MAX, SIM_LDS_BYTES, SIM_PSI_MAX * sizeof(double)};
+constexpr LdsPolicy SIM_LDS_POLICY = {true, true, SIM_RING_LDS_MAX, SIM_LDS_BYTES, SIM_PSI_MAX * sizeof(double)};
 
-// The plan of a launch of R trajectories, and the head of its argument block (what is not set here is the entry point's own).  x in LDS is
-// N*B doubles, or with the rows of Wm in registers GEN_KR * 64 (twice that when the kernel double-buffers x).
-int plan(int N, int B, int L, int R, const LdsPolicy& pol, const double* Wm, const double* bias, const double* basis, double* ring, long t0,
+// (pgl_conditional_simulate: the same caps on ring and basis, below the CU's LDS as a whole; Wff takes what is left, decided by the entry point)
+constexpr LdsPolicy COND_LDS_POLICY = {false, false, SIM_RING_LDS_MAX, SIM_LDS_BYTES, 0};
+
+// The plan of a launch of R trajectories per workgroup on the geometry q, and the head of its argument block (what is not set here is the
+// entry point's own).  x in LDS is N*B doubles, or with the rows of Wm in registers GEN_KR * 64 (twice that when the kernel double-buffers x).
+int plan(const GenGeometry& q, int N, int B, int L, int R, const LdsPolicy& pol, const double* Wm, const double* bias, const double* basis, double* ring, long t0,
          int Tc, void* work, int* status, GenArgs& a, GenPlan& p) {
     PGL_CHECK_ARG((long)N * B <= (1L << 30) && (long)L * N <= (1L << 31) - 1);
-    const GenGeometry q = geometry(N, B);
     const int NB = N * B;
     auto al16 = [](size_t x) { return (x + 15) / 16 * 16; };
     p.q = q;
     p.xlds = NB <= GEN_XLDS_MAX;
     // registers for the rows of Wm: one neuron per wave (npw <= 4, 64 lanes per neuron) and at most GEN_KR elements per lane
-    p.regs = p.xlds && q.npw <= GEN_WAVES && q.lpn == 64 && NB <= GEN_KR * 64;
+    p.regs = pol.row_regs && p.xlds && q.npw <= GEN_WAVES && q.lpn == 64 && NB <= GEN_KR * 64;
     size_t lds = 16 + (p.regs ? (pol.x_double ? 2 : 1) * (size_t)GEN_KR * 64 * sizeof(double) : p.xlds ? al16((size_t)NB * sizeof(double)) : 0);
     const size_t ring_bytes = (size_t)R * L * q.npw * sizeof(double), basis_bytes = (size_t)L * B * sizeof(double);
     const bool basis_lds = basis_bytes <= GEN_BASIS_LDS_MAX;
@@ -611,8 +698,8 @@ int plan(int N, int B, int L, int R, const LdsPolicy& pol, const double* Wm, con
     if (basis_lds) { a.basis_off = (int)lds; lds += al16(basis_bytes); }
     p.lds = lds;
     a.Wm = Wm; a.bias = bias; a.basis = basis; a.ring = ring;
-    a.bar = static_cast<unsigned*>(work);
-    a.xbuf = reinterpret_cast<double*>(static_cast<char*>(work) + GEN_BAR_BYTES);
+    a.bar = static_cast<unsigned*>(work);                            // (work null: a kernel without exchange buffers and grid barrier)
+    a.xbuf = work ? reinterpret_cast<double*>(static_cast<char*>(work) + GEN_BAR_BYTES) : nullptr;
     a.status = status;
     a.t0 = t0; a.Tc = Tc; a.N = N; a.B = B; a.L = L;
     a.npw = q.npw; a.lpn = q.lpn; a.lpp = q.lpp;
@@ -634,7 +721,7 @@ extern "C" int pgl_generate(const double* Wm, const double* bias, const double* 
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     GenArgs a{};
     GenPlan p;
-    int rc = plan(N, B, L, 1, GEN_LDS_POLICY, Wm, bias, basis, ring, t0, Tc, work, status, a, p);
+    int rc = plan(geometry(N, B), N, B, L, 1, GEN_LDS_POLICY, Wm, bias, basis, ring, t0, Tc, work, status, a, p);
     if (rc) return rc;
     a.U = U; a.Y = Y; a.obs = obs; a.scale = noise_scale;
     if (p.regs) return launch<generate_kernel<true, GEN_KR>>("pgl_generate", a, work, p.q.G, p.lds, st);
@@ -657,7 +744,7 @@ extern "C" int pgl_simulate(const double* Wm, const double* bias, const double* 
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     SimArgs s{};
     GenPlan p;
-    int rc = plan(N, B, L, R, SIM_LDS_POLICY, Wm, bias, basis, ring, t0, Tc, work, status, s.g, p);
+    int rc = plan(geometry(N, B), N, B, L, R, SIM_LDS_POLICY, Wm, bias, basis, ring, t0, Tc, work, status, s.g, p);
     if (rc) return rc;
     PGL_CHECK_ARG((long)R * p.q.npw * B <= (1L << 30) && (long)R * L * p.q.npw <= (1L << 30) && p.q.npw <= SIM_PSI_MAX);
     s.psi_off = (int)p.lds;                                          // the activation table at the end
@@ -666,4 +753,39 @@ extern "C" int pgl_simulate(const double* Wm, const double* bias, const double* 
     if (p.regs) return launch<simulate_kernel<true, GEN_KR>>("pgl_simulate", s, work, p.q.G, p.lds, st);
     if (p.xlds) return launch<simulate_kernel<true, 0>>("pgl_simulate", s, work, p.q.G, p.lds, st);
     return launch<simulate_kernel<false, 0>>("pgl_simulate", s, work, p.q.G, p.lds, st);
+}
+
+extern "C" int pgl_conditional_max_free(void) { return PGL_COND_MAX_FREE; }
+
+extern "C" int pgl_conditional_simulate(const double* Wff, const double* base, long ldb, const double* basis, int F, int B, int L, const int* kind,
+                                        const double* par, const int* neuron, int R, long rep0, unsigned long long seed, double* ring, double* Y,
+                                        long ldr, double* Psi, long ldp, double* sum, double* sumsq, long t0, int Tc, int* status,
+                                        void* hip_stream) {
+    static PglPerDeviceSize lds_set;
+    PGL_CHECK_ARG(Wff && base && basis && kind && par && neuron && ring && sum && sumsq && status);
+    PGL_CHECK_ARG(F > 0 && F <= PGL_COND_MAX_FREE && B > 0 && L > 0 && R > 0 && Tc > 0 && t0 >= 0 && rep0 >= 0);
+    PGL_CHECK_ARG((long)F * B <= GEN_XLDS_MAX);                                      // x_t lives in LDS
+    PGL_CHECK_ARG(t0 + Tc <= (1L << 31) - 1 && rep0 + R <= (1L << 31) - 1);           // the status word and the Philox counter hold them in 32 bits
+    PGL_CHECK_ARG(ldb >= F && (!Y || ldr >= (long)Tc * F) && (!Psi || ldp >= (long)Tc * F));
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    CondArgs c{};
+    GenPlan p;
+    GenGeometry q;
+    q.G = R; q.npw = F;
+    lane_split(q, B);
+    PGL_CHECK_ARG(F <= GEN_WAVES * (64 / q.lpn));                                    // one round of neurons
+    int rc = plan(q, F, B, L, 1, COND_LDS_POLICY, Wff, base, basis, ring, t0, Tc, nullptr, status, c.g, p);
+    if (rc) return rc;
+    const size_t wff_bytes = ((size_t)F * F * B * sizeof(double) + 15) / 16 * 16;
+    if (p.lds + wff_bytes <= SIM_LDS_BYTES) {                         // Wff behind x, the ring and the basis, when it fits
+        c.wff_off = (int)p.lds;
+        p.lds += wff_bytes;
+    }
+    c.base = base; c.ldb = ldb; c.kind = kind; c.par = par; c.neuron = neuron; c.Y = Y; c.ldr = ldr; c.Psi = Psi; c.ldp = ldp;
+    c.sum = sum; c.sumsq = sumsq; c.rep0 = rep0; c.seed = seed;
+    rc = pgl_grow_dynamic_lds(reinterpret_cast<const void*>(conditional_kernel), p.lds, lds_set);
+    if (rc) return rc;
+    hipLaunchKernelGGL(conditional_kernel, dim3(R), dim3(GEN_THREADS), p.lds, st, c);
+    PGL_CHECK_LAUNCH();
+    return PGL_OK;
 }

@@ -668,6 +668,15 @@ class GibbsEngine(object):
         ds = self.datasets[i]
         return ds.Psi[:, :self.nloc].cpu().numpy()
 
+    @_on_device
+    def psi_columns(self, a, W, b, i, cols, start, stop):
+        """rows [start, stop) and the local columns `cols` of psi(a, W, b, i) -> host (stop - start, len(cols)): the slice is taken on the
+        device, so only it crosses to the host (conditional simulation reads a few neurons' columns of a long recording)"""
+        self._upload_weights(a, W, b)
+        self._psi_pass(False, 0, 0)
+        idx = torch.from_numpy(np.ascontiguousarray(cols, dtype=np.int64)).to(self.dev)
+        return self.datasets[i].Psi[start:stop].index_select(1, idx).cpu().numpy()
+
     # ------------------------------------------------------------------ posterior accumulators (pyglm_amd/summary.py)
     def summary_bytes(self, rates=True, pointwise=False):
         """device bytes summary_alloc takes: (T_i x ldn) doubles per data set x 2 (rates) + 4 (pointwise), and the state's moments"""

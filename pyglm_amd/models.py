@@ -564,6 +564,77 @@ class NonlinearAutoregressiveModel(object):
             self._refuse_gaussian_intervals("predictive_check(isi=%d)" % isi)
         return PredictiveCheck(self, replicates=replicates, seed=seed, data=data, gpu=gpu, lags=lags, isi=isi)
 
+    def _conditional_inputs(self, free, data, start, stop):
+        """what the conditional law (simulate.conditional_host) takes, read from the current state and data set `data` for the checked `free`
+        and window -> dict(Wff (F, F*B), base (T', F), basis, kind, par (F,), hist (L, F), Y: the recording).  base comes from engine.psi on
+        the state with the free columns of the adjacency set to zero, gathered over the shards as `means` gathers"""
+        from . import simulate as _sim
+        A, W, b = self._adopt_state()
+        N, B = self.N, self.B
+        L = self.basis.shape[0]
+        kind, par = _sim.observation_kinds([self.regressions[n] for n in free])
+        Wm = (W * A[:, :, None]).reshape(N, N * B)
+        cols = (free[:, None] * B + np.arange(B)[None, :]).ravel()
+        a, Wl, bl = self._local_state()
+        a = np.array(a, dtype=bool)
+        a[:, free] = False
+        if _dist() is None or self._shard_override:     # every column is local: only the window's free columns leave the engine
+            if free[0] < self.n0 or free[-1] >= self.n1:
+                raise ValueError("conditional simulation: this model holds neurons [%d, %d) only; free neuron %d is outside"
+                                 % (self.n0, self.n1, free[0] if free[0] < self.n0 else free[-1]))
+            eng = self.engine
+            if hasattr(eng, "psi_columns"):
+                base = eng.psi_columns(a, Wl, bl, data, free - self.n0, start, stop)
+            else:
+                base = np.asarray(eng.psi(a, Wl, bl, data), dtype=np.float64)[start:stop][:, free - self.n0]
+        else:
+            psi = np.asarray(self.engine.psi(a, Wl, bl, data), dtype=np.float64)[start:stop]
+            base = self._gather_rows(np.ascontiguousarray(psi.T)).T[:, free]
+        Y = np.asarray(self.data_list[data][1], dtype=np.float64)
+        hist = np.zeros((L, free.size))
+        h = Y[max(0, start - L):start][:, free]
+        hist[L - h.shape[0]:] = h
+        return dict(Wff=np.ascontiguousarray(Wm[free][:, cols]), base=np.ascontiguousarray(base, dtype=np.float64),
+                    basis=np.asarray(self.basis, dtype=np.float64), kind=kind, par=par, hist=hist, Y=Y)
+
+    def conditional_simulate(self, free, data=0, replicates=1, seed=0, first_replicate=0, start=0, stop=None, keep_paths=True, gpu=None):
+        """Conditional simulation: the neurons `free` (distinct indices, at most simulate.PGL_COND_MAX_FREE) are drawn from the model's CURRENT
+        state while every other neuron is clamped to the recording of data set `data`, over the window [start, stop) of its bins -- what
+        the model says neuron j does GIVEN the rest of the population.  `means` does not answer that (it feeds the neuron's own recorded
+        history through its self-coupling) and simulate() simulates everybody.  pyglm_amd/simulate.py (conditional_host) states the law: the
+        clamped neurons enter through base = bias + their columns of a*W against the data set's regressors X -- a data set added with a
+        caller's own X uses THAT X for the clamped part --, the free neurons through their own simulated history, which before `start` is
+        the recording's; the random stream is simulate()'s, keyed by the global neuron index, so replicate r = first_replicate + i depends on
+        (seed, r, the state, the recording, free, the window) and on nothing else.
+        Returns a simulate.ConditionalSimulation: free; Y (R, T', F) or None (keep_paths=False); sum, sumsq (R, F), rate(), fano(); history
+        (R, L, F); base (T', F); t0, t1; paths(r) -> (T', N), the recording's window with the free columns replaced by replicate r.
+        gpu as for simulate(): None -- the device (pgl_conditional_simulate: one workgroup per replicate, no grid barrier) when there is
+        one, True -- the device or a PglError, False -- NumPy; a model with an engine_factory takes the NumPy path.  An empty `free`, more
+        than 256 free neurons, a duplicate, an index out of range and a window outside the recording are ValueErrors that name the offender.
+        On a sharded model base is gathered; every rank then simulates the same thing."""
+        from . import simulate as _sim
+        data = range(len(self.data_list))[data]
+        free = _sim.check_free(free, self.N)
+        start, stop = _sim.check_window(start, stop, self.data_list[data][1].shape[0])
+        if self._engine_factory is not None and gpu:
+            raise ValueError("conditional_simulate(gpu=True): a model with an engine_factory takes the NumPy path (gpu=None or False)")
+        on_device = self._on_gpu(gpu, "conditional_simulate")
+        inp = self._conditional_inputs(free, data, start, stop)
+        sim = _sim.conditional_simulate(inp["Wff"], inp["base"], inp["basis"], inp["kind"], inp["par"], free, replicates, seed, first_replicate,
+                                        inp["hist"], start, keep_paths, on_device, self._device)
+        sim._recording = inp["Y"]
+        return sim
+
+    def conditional_check(self, free, replicates=8, seed=0, data=0, start=0, stop=None, gpu=None):
+        """the population-conditioned prediction of the neurons `free` of data set `data` bound to this model (simulate.ConditionalPrediction):
+        call its collect() after every sweep to be kept -- it simulates `replicates` fresh conditional replicates over [start, stop) from the
+        current state --, read rate_mean / rate_std (T', F), log_score() -> dict(total, per_neuron, per_bin) and count at the end.  Changes
+        nothing in the chain."""
+        from .simulate import ConditionalPrediction
+        if self._engine_factory is not None and gpu:
+            raise ValueError("conditional_check(gpu=True): a model with an engine_factory takes the NumPy path (gpu=None or False)")
+        return ConditionalPrediction(self, free, replicates=replicates, seed=seed, data=data, start=start, stop=stop, gpu=gpu)
+
     def time_rescaling(self, bins=64, seed=0, coef=1.36, datas=None):
         """the time-rescaling goodness-of-fit test of the data under this model's chain (pyglm_amd/rescale.py: TimeRescaling): call its
         collect() after every sweep to be kept -- it reads the recorded data against the current rates, no replicate is simulated --, read

@@ -1,6 +1,7 @@
 """Forward simulation of a population model: the device path of `NetworkGLM.generate()` (reference pyglm/models.py:98-151), and -- second half
 of this file -- posterior predictive simulation, `model.simulate()` / `model.predictive_check()`: its law, the NumPy path and the driver of
-pgl_simulate.
+pgl_simulate; and -- last part -- conditional simulation, `model.conditional_simulate()` / `model.conditional_check()`: some neurons are drawn
+while the others are clamped to a recording (its law: conditional_host; the driver of pgl_conditional_simulate).
 
 generate():
 
@@ -902,3 +903,325 @@ class PredictiveCheck(object):
             le = (ok & (rep <= obs)).sum(axis=0)
         p = np.minimum(1.0, 2.0 * np.minimum(1 + ge, 1 + le) / (M + 1.0))
         return np.where(np.isnan(obs), np.nan, p)
+
+
+# =====================================================================================================================================
+# Conditional simulation: model.conditional_simulate() / model.conditional_check().  Some neurons are data, the others are drawn.
+PGL_COND_MAX_FREE = 256         # free neurons at most (include/pyglm_hip.h)
+COND_MAX_X = 8192               # F * B at most on the device: x_t of a replicate lives in LDS
+
+
+def check_free(free, N):
+    """-> the free neurons as a sorted int64 array; ValueError, naming the offender, for an empty list, more than PGL_COND_MAX_FREE, a
+    duplicate or an index outside [0, N)"""
+    f = np.asarray(free)
+    if f.ndim != 1 or f.size == 0:
+        raise ValueError("conditional simulation: `free` is empty; a list of at least one neuron index is required")
+    if not np.issubdtype(f.dtype, np.integer):
+        raise ValueError("conditional simulation: `free` must hold integer neuron indices, got dtype %s" % f.dtype)
+    f = f.astype(np.int64)
+    if f.size > PGL_COND_MAX_FREE:
+        raise ValueError("conditional simulation: %d free neurons; at most PGL_COND_MAX_FREE = %d can be free" % (f.size, PGL_COND_MAX_FREE))
+    bad = f[(f < 0) | (f >= N)]
+    if bad.size:
+        raise ValueError("conditional simulation: free neuron index %d is outside [0, N = %d)" % (bad[0], N))
+    f = np.sort(f)
+    dup = f[1:][f[1:] == f[:-1]]
+    if dup.size:
+        raise ValueError("conditional simulation: neuron %d is listed more than once in `free`" % dup[0])
+    return f
+
+
+def check_window(start, stop, T):
+    """-> (start, stop) of a window of a recording of T bins (stop None: T); ValueError unless 0 <= start <= stop <= T"""
+    start, stop = int(start), T if stop is None else int(stop)
+    if not 0 <= start <= stop <= T:
+        raise ValueError("conditional simulation: the window [%d, %d) is not within the recording's bins [0, %d)" % (start, stop, T))
+    return start, stop
+
+
+class ConditionalSimulation(object):
+    """what model.conditional_simulate() returns: free (F,), the global indices of the free neurons; Y (R, T', F) float64, the free neurons'
+    paths over the window, or None (keep_paths=False); sum and sumsq (R, F), added in time order; history (R, L, F), the last L bins of every
+    replicate; base (T', F), the input of the serial law; t0 / t1, the window in the recording's bins; seed and first_replicate; psi (R, T', F)
+    where it was asked for."""
+
+    def __init__(self, free, Y, sum, sumsq, history, base, t0, t1, seed, first_replicate, psi=None, recording=None):
+        self.free, self.Y, self.sum, self.sumsq, self.history, self.base = np.asarray(free), Y, sum, sumsq, history, base
+        self.t0, self.t1, self.seed, self.first_replicate = int(t0), int(t1), int(seed), int(first_replicate)
+        self.psi, self._recording = psi, recording
+
+    @property
+    def T(self):
+        return self.t1 - self.t0
+
+    def rate(self):
+        """mean of y per bin, (R, F)"""
+        return self.sum / self.T
+
+    def fano(self):
+        """variance / mean of y over the bins, (R, F); NaN where the mean is zero"""
+        return fano_factor(self.sum, self.sumsq, self.T)
+
+    def paths(self, r):
+        """(T', N): the recording's window with the free columns replaced by replicate r"""
+        if self.Y is None or self._recording is None:
+            raise ValueError("paths(): the paths were not kept (keep_paths=False) or no recording is attached")
+        out = np.array(self._recording[self.t0:self.t1], dtype=np.float64)
+        out[:, self.free] = self.Y[r]
+        return out
+
+
+def cond_chunk_bins(F, R):
+    """bins per launch of pgl_conditional_simulate for F free neurons and R replicates"""
+    return int(max(1, min(MAX_CHUNK_BINS, CHUNK_DRAWS // (F * R))))
+
+
+def conditional_host(Wff, base, basis, kind, par, neuron, R, seed, rep0, hist, t0, keep_paths, want_psi=False):
+    """THE CONDITIONAL LAW in NumPy (the header comment of pgl_conditional_simulate in pyglm_amd/csrc/pgl_generate.hip refers to this; the
+    kernel and this function are two separately written implementations and are tested against each other).
+
+    Inputs: data set i of a model with recording Y (T, N) and regressors X (T, N, B) as add_data stored them; the model's current state; a
+    sorted list `free` of F distinct neuron indices n_0 < ... < n_{F-1}, every other neuron being clamped to the recording; a window
+    [start, stop) of the recording's bins.
+      Wm          = (a*W).reshape(N, N*B), the activation of `means` and simulate()
+      base[t, j]  = bias[n_j] + sum_{m clamped} sum_b Wm[n_j, m*B + b] X[t, m, b]   for t in the window: engine.psi on the current state with the
+                    free COLUMNS of the adjacency set to zero, columns `free` of the result (gathered as `means` gathers on a sharded model).
+                    base is an INPUT of the serial law: this function and the kernel receive the same array (T', F), row 0 = bin t0 = start
+      Wff[j, k*B + b] = Wm[n_j, n_k*B + b]                                            the free block, (F, F*B)
+      x_r[t][k, b]    = sum_l y_r[t-1-l, n_k] basis[l, b]
+      psi_r[t, j]     = base[t, j] + Wff[j, :] . x_r[t]
+      y_r[t, n_j]     ~ neuron n_j's own model at psi_r[t, j], by host_draw / sim_draw exactly as in THE LAW of simulate: kind / par (F,) are
+                    those of the free neurons
+      history     the free neurons' bins before `start` are the recording's own rows Y[start-L:start, free], silence before bin 0 (the
+                    convention of convolve_with_basis): hist (R, L, F) in time order
+      stream      that of simulate: PURPOSE_SIM, stream = (replicate << 32) | n_j with the GLOBAL neuron index, element = the bin's index in the
+                    recording, call 0.  A free neuron sees the uniforms it sees in simulate(seed, replicate); path r depends on (seed, r, state,
+                    recording, free, window) and not on R or on the chunking
+    With every neuron free and start = 0, base is the bias and this is simulate_host from silence: the array expressions below are that
+    function's, so the bits are too.
+    -> ConditionalSimulation (free = `neuron`); want_psi: True keeps psi (R, T', F); a callable f(psi_block (R, n, F), k0) is fed the
+    activations of bins k0 .. k0 + n - 1 of the window block by block instead"""
+    Wff = np.ascontiguousarray(Wff, dtype=np.float64)
+    F = Wff.shape[0]
+    L, B = basis.shape
+    WffT = np.ascontiguousarray(Wff.T)
+    base = np.asarray(base, dtype=np.float64)
+    T = base.shape[0]
+    C = T if keep_paths else min(T, HOST_BLOCK_BINS)
+    buf = np.zeros((R, L + C, F))
+    buf[:, :L] = hist
+    s, ss = np.zeros((R, F)), np.zeros((R, F))
+    fold = want_psi if callable(want_psi) else None
+    P = np.empty((R, T if want_psi is True else C, F)) if want_psi else None
+    neurons, reps = np.asarray(neuron, dtype=np.int64), rep0 + np.arange(R)
+    pos, k0 = L, 0                                   # buf[:, pos] receives bin t; k0: the window row of buf[:, L]
+    for t in range(t0, t0 + T):
+        if pos == L + C:
+            if fold:
+                fold(P, k0)
+            buf[:, :L] = buf[:, C:].copy()
+            pos, k0 = L, t - t0
+        x = np.einsum("rlm,lb->rmb", buf[:, pos - L:pos][:, ::-1], basis)
+        psi = x.reshape(R, F * B).dot(WffT) + base[t - t0]
+        u1, u2 = sim_uniforms(seed, t, neurons, reps)
+        y, capped = host_draw(kind, par, psi, u1, u2)
+        if capped is not None:
+            _raise_cap(t, rep0 + capped[0], int(neurons[capped[1]]))
+        buf[:, pos] = y
+        if want_psi:
+            P[:, t - t0 if want_psi is True else pos - L] = psi
+        s += y
+        ss += y * y
+        pos += 1
+    if fold and pos > L:
+        fold(P[:, :pos - L], k0)
+    return ConditionalSimulation(neurons, buf[:, L:L + T].copy() if keep_paths else None, s, ss, buf[:, pos - L:pos].copy(), base, t0, t0 + T,
+                                 seed, rep0, psi=P if want_psi is True else None)
+
+
+def conditional_device(Wff, base, basis, kind, par, neuron, R, seed, rep0, hist, t0, keep_paths, device=None, chunk=None, want_psi=False):
+    """THE CONDITIONAL LAW through pgl_conditional_simulate, a chunk of bins per launch (chunk: its length, default cond_chunk_bins)
+    -> ConditionalSimulation.  A callable want_psi is fed device tensors."""
+    import torch
+    dev, st = _device("conditional_simulate", device)
+    F = np.shape(Wff)[0]
+    L, B = np.shape(basis)
+    T = np.shape(base)[0]
+    if F * B > COND_MAX_X:
+        raise ValueError("conditional_simulate(): %d free neurons x %d basis functions = %d; the device path holds at most %d" % (F, B, F * B, COND_MAX_X))
+    Tc = min(T, int(chunk) if chunk else cond_chunk_bins(F, R))
+    fold = want_psi if callable(want_psi) else None
+    with torch.cuda.device(dev):
+        f64 = dict(dtype=torch.float64, device=dev)
+        need = 8 * F * (T + R * T * bool(keep_paths) + R * (T if want_psi is True else Tc if want_psi else 0))
+        free = torch.cuda.mem_get_info(dev)[0]
+        if need > free:
+            raise PglError("conditional_simulate(): base, the paths and the activations of %d replicates x %d bins x %d free neurons need %d bytes "
+                           "of device memory, %d are free: simulate fewer replicates or bins per call, or pass keep_paths=False" % (R, T, F, need, free))
+        Wff_d, base_d, basis_d = (torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(dev) for v in (Wff, base, basis))
+        kind_d = torch.from_numpy(np.ascontiguousarray(kind, dtype=np.int32)).to(dev)
+        par_d = torch.from_numpy(np.ascontiguousarray(par, dtype=np.float64)).to(dev)
+        neuron_d = torch.from_numpy(np.ascontiguousarray(neuron, dtype=np.int32)).to(dev)
+        rows = (t0 - L + np.arange(L)) % L               # ring row t mod L = Y[t]
+        ring_h = np.empty((R, L, F))
+        ring_h[:, rows] = hist
+        ring = torch.from_numpy(ring_h).to(dev)
+        Y_d = torch.empty((R, T, F), **f64) if keep_paths else None
+        P_d = torch.empty((R, T if want_psi is True else Tc, F), **f64) if want_psi else None
+        sum_d, sq_d = torch.zeros((R, F), **f64), torch.zeros((R, F), **f64)
+        status = torch.zeros(4, dtype=torch.int32, device=dev)
+        status_h = torch.zeros(4, dtype=torch.int32).pin_memory()
+        for k0 in range(0, T, Tc):
+            n = min(Tc, T - k0)
+            yout, ldr = (Y_d[0, k0:], T * F) if keep_paths else (None, 0)
+            pout, ldp = (P_d[0, k0:], T * F) if want_psi is True else (P_d, Tc * F) if want_psi else (None, 0)
+            call("pgl_conditional_simulate", ptr(Wff_d), ptr(base_d[k0:]), F, ptr(basis_d), F, B, L, ptr(kind_d), ptr(par_d), ptr(neuron_d), R, rep0,
+                 seed & (2 ** 64 - 1), ptr(ring), ptr(yout), ldr, ptr(pout), ldp, ptr(sum_d), ptr(sq_d), t0 + k0, n, ptr(status), st)
+            _finish_launch("pgl_conditional_simulate", dev, status, status_h, t0 + k0, t0 + k0 + n - 1)
+            if fold:
+                fold(P_d[:, :n], k0)
+        rows = (t0 + T - L + np.arange(L)) % L
+        return ConditionalSimulation(np.asarray(neuron, dtype=np.int64), Y_d.cpu().numpy() if keep_paths else None, sum_d.cpu().numpy(),
+                                     sq_d.cpu().numpy(), ring.cpu().numpy()[:, rows], np.asarray(base, dtype=np.float64), t0, t0 + T, seed, rep0,
+                                     psi=P_d.cpu().numpy() if want_psi is True else None)
+
+
+def conditional_simulate(Wff, base, basis, kind, par, neuron, R, seed, rep0, hist, t0, keep_paths, on_device, device, chunk=None, want_psi=False):
+    """R replicates of the free neurons `neuron` (F,) over the T' = len(base) bins from t0 under THE CONDITIONAL LAW (conditional_host states
+    it) -> ConditionalSimulation; on the device (pgl_conditional_simulate) or in NumPy.  What model.conditional_simulate() calls once it has
+    read the model: Wff (F, F*B), base (T', F), basis (L, B), kind / par (F,) of the free neurons, hist (R, L, F) or (L, F), their L bins
+    before t0 in time order."""
+    Wff, base, basis = (np.asarray(v, dtype=np.float64) for v in (Wff, base, basis))
+    neuron = np.asarray(neuron, dtype=np.int64)
+    F, (L, B) = neuron.size, basis.shape
+    R, rep0, seed, t0 = int(R), int(rep0), int(seed), int(t0)
+    if not 1 <= F <= PGL_COND_MAX_FREE or Wff.shape != (F, F * B) or base.ndim != 2 or base.shape[1] != F:
+        raise ValueError("conditional_simulate(): 1 <= F <= %d free neurons, Wff (F, F*B) and base (T', F) are required, got F = %d, Wff %r, base %r"
+                         % (PGL_COND_MAX_FREE, F, Wff.shape, base.shape))
+    if R < 1 or rep0 < 0 or t0 < 0 or not 0 <= seed < 2 ** 64:
+        raise ValueError("conditional_simulate(): replicates >= 1, first_replicate >= 0, t0 >= 0 and 0 <= seed < 2^64 are required")
+    T = base.shape[0]
+    if t0 + T >= 2 ** 31 or rep0 + R >= 2 ** 31 or (neuron.size and neuron.max() >= 2 ** 31):
+        raise ValueError("conditional_simulate(): time bins, replicate and neuron indices must stay below 2^31")
+    kind, par = np.asarray(kind, dtype=np.int32), np.asarray(par, dtype=np.float64)
+    hist = np.array(np.broadcast_to(np.asarray(hist, dtype=np.float64), (R, L, F)))
+    if T == 0:
+        return ConditionalSimulation(neuron, np.zeros((R, 0, F)) if keep_paths else None, np.zeros((R, F)), np.zeros((R, F)), hist, base, t0, t0,
+                                     seed, rep0, psi=np.zeros((R, 0, F)) if want_psi is True else None)
+    if on_device:
+        return conditional_device(Wff, base, basis, kind, par, neuron, R, seed, rep0, hist, t0, keep_paths, device=device, chunk=chunk, want_psi=want_psi)
+    return conditional_host(Wff, base, basis, kind, par, neuron, R, seed, rep0, hist, t0, keep_paths, want_psi=want_psi)
+
+
+class ConditionalPrediction(object):
+    """Population-conditioned prediction of the free neurons of one data set (model.conditional_check()), in the pattern of PredictiveCheck:
+
+        cp = model.conditional_check(free=[3, 7], replicates=8, seed=0)
+        for it in range(n_sweeps):
+            model.resample_model()
+            if it >= burn:
+                cp.collect()
+        cp.rate_mean, cp.rate_std, cp.log_score()
+
+    collect() simulates `replicates` fresh conditional replicates over the window from the model's current state (the k-th call uses replicate
+    indices k R ... k R + R - 1) and folds, per cell (t, j) of the window and one replicate after the other, a Welford mean / M2 of the rate
+    E[y | psi_r[t, j]] -- by the neuron's own link, as regression.means_of_psi -- and a streaming log-sum-exp (m, s), as in summary.py, of
+    l_r = log p(Y[t, n_j] | psi_r[t, j]): logC + a psi - b log1p(e^psi) with the terms of regression.obs_terms for the Polya-gamma models,
+    -1/2 log(2 pi eta) - (y - psi)^2 / (2 eta) for Gaussian neurons.  The accumulators live where the simulation ran: torch tensors on the
+    device, folded elementwise from every launch's activations, else NumPy.  It changes nothing in the chain."""
+
+    def __init__(self, model, free, replicates=8, seed=0, data=0, start=0, stop=None, gpu=None):
+        self.model, self.R, self.seed, self.gpu = model, int(replicates), int(seed), gpu
+        self.data = range(len(model.data_list))[data]
+        Y = np.asarray(model.data_list[self.data][1], dtype=np.float64)
+        self.free = check_free(free, model.N)
+        self.t0, self.t1 = check_window(start, stop, Y.shape[0])
+        if self.R < 1:
+            raise ValueError("conditional_check(): replicates >= 1 is required")
+        regs = [model.regressions[n] for n in self.free]
+        models = observation_models(regs)
+        self._link = np.array([m.link for m in models], dtype=np.int64)
+        self._link_par = np.array([m.par(r) for m, r in zip(models, regs)], dtype=np.float64)
+        Yw = Y[self.t0:self.t1][:, self.free]
+        self._gauss = models[0].sim_kind == KIND_GAUSSIAN
+        if self._gauss:
+            self._terms = (Yw, np.array([float(r.eta) for r in regs]))
+        else:
+            self._terms = _reg.obs_terms(regs, Yw)
+        self.calls = self.count = 0
+        self._acc = None                         # [rate mean, rate M2, lse m, lse s], each (T', F), where the simulations run
+        self._consts = None                      # link masks, parameters and the terms of l, on the accumulators' side
+
+    def _setup(self, like):
+        shape = (self.t1 - self.t0, self.free.size)
+        if isinstance(like, np.ndarray):
+            conv, zeros = (lambda v: np.asarray(v)), (lambda: np.zeros(shape))
+        else:
+            import torch
+            conv, zeros = (lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(like.device)), (lambda: torch.zeros(shape, dtype=torch.float64, device=like.device))
+        self._acc = [zeros() for _ in range(4)]
+        self._consts = dict(link=[conv(self._link == c) for c in range(4)], par=conv(self._link_par), terms=tuple(conv(v) for v in self._terms))
+
+    def _fold(self, psi, k0):
+        """psi (R, n, F): the activations of window rows k0 .. k0 + n - 1 of this call's R replicates"""
+        xp = np
+        if not isinstance(psi, np.ndarray):
+            import torch
+            xp = torch
+        if self._acc is None:
+            self._setup(psi)
+        n = psi.shape[1]
+        mean, M2, lm, ls = (v[k0:k0 + n] for v in self._acc)
+        link, par = self._consts["link"], self._consts["par"]
+        terms = tuple(v[k0:k0 + n] if v.ndim == 2 else v for v in self._consts["terms"])
+        for r in range(psi.shape[0]):            # one replicate at a time: Welford's order
+            p = psi[r]
+            k = self.count + r + 1
+            lg = 1.0 / (1.0 + xp.exp(-p))
+            rate = xp.where(link[0], lg, xp.where(link[1], p, xp.where(link[2], par * xp.exp(p), par * lg)))
+            d = rate - mean
+            mean += d / k
+            M2 += d * (rate - mean)
+            if self._gauss:
+                y, eta = terms
+                l = -0.5 * xp.log(2 * np.pi * eta) - (y - p) ** 2 / (2 * eta)
+            else:
+                A, Bv, logC = terms
+                l = logC + A * p - Bv * xp.log1p(xp.exp(p))
+            if k == 1:
+                lm[...] = l
+                ls[...] = 1.0
+            else:
+                m1 = xp.maximum(lm, l)
+                ls[...] = ls * xp.exp(lm - m1) + xp.exp(l - m1)
+                lm[...] = m1
+
+    def collect(self):
+        inp = self.model._conditional_inputs(self.free, self.data, self.t0, self.t1)
+        conditional_simulate(inp["Wff"], inp["base"], inp["basis"], inp["kind"], inp["par"], self.free, self.R, self.seed, self.calls * self.R,
+                             inp["hist"], self.t0, False, self.model._on_gpu(self.gpu, "conditional_check"), self.model._device, want_psi=self._fold)
+        self.calls += 1
+        self.count += self.R
+
+    def _state(self):
+        if self._acc is None:
+            raise ValueError("conditional_check(): the read-outs need at least one collect()")
+        return [v if isinstance(v, np.ndarray) else v.cpu().numpy() for v in self._acc]
+
+    @property
+    def rate_mean(self):
+        """mean over the S R replicates folded so far of E[y | psi_r], (T', F)"""
+        return self._state()[0].copy()
+
+    @property
+    def rate_std(self):
+        """its standard deviation, sqrt(M2 / (S R)), (T', F)"""
+        return np.sqrt(self._state()[1] / self.count)
+
+    def log_score(self):
+        """the conditional log predictive score of the recording: dict(total, per_neuron (F,), per_bin (T', F)), per_bin = logsumexp_r l_r -
+        log(S R)"""
+        _, _, lm, ls = self._state()
+        per_bin = lm + np.log(ls) - np.log(self.count)
+        return dict(total=float(per_bin.sum()), per_neuron=per_bin.sum(axis=0), per_bin=per_bin)
