@@ -1,128 +1,94 @@
-"""ctypes binding of libpyglm_hip.so (C ABI: include/pyglm_hip.h). Fails loudly when the library is absent."""
+"""ctypes binding of libpyglm_hip.so, derived at import from the one statement of its C ABI, include/pyglm_hip.h: argument and return types,
+parameter names, struct layouts and constants. Fails loudly when the library is absent, and when the header holds a declaration the
+parser below cannot classify completely."""
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libpyglm_hip.so")
-
-c_p, c_l, c_i, c_d, c_u64, c_u32, c_sz = (ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_double,
-                                          ctypes.c_uint64, ctypes.c_uint32, ctypes.c_size_t)
-
-
-class FlipState(ctypes.Structure):   # pgl_flip_t
-    _fields_ = [("M", c_p), ("ldj", c_l), ("strideM", c_l), ("nb", c_i), ("N", c_i), ("B", c_i),
-                ("perm", c_p), ("u", c_p), ("rho", c_p), ("c0", c_p), ("a", c_p), ("skip", c_p),
-                ("d_idx", c_p), ("d_sign", c_p), ("d_cnt", c_p), ("batch_k", c_p), ("G", c_p), ("Lws", c_p),
-                ("Ut", c_p), ("Wt", c_p), ("ldu", c_l), ("status", c_p), ("visit_order", c_i), ("logodds", c_p)]
-
-
-class CholState(ctypes.Structure):   # pgl_chol_t
-    _fields_ = [("J", c_p), ("ldj", c_l), ("strideJ", c_l), ("a", c_p), ("act", c_p), ("ldact", c_l), ("na", c_p),
-                ("Ac", c_p), ("ldc", c_l), ("strideC", c_l), ("hc", c_p), ("Tinv", c_p), ("z", c_p), ("ldz", c_l),
-                ("W", c_p), ("b", c_p), ("nb", c_i), ("N", c_i), ("B", c_i), ("status", c_p)]
-
-
-class Dataset(ctypes.Structure):     # pgl_dataset_t
-    _fields_ = [("T", c_i), ("Tp", c_i), ("X", c_p), ("Xt", c_p), ("Y", c_p), ("Psi", c_p), ("OK", c_p), ("llpart", c_p), ("elem0", c_u64),
-                ("int8", c_i), ("planes", c_i), ("sA", c_p), ("PA", c_p), ("omega_override", c_p), ("xmax", c_p),
-                ("hooks", c_p)]
-
-
-NSTAGES = 16
-
-
-class StageTimes(ctypes.Structure):  # pgl_stage_times_t
-    _fields_ = [("ms", c_d * NSTAGES), ("work", c_d * NSTAGES), ("calls", c_i * NSTAGES), ("pending", c_p), ("mask", c_u32)]
-
-
-class Sweep(ctypes.Structure):       # pgl_sweep_t
-    _fields_ = [("N", c_i), ("B", c_i), ("n0", c_i), ("nloc", c_i), ("nb", c_i), ("obs", c_i), ("xi", c_d), ("visit_order", c_i),
-                ("planes", c_i), ("i8_group", c_i), ("datasets", ctypes.POINTER(Dataset)), ("ndatasets", c_i),
-                ("a", c_p), ("W", c_p), ("b", c_p), ("rho", c_p), ("Jw", c_p), ("hw", c_p), ("label", c_p), ("Jb", c_p), ("hb", c_p), ("c0", c_p),
-                ("perm", c_p), ("u", c_p), ("z", c_p), ("inv_eta", c_p), ("G0", c_p), ("ll", c_p), ("status", c_p), ("logodds", c_p),
-                ("Wt", c_p), ("bias", c_p), ("border", c_p), ("skip", c_p), ("c0_dense", c_p),
-                ("Jbuf", c_p), ("Mtab", c_p), ("Ac", c_p), ("hc", c_p), ("Tinv", c_p), ("G", c_p), ("Lws", c_p), ("Ut", c_p), ("Wt_ws", c_p),
-                ("d_idx", c_p), ("d_sign", c_p), ("d_cnt", c_p), ("batch_k", c_p), ("act", c_p), ("na", c_p),
-                ("i8_PB", c_p), ("i8_R", c_p), ("i8_stat", c_p), ("i8_slice", c_i), ("i8_PAs", c_p), ("i8_Rx", c_p), ("i8_norm", c_p), ("nrun", c_i), ("nfirst", c_i),
-                ("all_deterministic", c_i), ("init_rows_bound", c_i), ("active_rows_bound", c_i), ("flip_single_pass", c_i),
-                ("times", ctypes.POINTER(StageTimes)), ("obs_param", c_p)]
-
-
-# symbol -> argument types; every function returns int status unless noted. Mirrors include/pyglm_hip.h 1:1.
-SIGNATURES = {
-    "pgl_abi_version": [],
-    "pgl_last_error": [],
-    "pgl_philox_words": [c_u64, c_u32, c_u32, c_u64, c_u64, c_p, c_sz, c_p],
-    "pgl_pg_draw": [c_p, c_p, c_p, c_sz, c_u64, c_u64, c_u64, c_p],
-    "pgl_design_matrix": [c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_p],
-    "pgl_transpose": [c_p, c_l, c_p, c_l, c_i, c_i, c_p],
-    "pgl_activation": [c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_i, c_i, c_p],
-    "pgl_pg_loglik": [c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_p, c_i, c_i, c_i, c_i, c_d, c_u64, c_u64, c_u64, c_u64, c_p],
-    "pgl_pg_loglik_partials": [c_i],
-    "pgl_pg_loglik_ex": [c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_p, c_i, c_i, c_i, c_i, c_d, c_p, c_p, c_l, c_u64, c_u64, c_u64, c_u64, c_p],
-    "pgl_gaussian_stats": [c_p, c_l, c_p, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p, c_p, c_i, c_i, c_i, c_p],
-    "pgl_scaled_gram": [c_p, c_l, c_p, c_p, c_l, c_l, c_i, c_i, c_p],
-    "pgl_weighted_gram": [c_p, c_l, c_i, c_p, c_l, c_i, c_i, c_i, c_p, c_l, c_l, c_i, c_p],
-    "pgl_i8_plane_bytes": [c_i, c_i],
-    "pgl_i8_residue_bytes": [c_i],
-    "pgl_i8_max_planes": [],
-    "pgl_i8_padded_rows": [c_i],
-    "pgl_i8_min_planes": [c_i],
-    "pgl_i8_norm_bits": [c_i, c_i],
-    "pgl_i8_norm_limit": [c_i, c_i],
-    "pgl_i8_colstats": [c_p, c_l, c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_p],
-    "pgl_i8_scales": [c_p, c_p, c_l, c_i, c_i, c_p, c_p],
-    "pgl_i8_planes": [c_p, c_l, c_p, c_l, c_p, c_p, c_i, c_i, c_i, c_i, c_l, c_p],
-    "pgl_i8_planes_t": [c_p, c_l, c_p, c_l, c_p, c_p, c_i, c_i, c_i, c_i, c_l, c_p],
-    "pgl_i8_gram": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
-    "pgl_i8_gram_slice": [c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
-    "pgl_i8_crt": [c_p, c_p, c_p, c_p, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_p],
-    "pgl_contract_tn": [c_p, c_l, c_i, c_p, c_l, c_i, c_p, c_l, c_i, c_i, c_i, c_d, c_d, c_p],
-    "pgl_contract_tn_batched": [c_p, c_l, c_l, c_i, c_p, c_l, c_l, c_i, c_p, c_l, c_l, c_i, c_i, c_i, c_i, c_p, c_d, c_d, c_i, c_i, c_p],
-    "pgl_assemble_posterior": [c_p, c_l, c_l, c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
-    "pgl_flip_kmax": [],
-    "pgl_flip_window_blocks": [c_i],
-    "pgl_flip_apply": [ctypes.POINTER(FlipState), c_p],
-    "pgl_flip_apply_chunk": [ctypes.POINTER(FlipState), c_i, c_p],
-    "pgl_flip_apply_window": [ctypes.POINTER(FlipState), c_i, c_p],
-    "pgl_flip_visit_order": [ctypes.POINTER(FlipState), c_p, c_l, c_l, c_p],
-    "pgl_flip_decide": [ctypes.POINTER(FlipState), c_i, c_p],
-    "pgl_row_stats": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
-    "pgl_sweep_dims": [c_i, c_i, c_i, ctypes.POINTER(c_i), ctypes.POINTER(c_i), ctypes.POINTER(c_i)],
-    "pgl_sweep": [ctypes.POINTER(Sweep), c_u64, c_u64, c_p],
-    "pgl_sweep_gram": [ctypes.POINTER(Sweep), c_i, c_i, c_p],
-    "pgl_get_state": [ctypes.POINTER(Sweep), c_p, c_p, c_p, c_p, c_p, c_p],
-    "pgl_stage_name": [c_i],
-    "pgl_stage_times_collect": [ctypes.POINTER(StageTimes)],
-    "pgl_active_index": [ctypes.POINTER(CholState), c_p],
-    "pgl_sample_weights": [ctypes.POINTER(CholState), c_i, c_p],
-    "pgl_ubench_mfma": [c_i, c_d, ctypes.POINTER(c_d), ctypes.POINTER(c_d), c_p],
-    "pgl_generate_work_bytes": [c_i, c_i],
-    "pgl_summary_fold": [c_p, c_l, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_d, c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_i, c_p, c_d, c_p, c_p, c_p, c_p, c_i, c_p],
-    "pgl_summary_state": [c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
-    "pgl_summary_colsum": [c_p, c_l, c_i, c_i, c_p, c_p, c_i, c_p],
-    "pgl_generate": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_d, c_p, c_p, c_p, c_l, c_i, c_p, c_p, c_p],
-    "pgl_simulate_work_bytes": [c_i, c_i, c_i],
-    "pgl_simulate": [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_l, c_u64, c_p, c_p, c_l, c_p, c_p, c_l, c_i, c_p, c_p, c_p],
-    "pgl_conditional_max_free": [],
-    "pgl_conditional_simulate": [c_p, c_p, c_l, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_l, c_u64, c_p, c_p, c_l, c_p, c_l, c_p, c_p, c_l, c_i, c_p, c_p],
-    "pgl_lagged_work_bytes": [c_i, c_i, c_i, c_i],
-    "pgl_lagged_products": [c_p, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_p, c_l, c_i, c_i, c_p, c_p, c_p],
-    "pgl_isi_segment_rows": [],
-    "pgl_isi_work_bytes": [c_i, c_i, c_i],
-    "pgl_isi_fold": [c_p, c_l, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p],
-    "pgl_rescale_segment_rows": [],
-    "pgl_rescale_work_bytes": [c_i, c_i],
-    "pgl_rescale_fold": [c_p, c_l, c_p, c_p, c_i, c_i, c_p, c_d, c_i, c_u64, c_u32, c_u64, c_u64, c_p, c_p, c_i, c_p, c_p],
-    "pgl_rescale_ks": [c_p, c_i, c_i, c_d, c_p, c_p, c_p, c_p, c_p, c_i, c_p],
-}
-
-ABI_VERSION = 11
-_lib = None
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip.h")
 
 
 class PglError(RuntimeError):
     pass
+
+
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "long long": ctypes.c_longlong, "unsigned int": ctypes.c_uint,
+            "unsigned long long": ctypes.c_ulonglong, "double": ctypes.c_double, "size_t": ctypes.c_size_t, "uint32_t": ctypes.c_uint32,
+            "uint64_t": ctypes.c_uint64}
+_TYPE_WORDS = {w for t in _SCALARS for w in t.split()} | {"const", "void", "char"}
+_CLASS_NAMES = {"pgl_flip_t": "FlipState", "pgl_chol_t": "CholState", "pgl_dataset_t": "Dataset", "pgl_stage_times_t": "StageTimes",
+                "pgl_sweep_t": "Sweep"}
+
+
+def parse_header(text):
+    """The declarations of a C header in the header's own regular style -> (constants {name: int}, structs {typedef name: ctypes.Structure
+    class}, functions {name: (restype, [(parameter name, ctypes type), ...])}). A pointer to a struct typedef of the header is POINTER(its
+    class), every other pointer c_void_p. Raises PglError, naming the declaration, on whatever it cannot classify: no default type."""
+    consts, structs, funcs = {}, {}, {}
+
+    def directive(m):    # '#define PGL_<NAME> <integer>' is a constant and a define without a value an include guard; other directives drop out
+        d = re.fullmatch(r"define\s+(\w+)(?:\s+(.*\S))?\s*", m.group(1))
+        if d and d.group(2) is not None:
+            if not (d.group(1).startswith("PGL_") and re.fullmatch(r"-?\d+", d.group(2))):
+                raise PglError("pyglm_hip.h: '#%s' does not define an integer PGL_ constant" % m.group(1).strip())
+            consts[d.group(1)] = int(d.group(2))
+        return ""
+
+    def ctype(spec, decl):
+        words = spec.replace("*", " * ").split()
+        base, stars = " ".join(w for w in words if w not in ("const", "*")), words.count("*")
+        if stars == 0 and base in _SCALARS:
+            return _SCALARS[base]
+        if stars == 1 and base in structs:
+            return ctypes.POINTER(structs[base])
+        if stars == 1 and (base in _SCALARS or base == "void"):
+            return ctypes.c_void_p
+        raise PglError("pyglm_hip.h: unknown type '%s' in: %s" % (spec.strip(), decl))
+
+    def named(spec, decl):    # 'type name' or 'type name[DIM]' -> (type text, name, ctypes type)
+        m = re.fullmatch(r"(.*[\s*])(\w+)\s*(?:\[\s*(\w+)\s*\])?", spec.strip(), flags=re.S)
+        if not m or m.group(2) in _TYPE_WORDS:
+            raise PglError("pyglm_hip.h: no name for '%s' in: %s" % (spec.strip(), decl))
+        t, dim = ctype(m.group(1), decl), m.group(3)
+        if dim is not None and not (dim.isdigit() or dim in consts):
+            raise PglError("pyglm_hip.h: unknown array size '%s' in: %s" % (dim, decl))
+        return m.group(1), m.group(2), t if dim is None else t * (int(dim) if dim.isdigit() else consts[dim])
+
+    def struct(m):
+        fields = []
+        for decl in filter(None, (" ".join(d.split()) for d in m.group(1).split(";"))):
+            first, *more = decl.split(",")
+            spec, name, t = named(first, decl)
+            if more and "*" in spec:
+                raise PglError("pyglm_hip.h: several declarators after a pointer type in: %s" % decl)
+            fields += [(name, t)] + [named(spec + d, decl)[1:] for d in more]
+        structs[m.group(2)] = type(_CLASS_NAMES.get(m.group(2), m.group(2)), (ctypes.Structure,), {"_fields_": fields})
+        return ""
+
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#[ \t]*(.*)$", directive, text, flags=re.M)
+    text = re.sub(r'\A\s*extern\s+"C"\s*\{(.*)\}\s*\Z', r"\1", text, flags=re.S)
+    text = re.sub(r"\btypedef\s+struct\s*\{([^{}]*)\}\s*(\w+)\s*;", struct, text)
+    for decl in filter(None, (" ".join(d.split()) for d in text.split(";"))):
+        m = re.fullmatch(r"(.*[\s*])(\w+)\s*\((.*)\)", decl)
+        if not m:
+            raise PglError("pyglm_hip.h: text that is no declaration: %s" % decl)
+        ret, name, params = m.groups()
+        restype = ctypes.c_char_p if ret.replace("*", " * ").split() == ["const", "char", "*"] else ctype(ret, decl)
+        funcs[name] = (restype, [] if params.strip() == "void" else [named(p, decl)[1:] for p in params.split(",")])
+    return consts, structs, funcs
+
+
+with open(HEADER) as _fh:
+    CONSTANTS, _structs, FUNCTIONS = parse_header(_fh.read())
+globals().update(CONSTANTS)                                       # PGL_LAG_MAX, PGL_ISI_MAX_BINS, ...: every integer #define of the header
+ABI_VERSION, NSTAGES = CONSTANTS["PGL_ABI_VERSION"], CONSTANTS["PGL_NSTAGES"]
+FlipState, CholState, Dataset, StageTimes, Sweep = (_structs[c] for c in _CLASS_NAMES)
+SIGNATURES = {f: [t for _, t in params] for f, (_, params) in FUNCTIONS.items()}    # symbol -> argument types
+PARAMS = {f: [p for p, _ in params] for f, (_, params) in FUNCTIONS.items()}        # symbol -> parameter names, in the header's order
+_lib = None
 
 
 def load():
@@ -137,11 +103,10 @@ def load():
     #                      dependency on libamdhip64 has to resolve to the copy torch has loaded (loading the library first leaves
     #                      two runtimes in the process: "no ROCm-capable device is detected" at the first launch)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, args in SIGNATURES.items():
+    for name, (restype, _) in FUNCTIONS.items():
         fn = getattr(lib, name)     # AttributeError if the export is missing
-        fn.argtypes = args
-        fn.restype = (ctypes.c_char_p if name in ("pgl_last_error", "pgl_stage_name") else ctypes.c_size_t if name in ("pgl_i8_plane_bytes", "pgl_i8_residue_bytes", "pgl_generate_work_bytes", "pgl_simulate_work_bytes", "pgl_lagged_work_bytes", "pgl_isi_work_bytes", "pgl_rescale_work_bytes")
-                      else ctypes.c_double if name == "pgl_i8_norm_limit" else ctypes.c_int)
+        fn.argtypes = SIGNATURES[name]
+        fn.restype = restype
     if lib.pgl_abi_version() != ABI_VERSION:
         raise PglError("libpyglm_hip.so ABI version %d != %d (rebuild: make -C pyglm_amd/csrc)" % (lib.pgl_abi_version(), ABI_VERSION))
     _lib = lib
@@ -164,7 +129,17 @@ def source_hash():
     return h.hexdigest()[:16]
 
 
-def call(name, *args):
+def call(name, *args, **by_name):
+    """name(*args), or name(**by_name) with the keywords put in the order of the header's parameter names; raises PglError on a non-zero status"""
+    if by_name:
+        names = PARAMS[name]
+        if args:
+            raise TypeError("%s: positional values mixed with keyword '%s'" % (name, next(iter(by_name))))
+        missing = [k for k in names if k not in by_name]
+        if missing or len(by_name) != len(names):
+            unknown = [k for k in by_name if k not in names]
+            raise TypeError("%s %s '%s'" % (name, "has no parameter" if unknown else "is missing parameter", (unknown or missing)[0]))
+        args = [by_name[k] for k in names]
     lib = load()
     rc = getattr(lib, name)(*args)
     if rc != 0:

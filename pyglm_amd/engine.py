@@ -390,7 +390,8 @@ class GibbsEngine(object):
             clip = int(basis.min() >= 0 and Y.min() >= 0)
             S_dev = torch.from_numpy(Y).to(self.dev)
             b_dev = torch.from_numpy(basis).to(self.dev)
-            call("pgl_design_matrix", ptr(S_dev), self.N, ptr(b_dev), ptr(ds.X), self.Dp, ptr(ds.Xt), ds.Tp, T, self.N, self.B, R, clip, st)
+            call("pgl_design_matrix", S=ptr(S_dev), lds=self.N, basis=ptr(b_dev), X=ptr(ds.X), ldx=self.Dp, Xt=ptr(ds.Xt), ldxt=ds.Tp, T=T,
+                 N=self.N, B=self.B, R=R, clip=clip, hip_stream=st)
             torch.cuda.synchronize(self.dev)
         else:
             X = np.ascontiguousarray(X, dtype=np.float64).reshape(T, self.D)
@@ -427,7 +428,8 @@ class GibbsEngine(object):
             ds.planes = plan["planes"]
             stat = self._z(2, self.D)
             ds.sA = self._z(self.D)
-            call("pgl_i8_colstats", ptr(ds.X), self.Dp, None, 0, T, self.D, 1, ptr(stat[0]), ptr(stat[1]), st)
+            call("pgl_i8_colstats", X=ptr(ds.X), ldx=self.Dp, Om=None, ldo=0, T=T, D=self.D, G=1, amax=ptr(stat[0]), sumsq=ptr(stat[1]),
+                 hip_stream=st)
             call("pgl_i8_scales", ptr(stat[0]), ptr(stat[1]), self.D, T, ds.planes, ptr(ds.sA), st)
             ds.xmax = stat[0]               # column maxima of X: with _i8_norm, the sweep takes the norms of omega_n X per batch (pgl_sweep_t.i8_norm)
             if self._i8_norm is None:
@@ -435,14 +437,15 @@ class GibbsEngine(object):
             ds.PA = None
             if plan["resident"]:
                 ds.PA = torch.empty(lib.pgl_i8_plane_bytes(self.D, T) // lib.pgl_i8_max_planes() * ds.planes, dtype=torch.int8, device=self.dev)
-                call("pgl_i8_planes_t", ptr(ds.Xt), ds.Tp, None, 0, ptr(ds.sA), ptr(ds.PA), T, self.D, 1, ds.planes, 0, st)
+                call("pgl_i8_planes_t", Xt=ptr(ds.Xt), ldt=ds.Tp, Om=None, ldo=0, scale=ptr(ds.sA), planes=ptr(ds.PA), T=T, D=self.D, G=1,
+                     nplanes=ds.planes, t0=0, hip_stream=st)
             self._i8_reserve(T, plan)
             torch.cuda.synchronize(self.dev)
         if self.obs == OBS_GAUSSIAN:
             ones = self._z(ds.Tp, 2)
             ones[:T, 0] = 1.0
-            call("pgl_weighted_gram", ptr(ds.X), self.Dp, self.Dp, ptr(ones), 2, ds.Tp, self.D, 1, ptr(self.G0), self.ldj, self.ldj * self.ldj,
-                 int(len(self.datasets) > 1), st)
+            call("pgl_weighted_gram", X=ptr(ds.X), ldx=self.Dp, x_cols=self.Dp, W=ptr(ones), ldw=2, Tp=ds.Tp, D=self.D, nz=1, J=ptr(self.G0),
+                 ldj=self.ldj, strideJ=self.ldj * self.ldj, accumulate=int(len(self.datasets) > 1), hip_stream=st)
             torch.cuda.synchronize(self.dev)
         return ds
 
@@ -618,7 +621,8 @@ class GibbsEngine(object):
     def _activation(self, ds, st):
         """queues Psi = X (a * W)' of data set ds for the whole shard (regression.py:195-201; bias not added), as its own stage"""
         h = self._tic("activation", 2.0 * ds.T * self.D * self.nloc)
-        call("pgl_activation", ptr(ds.Xt), ds.Tp, ptr(self.Wt), self.ldn, ptr(ds.Psi), self.ldn, ds.T, self.Dp, self.nloc, st)
+        call("pgl_activation", Xt=ptr(ds.Xt), ldxt=ds.Tp, Wt=ptr(self.Wt), ldw=self.ldn, Psi=ptr(ds.Psi), ldpsi=self.ldn, T=ds.T, Dk=self.Dp,
+             nloc=self.nloc, hip_stream=st)
         self._toc(h)
 
     def _psi_pass(self, draw, seed, sweep):
@@ -630,12 +634,14 @@ class GibbsEngine(object):
             om = ds.OK if draw else None
             kp = ctypes.c_void_p(ds.OK.data_ptr() + 8 * self.ldn) if draw else None
             if self.obs == OBS_GAUSSIAN:      # self.ll then holds the sums of squared residuals
-                call("pgl_gaussian_stats", ptr(ds.Psi), self.ldn, ptr(self.bias), ptr(ds.Y), self.ldn, ptr(self.inv_eta), ptr(om), 2 * self.ldn,
-                     kp, 2 * self.ldn, ptr(ds.llpart), ptr(self.ll), int(i > 0), ds.T, self.nloc, st)
+                call("pgl_gaussian_stats", Psi=ptr(ds.Psi), ldpsi=self.ldn, bias=ptr(self.bias), Y=ptr(ds.Y), ldy=self.ldn, inv_eta=ptr(self.inv_eta),
+                     Omega=ptr(om), ldo=2 * self.ldn, Kappa=kp, ldk=2 * self.ldn, part=ptr(ds.llpart), sse_out=ptr(self.ll), accumulate=int(i > 0),
+                     T=ds.T, nloc=self.nloc, hip_stream=st)
             else:
-                call("pgl_pg_loglik_ex", ptr(ds.Psi), self.ldn, ptr(self.bias), ptr(ds.Y), self.ldn, ptr(om), 2 * self.ldn, kp, 2 * self.ldn,
-                     ptr(ds.llpart), ptr(self.ll), int(i > 0), ds.T, self.nloc, self.obs, self.xi, ptr(self.obs_param), ptr(ds.hooks), self.ldn,
-                     int(seed), int(sweep), self.n0, ds.elem0, st)
+                call("pgl_pg_loglik_ex", Psi=ptr(ds.Psi), ldpsi=self.ldn, bias=ptr(self.bias), Y=ptr(ds.Y), ldy=self.ldn, Omega=ptr(om),
+                     ldo=2 * self.ldn, Kappa=kp, ldk=2 * self.ldn, llpart=ptr(ds.llpart), ll_out=ptr(self.ll), accumulate=int(i > 0), T=ds.T,
+                     nloc=self.nloc, obs=self.obs, xi=self.xi, param=ptr(self.obs_param), hooks=ptr(ds.hooks), ldh=self.ldn, seed=int(seed),
+                     sweep=int(sweep), neuron0=self.n0, elem0=ds.elem0, hip_stream=st)
             self._toc(h)
         return self.ll
 
@@ -733,12 +739,14 @@ class GibbsEngine(object):
             self._activation(ds, st)
             h = self._tic("summary_fold", float(ds.T) * self.nloc)
             r, p = s.rate[i] if s.rate else none2, s.pw[i] if s.pw else none4
-            call("pgl_summary_fold", ptr(ds.Psi), self.ldn, ptr(self.bias), ptr(ds.Y), ptr(ds.llpart), ptr(self.ll), int(i > 0), ds.T, self.nloc,
-                 self.obs, self.xi, ptr(self.obs_param), ptr(ds.hooks), self.ldn, ptr(self.inv_eta) if self.obs == OBS_GAUSSIAN else None, ptr(r[0]), ptr(r[1]),
-                 ptr(s.link), s.link0, ptr(s.link_par), s.link_par0, ptr(p[0]), ptr(p[1]), ptr(p[2]), ptr(p[3]), int(k), st)
+            call("pgl_summary_fold", Psi=ptr(ds.Psi), ldn=self.ldn, bias=ptr(self.bias), Y=ptr(ds.Y), llpart=ptr(ds.llpart), ll_out=ptr(self.ll),
+                 accumulate=int(i > 0), T=ds.T, nloc=self.nloc, obs=self.obs, xi=self.xi, param=ptr(self.obs_param), hooks=ptr(ds.hooks),
+                 ldh=self.ldn, inv_eta=ptr(self.inv_eta) if self.obs == OBS_GAUSSIAN else None, rate_mean=ptr(r[0]), rate_M2=ptr(r[1]),
+                 link=ptr(s.link), link0=s.link0, link_par=ptr(s.link_par), link_par0=s.link_par0, l_mean=ptr(p[0]), l_M2=ptr(p[1]),
+                 lse_m=ptr(p[2]), lse_s=ptr(p[3]), k=int(k), hip_stream=st)
             self._toc(h)
-        call("pgl_summary_state", ptr(s.a), ptr(self.Wt), self.ldn, ptr(self.bias), ptr(s.edge), ptr(s.w[0]), ptr(s.w[1]), ptr(s.b[0]), ptr(s.b[1]),
-             self.N, self.B, self.nloc, int(k), st)
+        call("pgl_summary_state", a=ptr(s.a), Wt=ptr(self.Wt), ldw=self.ldn, bias=ptr(self.bias), edge=ptr(s.edge), w_mean=ptr(s.w[0]),
+             w_M2=ptr(s.w[1]), b_mean=ptr(s.b[0]), b_M2=ptr(s.b[1]), N=self.N, B=self.B, nloc=self.nloc, k=int(k), hip_stream=st)
         return self._ll_host(self.ll)
 
     @_on_device
@@ -823,11 +831,13 @@ class GibbsEngine(object):
                 continue
             self._activation(ds, st)
             h = self._tic("rescale_fold", float(ds.T) * self.nloc)
-            call("pgl_rescale_fold", ptr(ds.Psi), self.ldn, ptr(self.bias), ptr(ds.Y), ds.T, self.nloc, ptr(s.qpar), s.qpar0, s.D,
-                 int(seed) & (2 ** 64 - 1), (int(k) - 1) & 0xFFFFFFFF, self.n0, ds.elem0, ptr(s.hist), ptr(s.zsum), more, ptr(s.work), st)
+            call("pgl_rescale_fold", Psi=ptr(ds.Psi), ldn=self.ldn, bias=ptr(self.bias), Y=ptr(ds.Y), T=ds.T, nloc=self.nloc, qpar=ptr(s.qpar),
+                 qpar0=s.qpar0, D=s.D, seed=int(seed) & (2 ** 64 - 1), draw=(int(k) - 1) & 0xFFFFFFFF, neuron0=self.n0, elem0=ds.elem0,
+                 hist=ptr(s.hist), zsum=ptr(s.zsum), accumulate=more, work=ptr(s.work), hip_stream=st)
             self._toc(h)
             more = 1
-        call("pgl_rescale_ks", ptr(s.hist), self.nloc, s.D, s.coef, ptr(s.ks), ptr(s.ks_mean), ptr(s.ks_M2), ptr(s.exceed), ptr(s.hist_sum), int(k), st)
+        call("pgl_rescale_ks", hist=ptr(s.hist), nloc=self.nloc, D=s.D, coef=s.coef, ks=ptr(s.ks), ks_mean=ptr(s.ks_mean), ks_M2=ptr(s.ks_M2),
+             exceed=ptr(s.exceed), hist_sum=ptr(s.hist_sum), k=int(k), hip_stream=st)
 
     @_on_device
     def rescale_read(self, s):

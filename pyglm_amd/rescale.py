@@ -22,11 +22,12 @@ with an engine_factory folds through them on the host from engine.psi(...).
 """
 import numpy as np
 
+from . import _lib
 from . import simulate as _sim
 from .summary import _welford
 
 PURPOSE_RESCALE = 3
-PGL_RESCALE_MAX_BINS = 256          # bins of the histogram of z at most (include/pyglm_hip.h)
+PGL_RESCALE_MAX_BINS = _lib.PGL_RESCALE_MAX_BINS    # bins of the histogram of z at most
 _M32 = 0xFFFFFFFF
 
 

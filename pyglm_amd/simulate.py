@@ -90,8 +90,8 @@ def generate(Wm, bias, basis, T, obs, noise_scale=0.0, device=None, verbose=Fals
             n = min(Tc, T - t0)
             U_h[:n].numpy()[...] = U
             U_d[:n].copy_(U_h[:n], non_blocking=True)
-            call("pgl_generate", ptr(Wm_d), ptr(bias_d), ptr(basis_d), N, B, L, obs, float(noise_scale), ptr(U_d), ptr(ring),
-                 ptr(Y_d[t0:t0 + n]), t0, n, ptr(work), ptr(status), st)
+            call("pgl_generate", Wm=ptr(Wm_d), bias=ptr(bias_d), basis=ptr(basis_d), N=N, B=B, L=L, obs=obs, noise_scale=float(noise_scale),
+                 U=ptr(U_d), ring=ptr(ring), Y=ptr(Y_d[t0:t0 + n]), t0=t0, Tc=n, work=ptr(work), status=ptr(status), hip_stream=st)
             more = min(Tc, T - t0 - n)                     # the next chunk's draws, while this one runs
             U = _finish_launch("pgl_generate", dev, status, status_h, t0, t0 + n - 1, (lambda: draw(more, N)) if more > 0 else None)
             if verbose:
@@ -109,7 +109,8 @@ def generate(Wm, bias, basis, T, obs, noise_scale=0.0, device=None, verbose=Fals
         for r0 in range(0, T, rows):
             r1 = min(T, r0 + rows)
             h = min(L, r0)
-            call("pgl_design_matrix", ptr(Y_d[r0 - h:]), N, ptr(basis_d), ptr(Xs), D + 1, None, 0, r1 - r0 + h, N, B, L, 0, st)
+            call("pgl_design_matrix", S=ptr(Y_d[r0 - h:]), lds=N, basis=ptr(basis_d), X=ptr(Xs), ldx=D + 1, Xt=None, ldxt=0, T=r1 - r0 + h,
+                 N=N, B=B, R=L, clip=0, hip_stream=st)
             X2[r0:r1].copy_(Xs[h:h + r1 - r0, :D])
     return X, Y
 
@@ -138,12 +139,12 @@ PURPOSE_SIM = 2
 KINDS = tuple(sorted(_reg.MODELS, key=lambda name: _reg.MODELS[name].sim_kind))          # KINDS[kind[n]]: the model's name
 KIND_BERNOULLI, KIND_GAUSSIAN, KIND_NEGBIN, KIND_BINOMIAL = (_reg.MODELS[name].sim_kind for name in KINDS)
 NEGBIN_CAP = 65535
-BINOMIAL_MAX_N = 64
+BINOMIAL_MAX_N = _lib.PGL_SIM_BINOMIAL_MAX_N
 HOST_BLOCK_BINS = 4096          # bins the host path keeps in its rolling buffer when the paths are not kept
-PGL_LAG_MAX = 256               # lags of the cross-correlogram at most (include/pyglm_hip.h)
-LAG_I8, LAG_F64 = 0, 1          # modes of pgl_lagged_products: the counts on the int8 matrix cores (exact), any real Y through the fp64 contraction
+PGL_LAG_MAX = _lib.PGL_LAG_MAX  # lags of the cross-correlogram at most
+LAG_I8, LAG_F64 = _lib.PGL_LAG_I8, _lib.PGL_LAG_F64     # modes of pgl_lagged_products: the counts on the int8 matrix cores (exact), any real Y through the fp64 contraction
 LAG_REDOS = 0                   # folds of simulate_device that the int8 mode refused (a count beyond 127) and the fp64 mode redid, since import
-PGL_ISI_MAX_BINS = 256          # bins of the inter-spike-interval histogram at most (include/pyglm_hip.h)
+PGL_ISI_MAX_BINS = _lib.PGL_ISI_MAX_BINS    # bins of the inter-spike-interval histogram at most
 
 _M32 = np.uint64(0xFFFFFFFF)
 
@@ -412,8 +413,8 @@ class _IsiFold(object):
 
     def fold(self, Y, ldy, strideY, rows):
         """Y: the tensor that starts at the first new row of replicate 0"""
-        call("pgl_isi_fold", ptr(Y), ldy, strideY, rows, self.N, self.R, self.D, ptr(self.hist), ptr(self.moments), ptr(self.since),
-             0 if self.first else 1, ptr(self.work), self.st)
+        call("pgl_isi_fold", Y=ptr(Y), ldy=ldy, strideY=strideY, rows=rows, N=self.N, R=self.R, D=self.D, hist=ptr(self.hist),
+             moments=ptr(self.moments), since=ptr(self.since), accumulate=0 if self.first else 1, work=ptr(self.work), hip_stream=self.st)
         self.first = False
 
     def finish(self):
@@ -507,7 +508,8 @@ def lagged_products_device(Y, lags, mode=None, device=None):
         S = torch.empty((K, N, N), dtype=torch.float64, device=dev)
         work = torch.empty(_lib.load().pgl_lagged_work_bytes(N, K, 1, T), dtype=torch.uint8, device=dev)
         status = torch.zeros(4, dtype=torch.int32, device=dev)
-        call("pgl_lagged_products", ptr(Y_d), N, T * N, T, 0, N, K, 1, ptr(S), K * N * N, 0, mode, ptr(work), ptr(status), st)
+        call("pgl_lagged_products", Y=ptr(Y_d), ldy=N, strideY=T * N, rows=T, prev=0, N=N, K=K, R=1, S=ptr(S), strideS=K * N * N, accumulate=0,
+             mode=mode, work=ptr(work), status=ptr(status), hip_stream=st)
         code = status.cpu().numpy()
         if code[0]:
             raise PglError("pgl_lagged_products: the value of neuron %d at row %d is no integer of [-127, 127]" % (code[3], code[1]))
@@ -530,8 +532,9 @@ class _LagFold(object):
         self.first, self.redos = True, 0
 
     def _call(self, Y, strideY, rows, prev, mode):
-        call("pgl_lagged_products", ptr(Y), self.N, strideY, rows, prev, self.N, self.K, self.R, ptr(self.S), self.K * self.N * self.N,
-             0 if self.first else 1, mode, ptr(self.work), ptr(self.status), self.st)
+        call("pgl_lagged_products", Y=ptr(Y), ldy=self.N, strideY=strideY, rows=rows, prev=prev, N=self.N, K=self.K, R=self.R, S=ptr(self.S),
+             strideS=self.K * self.N * self.N, accumulate=0 if self.first else 1, mode=mode, work=ptr(self.work), status=ptr(self.status),
+             hip_stream=self.st)
 
     def fold(self, Y, strideY, rows, prev):
         """Y: the tensor that starts at the first new row of replicate 0"""
@@ -672,8 +675,9 @@ def simulate_device(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep
             n = min(Tc, T - k0)
             out, ldr = ((Y_d[0, k0:], T * N) if keep_paths else (buf[0, K - 1:], Tb * N) if K else (ibuf, min(Tc, T) * N) if D
                         else (None, T * N))
-            call("pgl_simulate", ptr(Wm_d), ptr(bias_d), ptr(basis_d), N, B, L, ptr(kind_d), ptr(par_d), R, rep0, seed & (2 ** 64 - 1), ptr(ring),
-                 ptr(out), ldr, ptr(sum_d), ptr(sq_d), t0 + k0, n, ptr(work), ptr(status), st)
+            call("pgl_simulate", Wm=ptr(Wm_d), bias=ptr(bias_d), basis=ptr(basis_d), N=N, B=B, L=L, kind=ptr(kind_d), par=ptr(par_d), R=R, rep0=rep0,
+                 seed=seed & (2 ** 64 - 1), ring=ptr(ring), Y=ptr(out), ldr=ldr, sum=ptr(sum_d), sumsq=ptr(sq_d), t0=t0 + k0, Tc=n, work=ptr(work),
+                 status=ptr(status), hip_stream=st)
             _finish_launch("pgl_simulate", dev, status, status_h, t0 + k0, t0 + k0 + n - 1)
             if D:
                 ifold.fold(out, N, ldr, n)
@@ -907,7 +911,7 @@ class PredictiveCheck(object):
 
 # =====================================================================================================================================
 # Conditional simulation: model.conditional_simulate() / model.conditional_check().  Some neurons are data, the others are drawn.
-PGL_COND_MAX_FREE = 256         # free neurons at most (include/pyglm_hip.h)
+PGL_COND_MAX_FREE = _lib.PGL_COND_MAX_FREE  # free neurons at most
 COND_MAX_X = 8192               # F * B at most on the device: x_t of a replicate lives in LDS
 
 
@@ -1076,8 +1080,9 @@ def conditional_device(Wff, base, basis, kind, par, neuron, R, seed, rep0, hist,
             n = min(Tc, T - k0)
             yout, ldr = (Y_d[0, k0:], T * F) if keep_paths else (None, 0)
             pout, ldp = (P_d[0, k0:], T * F) if want_psi is True else (P_d, Tc * F) if want_psi else (None, 0)
-            call("pgl_conditional_simulate", ptr(Wff_d), ptr(base_d[k0:]), F, ptr(basis_d), F, B, L, ptr(kind_d), ptr(par_d), ptr(neuron_d), R, rep0,
-                 seed & (2 ** 64 - 1), ptr(ring), ptr(yout), ldr, ptr(pout), ldp, ptr(sum_d), ptr(sq_d), t0 + k0, n, ptr(status), st)
+            call("pgl_conditional_simulate", Wff=ptr(Wff_d), base=ptr(base_d[k0:]), ldb=F, basis=ptr(basis_d), F=F, B=B, L=L, kind=ptr(kind_d),
+                 par=ptr(par_d), neuron=ptr(neuron_d), R=R, rep0=rep0, seed=seed & (2 ** 64 - 1), ring=ptr(ring), Y=ptr(yout), ldr=ldr,
+                 Psi=ptr(pout), ldp=ldp, sum=ptr(sum_d), sumsq=ptr(sq_d), t0=t0 + k0, Tc=n, status=ptr(status), hip_stream=st)
             _finish_launch("pgl_conditional_simulate", dev, status, status_h, t0 + k0, t0 + k0 + n - 1)
             if fold:
                 fold(P_d[:, :n], k0)

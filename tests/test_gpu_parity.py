@@ -36,6 +36,20 @@ def test_philox_words_bit_exact(torch_dev):
     np.testing.assert_array_equal(got, orc.philox_words(seed, 1, 3, 10, stream, n))
 
 
+def test_philox_words_called_by_parameter_name(torch_dev):
+    """one launch with positional values, one with the header's parameter names (written in another order): the same four words"""
+    torch = torch_dev
+    from pyglm_amd import simulate
+    from pyglm_amd._lib import call, ptr
+    seed, stream = 0x1234567890ABCDEF, orc.stream_id(77, 5)
+    pos, named = (torch.zeros(4, 4, dtype=torch.int32, device="cuda:0") for _ in range(2))
+    call("pgl_philox_words", seed, 1, 3, 10, stream, ptr(pos), 4, None)
+    call("pgl_philox_words", out=ptr(named), n=4, hip_stream=None, stream=stream, elem0=10, j=3, purpose=1, seed=seed)
+    pos, named = pos.cpu().numpy().view(np.uint32), named.cpu().numpy().view(np.uint32)
+    np.testing.assert_array_equal(pos, named)
+    np.testing.assert_array_equal(named, simulate.philox_words(seed, 1, 3, 10, stream, 4))
+
+
 @pytest.mark.parametrize("zscale", [0.5, 3.0, 12.0])
 def test_pg_draw_matches_oracle(torch_dev, zscale):
     torch = torch_dev
