@@ -8,6 +8,9 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libpyglm_hip.so")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip.h")
+# the entries added beside ABI 11 (the dispersion fold): a header of the same regular shape, parsed into tables of its own -- FUNCTIONS,
+# SIGNATURES, PARAMS and CONSTANTS describe pyglm_hip.h alone
+HEADER_DISPERSION = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip_dispersion.h")
 
 
 class PglError(RuntimeError):
@@ -88,7 +91,16 @@ ABI_VERSION, NSTAGES = CONSTANTS["PGL_ABI_VERSION"], CONSTANTS["PGL_NSTAGES"]
 FlipState, CholState, Dataset, StageTimes, Sweep = (_structs[c] for c in _CLASS_NAMES)
 SIGNATURES = {f: [t for _, t in params] for f, (_, params) in FUNCTIONS.items()}    # symbol -> argument types
 PARAMS = {f: [p for p, _ in params] for f, (_, params) in FUNCTIONS.items()}        # symbol -> parameter names, in the header's order
+with open(HEADER_DISPERSION) as _fh:
+    DISPERSION_CONSTANTS, _, DISPERSION_FUNCTIONS = parse_header(_fh.read())
+globals().update(DISPERSION_CONSTANTS)                            # PGL_PURPOSE_DISPERSION, PGL_DISPERSION_ROWS, ...
+DISPERSION_PARAMS = {f: [p for p, _ in params] for f, (_, params) in DISPERSION_FUNCTIONS.items()}
 _lib = None
+
+
+def _params(name):
+    """the parameter names of entry `name`, of whichever header declares it"""
+    return PARAMS[name] if name in PARAMS else DISPERSION_PARAMS[name]
 
 
 def load():
@@ -103,10 +115,11 @@ def load():
     #                      dependency on libamdhip64 has to resolve to the copy torch has loaded (loading the library first leaves
     #                      two runtimes in the process: "no ROCm-capable device is detected" at the first launch)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, _) in FUNCTIONS.items():
-        fn = getattr(lib, name)     # AttributeError if the export is missing
-        fn.argtypes = SIGNATURES[name]
-        fn.restype = restype
+    for functions in (FUNCTIONS, DISPERSION_FUNCTIONS):
+        for name, (restype, params) in functions.items():
+            fn = getattr(lib, name)     # AttributeError if the export is missing
+            fn.argtypes = [t for _, t in params]
+            fn.restype = restype
     if lib.pgl_abi_version() != ABI_VERSION:
         raise PglError("libpyglm_hip.so ABI version %d != %d (rebuild: make -C pyglm_amd/csrc)" % (lib.pgl_abi_version(), ABI_VERSION))
     _lib = lib
@@ -121,7 +134,7 @@ def source_hash():
     h = hashlib.sha256()
     src = os.path.join(_HERE, "csrc")
     files = [os.path.join(src, f) for f in sorted(os.listdir(src)) if f.endswith((".hip", ".h")) or f == "Makefile"]
-    files.append(os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip.h"))
+    files += [HEADER, HEADER_DISPERSION]
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")
         with open(f, "rb") as fh:
@@ -132,7 +145,7 @@ def source_hash():
 def call(name, *args, **by_name):
     """name(*args), or name(**by_name) with the keywords put in the order of the header's parameter names; raises PglError on a non-zero status"""
     if by_name:
-        names = PARAMS[name]
+        names = _params(name)
         if args:
             raise TypeError("%s: positional values mixed with keyword '%s'" % (name, next(iter(by_name))))
         missing = [k for k in names if k not in by_name]

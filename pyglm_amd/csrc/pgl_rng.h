@@ -20,6 +20,8 @@
 #define PGL_PURPOSE_PG 1u
 #define PGL_PURPOSE_SIM 2u          // forward simulation (pgl_simulate): stream = (replicate << 32) | global neuron, element = time bin
 #define PGL_PURPOSE_RESCALE 3u      // time rescaling (pgl_rescale_fold): stream = global neuron, element = elem0 + the event's time bin, call = draw
+//                                  purpose 4 is PGL_PURPOSE_DISPERSION of include/pyglm_hip_dispersion.h (pgl_dispersion_fold): stream = (sweep << 32) | global
+//                                  neuron, element = elem0 + the cell's time bin, call j = uniforms 2j and 2j + 1 of the cell's CRT trials
 #define PGL_PG_TRUNC 0.64
 #define PGL_PG_MAX_TRIALS 10000     // bound of every rejection loop (BayesLogit's own bound); never met on finite input
 #define PGL_PG_MAX_INNER 1000       // bound of the alternating partial sums (they decide within a few terms)

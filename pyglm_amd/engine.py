@@ -52,12 +52,13 @@ def make_draws(seed, sweep, neuron_ids, N, D):
     return perm, u, z
 
 
-def make_gamma_draws(seed, sweep, neuron_ids, alpha):
+def make_gamma_draws(seed, sweep, neuron_ids, alpha, lane=1):
     """standard Gamma(alpha, 1) variates for the noise-variance update of the Gaussian model (regression.py:433-445), keyed like
-    make_draws by (seed, sweep, GLOBAL neuron) on a separate counter lane"""
+    make_draws by (seed, sweep, GLOBAL neuron) on a separate counter lane: 1, the noise variance eta; 2, the negative-binomial dispersion
+    xi (dispersion.XI_LANE)"""
     g = np.empty(len(neuron_ids))
     for i, n in enumerate(neuron_ids):
-        rng = np.random.Generator(np.random.Philox(key=int(seed) & (2 ** 64 - 1), counter=[int(sweep), int(n), 1, 0]))
+        rng = np.random.Generator(np.random.Philox(key=int(seed) & (2 ** 64 - 1), counter=[int(sweep), int(n), int(lane), 0]))
         g[i] = rng.standard_gamma(alpha)
     return g
 
@@ -101,6 +102,10 @@ class _Summary(object):
 class _Rescale(object):
     """device accumulators of one time-rescaling test (GibbsEngine.rescale_alloc): hist / zsum / ks of the last sample, the running
     ks_mean, ks_M2, exceed, hist_sum, and the fold's scratch"""
+
+
+class _Dispersion(object):
+    """scratch and results of GibbsEngine.dispersion_stats: the fold's work, L and S per neuron"""
 
 
 class _I8Scratch(typing.NamedTuple):
@@ -200,6 +205,7 @@ class GibbsEngine(object):
         self.wait_seconds = 0.0
         self.overlap_seconds = 0.0
         self.launch_seconds = 0.0      # inside the pgl_sweep call itself: ~3 000 launches at the headline size (and, when the queue is full, waiting)
+        self._disp = None              # scratch and results of dispersion_stats, allocated at its first call
 
     def _obs_param(self, xi):
         """-> (scalar xi, None) or (1.0, [nloc] device array of the shard's per-neuron values), checked: > 0 (negative binomial), >= 0 (binomial)"""
@@ -218,6 +224,21 @@ class GibbsEngine(object):
         if self.obs == OBS_BINOMIAL and not np.all((vals >= 0) & (vals == np.floor(vals))):
             raise ValueError("binomial: the number of trials n must be an integer >= 0")
         return out
+
+    @_on_device
+    def set_obs_param(self, xi):
+        """overwrite the per-neuron parameter of the observation model (xi, negative binomial; n, binomial) IN PLACE: the device array's
+        pointer sits in the once-built pgl_sweep_t and in the accumulators that share it, so it is never reallocated.  xi: one value per
+        neuron of the model (N) or of this shard (n1 - n0), checked as at construction.  An engine built from a scalar has no such array
+        and raises."""
+        if self.obs_param is None:
+            raise ValueError("this engine was built with the scalar parameter %r, which its kernels read from their argument blocks: build "
+                             "the engine with one value per neuron to change it afterwards" % (self.xi,))
+        v = np.asarray(xi, dtype=np.float64)
+        if v.ndim == 0:
+            v = np.full(self.nloc, float(v))
+        _, new = self._obs_param(v)
+        self.obs_param.copy_(new)
 
     # ------------------------------------------------------------------ stage timing (HIP events on the launch stream)
     def _tic(self, name, work=0.0):
@@ -845,6 +866,55 @@ class GibbsEngine(object):
         host = lambda t: t.cpu().numpy()
         return dict(hist=host(s.hist).astype(np.int64), zsum=host(s.zsum), ks=host(s.ks), ks_mean=host(s.ks_mean), ks_M2=host(s.ks_M2),
                     exceed=host(s.exceed).astype(np.int64), hist_sum=host(s.hist_sum))
+
+    @_on_device
+    def rescale_set_par(self, s, par):
+        """replace the factor of log1p(exp(psi)) of the accumulators s (a model that learns xi: the factor moves with the chain)"""
+        par = np.broadcast_to(np.asarray(par, dtype=np.float64).reshape(-1), (self.nloc,))
+        s.qpar0 = float(par[0])
+        if s.qpar is not None:
+            s.qpar.copy_(torch.from_numpy(np.array(par)))
+        elif np.any(par != par[0]):
+            s.qpar = torch.from_numpy(np.array(par)).to(self.dev)
+
+    # ------------------------------------------------------------------ the negative-binomial dispersion (pyglm_amd/dispersion.py)
+    def dispersion_bytes(self):
+        """device bytes dispersion_stats takes: the workgroups' partials of the longest data set, and L and S per neuron"""
+        T = max([ds.T for ds in self.datasets] or [0])
+        return _lib.load().pgl_dispersion_work_bytes(self.nloc, T) + 16 * self.nloc
+
+    @_on_device
+    def dispersion_stats(self, a, W, b, seed, sweep):
+        """the sufficient statistics of xi | y, psi at the state (a, W, b) -> (L int64, S float64), host arrays (nloc,): the CRT table counts
+        under the engine's CURRENT per-neuron xi (set_obs_param) and sum_t log(1 + e^psi_t), over every data set.  One upload of the
+        weights; per data set ONE activation and ONE pgl_dispersion_fold (dispersion.dispersion_host states what it computes), the data
+        sets behind the first adding to the same sums.  The scratch is allocated at the first call and checked against what this engine
+        may still take on its GPU (_free_bytes) BEFORE that: MemoryError otherwise."""
+        if self.obs != OBS_NEGBIN or self.obs_param is None:
+            raise ValueError("dispersion_stats(): an engine of the negative-binomial model with one xi per neuron is required")
+        T = max([ds.T for ds in self.datasets] or [0])
+        need = _lib.load().pgl_dispersion_work_bytes(self.nloc, T)
+        d = self._disp
+        if d is None or d.work.numel() < need:
+            self._disp = d = None
+            total, free = self.dispersion_bytes(), self._free_bytes()
+            if total > free:
+                raise MemoryError("dispersion: the scratch needs %d bytes, %d are free on %s" % (total, free, self.dev))
+            d = self._disp = _Dispersion()
+            d.work = torch.empty(need, dtype=torch.uint8, device=self.dev)
+            d.L, d.S = self._z(self.nloc, dtype=torch.int64), self._z(self.nloc)
+        self._upload_weights(a, W, b)
+        st = self._st()
+        if not self.datasets:
+            d.L.zero_(), d.S.zero_()              # (with data the first fold, accumulate = 0, overwrites both)
+        for i, ds in enumerate(self.datasets):
+            self._activation(ds, st)
+            h = self._tic("dispersion_fold", float(ds.T) * self.nloc)
+            call("pgl_dispersion_fold", Psi=ptr(ds.Psi), ldn=self.ldn, bias=ptr(self.bias), Y=ptr(ds.Y), T=ds.T, nloc=self.nloc,
+                 xi=ptr(self.obs_param), seed=int(seed) & (2 ** 64 - 1), sweep=int(sweep) & (2 ** 64 - 1), neuron0=self.n0, elem0=ds.elem0,
+                 L=ptr(d.L), S=ptr(d.S), accumulate=int(i > 0), work=ptr(d.work), hip_stream=st)
+            self._toc(h)
+        return d.L.cpu().numpy(), d.S.cpu().numpy()
 
     # ------------------------------------------------------------------ one Gibbs sweep of the shard's regressions
     def _sweep_args(self, ovs=None):

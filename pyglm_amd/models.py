@@ -196,9 +196,56 @@ class NonlinearAutoregressiveModel(object):
         if self._engine is None:
             return
         mode = _regression.device_obs(self.regressions)
+        if mode[0] == self._engine_mode[0] == "negbin" and np.ndim(self._engine_mode[1]) and _regression.learns_xi(self.regressions):
+            self._engine_mode = mode          # a learned xi moves (and a user may set r.xi): the model kind is what stays guarded
+            return
         if not _regression.same_obs(mode, self._engine_mode):
             raise ValueError("the regressions now call for the device observation model %r (param %r), but this model's engine was built for %r "
                              "(param %r): build a new model for the new regressions" % (mode[0], mode[1], self._engine_mode[0], self._engine_mode[1]))
+
+    # ---- the negative-binomial dispersion, where regressions learn it (pyglm_amd/dispersion.py)
+    def _learns_xi(self):
+        """does any regression of the WHOLE model learn its xi?  (every rank answers alike: they take the same exchange path)"""
+        return self.engine_obs() == "negbin" and _regression.learns_xi(self.regressions)
+
+    def _push_xi(self, eng=None):
+        """the shard's current xi into the engine's per-neuron device array: the learned values, and whatever set_state() or a user's
+        `r.xi = ...` put there since the last sweep"""
+        eng = self.engine if eng is None else eng
+        if not hasattr(eng, "set_obs_param"):
+            raise ValueError("a regression with xi_prior needs an engine that takes a new xi: %s has no set_obs_param(xi)" % type(eng).__name__)
+        eng.set_obs_param([r.xi for r in self.regressions[self.n0:self.n1]])
+
+    def _resample_xi(self, a, W, b):
+        """xi of the shard's regressions after the CRT step under the weights (a, W, b) the sweep just drew -> (nloc,): the table counts and
+        sum_t log(1 + e^psi) from the device (engine.dispersion_stats), or through dispersion.dispersion_host from engine.psi for an
+        engine without it; the gamma variates from the host, keyed by the global neuron.  A regression without xi_prior keeps its xi."""
+        from . import dispersion as _disp
+        regs = self.regressions[self.n0:self.n1]
+        eng = self.engine
+        if hasattr(eng, "dispersion_stats"):
+            L, S = eng.dispersion_stats(a, W, b, self.seed, self.sweeps_done)
+        else:
+            xi_now = np.array([r.xi for r in regs], dtype=np.float64)
+            L, S, elem0 = np.zeros(len(regs), dtype=np.int64), np.zeros(len(regs)), 0
+            for i, (_, Y) in enumerate(self.data_list):
+                Yl = np.asarray(Y, dtype=np.float64)[:, self.n0:self.n1]
+                Li, Si = _disp.dispersion_host(np.asarray(eng.psi(a, W, b, i), dtype=np.float64), Yl, xi_now, self.seed, self.sweeps_done,
+                                               self.n0, elem0)
+                L, S, elem0 = L + Li, S + Si, elem0 + Yl.shape[0]
+        xi = np.array([r.xi for r in regs], dtype=np.float64)
+        for i, r in enumerate(regs):
+            if getattr(r, "xi_prior", None) is not None:
+                xi[i] = _disp.draw_xi(r, int(L[i]), float(S[i]), self.seed, self.sweeps_done, self.n0 + i)
+        return xi
+
+    def _store_xi(self, lo, xi):
+        """xi (k,) of neurons lo .. lo + k - 1 onto the regressions that learn it; the engine and the cached device mode follow"""
+        for n, r in enumerate(self.regressions[lo:lo + len(xi)]):
+            if getattr(r, "xi_prior", None) is not None:
+                r.xi = float(xi[n])
+        self._push_xi()
+        self._engine_mode = _regression.device_obs(self.regressions)
 
     # ---- local <-> global state
     def _local_state(self):
@@ -333,6 +380,8 @@ class NonlinearAutoregressiveModel(object):
         a, W, b = self._local_state()
         if self.engine_obs() == "gaussian":
             eng.set_noise([r.eta for r in self.regressions[self.n0:self.n1]])
+        elif self._learns_xi():
+            self._push_xi(eng)
         ll_loc = np.asarray(eng.log_likelihood(a, W, b), dtype=np.float64).reshape(-1)       # one value per local neuron
         return float(np.sum(self._all_neurons(ll_loc)))
 
@@ -391,6 +440,8 @@ class NonlinearAutoregressiveModel(object):
                 _regression.check_counts(self.regressions, Y)
                 eng.add_data(Y, X=X, basis=self.basis, **self._obs_terms_kw(Y))
             cache = self._heldout_cache = (key, eng)
+        if self._learns_xi():
+            self._push_xi(cache[1])              # (the cached engine was built at an earlier xi)
         return cache[1]
 
     def engine_obs(self):
@@ -404,6 +455,8 @@ class NonlinearAutoregressiveModel(object):
         """(models.py:153-163) E[y | X] per dataset, (T, N): per neuron, from its own observation model"""
         a, W, b = self._local_state()
         obs, par = self._engine_mode if self._engine is not None else _regression.device_obs(self.regressions)
+        if self._learns_xi():
+            obs, par = _regression.device_obs(self.regressions)      # xi as it is now (a user may have set r.xi since the last sweep)
         regs = self.regressions[self.n0:self.n1]
         if np.ndim(par):
             par = np.asarray(par, dtype=np.float64)[self.n0:self.n1]
@@ -713,12 +766,15 @@ class NonlinearAutoregressiveModel(object):
             nxt = (self.seed, self.sweeps_done + 1, self.n0, self.n1)
             self._draws_ahead = (nxt, make_draws(self.seed, self.sweeps_done + 1, range(self.n0, self.n1), self.N, self.N * self.B))
         gaussian = self.engine_obs() == "gaussian"
+        learns = self._learns_xi()
         if gaussian:
             self.engine.set_noise([r.eta for r in regs])
+        elif learns:
+            self._push_xi()
         kw = dict(host_overlap=draw_ahead) if self.N * self.N * self.B >= self.DRAW_AHEAD_MIN_SIZE else {}
         exchange = _dist() is not None and not self._shard_override
         handle = []
-        if exchange and not gaussian and hasattr(self.engine, "packed_state"):
+        if exchange and not gaussian and not learns and hasattr(self.engine, "packed_state"):
             # the shard's new rows never visit the host on their own: packed from the sweep's device buffers, gathered, read back once
             kw.update(after_queue=lambda eng: handle.append(self._gather_start(eng.packed_state())), readback=False)
         need_stats = hasattr(getattr(self, "network", None), "weight_blocks")
@@ -751,6 +807,10 @@ class NonlinearAutoregressiveModel(object):
             for i, r in enumerate(regs):
                 alpha, beta = r.eta_posterior(T_total, sse[i])
                 eta[i] = 1.0 / (make_gamma_draws(self.seed, self.sweeps_done, [self.n0 + i], alpha)[0] * (1.0 / beta))
+        elif learns:
+            # the dispersions (dispersion.py): the CRT table counts and sum log(1 + e^psi) under the NEW weights; with several ranks xi
+            # rides in the rows' eta slot, on the exchange path the Gaussian model takes
+            eta = self._resample_xi(a, W, b)
         self.sweeps_done += 1
         # the rows' sufficient statistics for the network prior (networks.py:132-149), from the state the sweep left on the device
         stats = None
@@ -773,18 +833,22 @@ class NonlinearAutoregressiveModel(object):
             if gaussian:
                 for i, r in enumerate(regs):
                     r.eta = float(eta[i])
+            elif learns:
+                self._store_xi(self.n0, eta)
             return
         if not exchange:
-            A_all, W_all, b_all, eta_all, stats_all = a, W, b, (eta if gaussian else None), stats
+            A_all, W_all, b_all, eta_all, stats_all = a, W, b, (eta if gaussian or learns else None), stats
         else:
             import torch
-            packed = torch.from_numpy(self._pack_rows_host(a, W, b, eta if gaussian else None, stats))
+            packed = torch.from_numpy(self._pack_rows_host(a, W, b, eta if gaussian or learns else None, stats))
             A_all, W_all, b_all, eta_all, stats_all = self._gather_finish(self._gather_start(packed))
         self._store_rows(0, self.N, A_all, W_all, b_all)
         self._fresh_stats = stats_all
         if gaussian:
             for n, r in enumerate(self.regressions):
                 r.eta = float(eta_all[n])
+        elif learns:
+            self._store_xi(0 if exchange else self.n0, eta_all)
 
     # ---- chain state (checkpoint / resume; also lets two samplers be run from one state)
     _STATE_ATTRS = ("regressions", "sweeps_done", "_hyper_cache", "network")

@@ -381,13 +381,45 @@ class BernoulliRegression(SparseBernoulliRegression):
 
 class SparseNegativeBinomialRegression(_SparsePGRegressionBase):
     """named in the reference docstring (:463-466) but not implemented there; defined through the hooks (:479-489):
-    y ~ NB(xi, sigma(psi)):  a = y, b = y + xi, c = C(y+xi-1, y)."""
+    y ~ NB(xi, sigma(psi)):  a = y, b = y + xi, c = C(y+xi-1, y).
+    xi_prior=(e0, f0), both > 0: xi ~ Gamma(e0, rate f0) is LEARNED -- resampled after every sweep from its conditional given the CRT
+    table counts (pyglm_amd/dispersion.py), starting at `xi`.  xi_prior=None (default): xi stays what the constructor was given."""
     _obs = "negbin"
 
-    def __init__(self, N, B, xi=1.0, **kwargs):
+    def __init__(self, N, B, xi=1.0, xi_prior=None, **kwargs):
         assert xi > 0
         self.xi = float(xi)
+        if xi_prior is not None:
+            e0, f0 = xi_prior
+            if not (np.isscalar(e0) and np.isscalar(f0) and e0 > 0 and f0 > 0):
+                raise ValueError("xi_prior = (e0, f0): shape and rate of the Gamma prior of xi, both > 0, got %r" % (xi_prior,))
+            xi_prior = (float(e0), float(f0))
+        self.xi_prior = xi_prior
         super(SparseNegativeBinomialRegression, self).__init__(N, B, **kwargs)
+
+    def check_data(self, y):
+        """a regression that learns xi walks the y trials of every cell: counts must be integers in [0, 2^24).  A fixed xi checks nothing"""
+        if getattr(self, "xi_prior", None) is None:
+            return
+        y = np.asarray(y, dtype=float)
+        if not np.all((y >= 0) & (y < 2 ** 24) & (y == np.floor(y))):
+            raise ValueError("negative-binomial observations of a regression that learns xi must be integers in [0, 2^24)")
+
+    def xi_posterior(self, L, S):
+        """(shape, rate) of the conditional of xi given the table counts: L = sum_t l_t, S = sum_t log(1 + e^psi_t) (dispersion.py)"""
+        e0, f0 = self.xi_prior
+        return e0 + L, f0 + S
+
+    def _before_sweep(self, eng):
+        if getattr(self, "xi_prior", None) is not None:
+            eng.set_obs_param([self.xi])
+
+    def _after_sweep(self, eng, seed, sweep):
+        if getattr(self, "xi_prior", None) is None:
+            return
+        from .dispersion import draw_xi
+        L, S = eng.dispersion_stats(self.a[None], self.W[None], self.b, seed, sweep)      # under the NEW weights
+        self.xi = draw_xi(self, int(L[0]), float(S[0]), seed, sweep, 0)
 
     def a_func(self, data):
         return data
@@ -540,9 +572,11 @@ def _kind(reg):
 def device_obs(regressions):
     """-> (obs, param): the observation model the device runs for ALL of `regressions` (a model's list, or [reg] for a stand-alone one).
     Built-in Bernoulli: ("bernoulli", 1.0).  Built-in negative binomial: ("negbin", xi) -- a scalar when every xi is equal, else one per
-    regression.  Built-in binomial: ("binomial", n), likewise.  Gaussian: ("gaussian", 1.0).  Any other mix of Polya-gamma regressions, or a
+    regression; always one per regression when any of them learns its xi (xi_prior): the kernels then read the per-neuron array, which
+    GibbsEngine.set_obs_param overwrites, never a scalar captured at allocation time.  Built-in binomial: ("binomial", n), likewise.  Gaussian: ("gaussian", 1.0).  Any other mix of Polya-gamma regressions, or a
     hook overridden in a class or on an instance: ("hooks", 1.0) -- their a/b/c are evaluated on the host (obs_terms).  Gaussian mixed with
-    a Polya-gamma model raises ValueError; a regression type the device cannot run raises TypeError."""
+    a Polya-gamma model raises ValueError, and so does a regression that learns xi in a list that runs in hooks mode; a regression type the
+    device cannot run raises TypeError."""
     # (this runs over all N regressions before every sweep: the classes' answers once per distinct class, in the list's order)
     kinds = set(map(_kind_of_class, dict.fromkeys(map(type, regressions))))
     if "gaussian" in kinds:
@@ -550,13 +584,22 @@ def device_obs(regressions):
             raise ValueError("a Gaussian regression cannot share a model with Polya-gamma regressions (%s)" % sorted(set(map(_kind, regressions))))
         return "gaussian", 1.0
     if len(kinds) != 1 or "hooks" in kinds or any(_on_instance(r, _HOOKS) for r in regressions):
+        if learns_xi(regressions):
+            raise ValueError("xi_prior: regression %d learns its xi, but this list of regressions runs in hooks mode (mixed observation "
+                             "models, or a_func / b_func / c_func overridden): the hook arrays a(y), b(y), log c(y) are evaluated once per "
+                             "data set and cannot follow a moving xi" % next(i for i, r in enumerate(regressions) if learns_xi([r])))
         return "hooks", 1.0
     kind = kinds.pop()
     attr = MODELS[kind].param
     if attr is None:
         return kind, 1.0
     vals = np.array([float(getattr(r, attr)) for r in regressions])
-    return kind, (float(vals[0]) if np.all(vals == vals[0]) else vals)
+    return kind, (float(vals[0]) if np.all(vals == vals[0]) and not learns_xi(regressions) else vals)
+
+
+def learns_xi(regressions):
+    """does any of `regressions` resample its negative-binomial xi (xi_prior set)?"""
+    return any(getattr(r, "xi_prior", None) is not None for r in regressions)
 
 
 def means_of_psi(regressions, mode, psi, X=None):

@@ -138,6 +138,9 @@ class _HostFold(object):
             s["exceed"] += s["ks"] > band(g.coef, s["hist"].sum(axis=1))
         s["hist_sum"] += s["hist"]
 
+    def set_par(self, par):
+        pass                                                  # (fold reads the test's par at every sample)
+
     def read(self):
         return self.s
 
@@ -151,6 +154,9 @@ class _DeviceFold(object):
 
     def reset(self):
         self.eng.rescale_reset(self.buf)
+
+    def set_par(self, par):
+        self.eng.rescale_set_par(self.buf, par)
 
     def fold(self, eng, a, W, b, k):
         eng.rescale_fold(self.buf, a, W, b, k, self.g.seed)
@@ -195,6 +201,11 @@ class TimeRescaling(object):
         if not self.heldout and len(m.data_list) != self._ndata:
             raise RuntimeError("data was added to the model after time_rescaling(): the test covers %d data sets, the model holds %d "
                                "(build a new one)" % (self._ndata, len(m.data_list)))
+        if m._learns_xi():
+            # the factor of log1p(exp(psi)) is the CURRENT xi: read again at every sample, and the device copy with it (a fixed xi keeps
+            # the single read of the constructor)
+            self.par = interval_par(m.regressions)[m.n0:m.n1]
+            self._acc.set_par(self.par)
         a, W, b = m._local_state()
         self._acc.fold(self._eng, a, W, b, self.count + 1)
         self.count += 1

@@ -1144,19 +1144,24 @@ class ConditionalPrediction(object):
         self.t0, self.t1 = check_window(start, stop, Y.shape[0])
         if self.R < 1:
             raise ValueError("conditional_check(): replicates >= 1 is required")
-        regs = [model.regressions[n] for n in self.free]
-        models = observation_models(regs)
-        self._link = np.array([m.link for m in models], dtype=np.int64)
-        self._link_par = np.array([m.par(r) for m, r in zip(models, regs)], dtype=np.float64)
-        Yw = Y[self.t0:self.t1][:, self.free]
-        self._gauss = models[0].sim_kind == KIND_GAUSSIAN
-        if self._gauss:
-            self._terms = (Yw, np.array([float(r.eta) for r in regs]))
-        else:
-            self._terms = _reg.obs_terms(regs, Yw)
+        self._Yw = Y[self.t0:self.t1][:, self.free]
+        self._read_par()
         self.calls = self.count = 0
         self._acc = None                         # [rate mean, rate M2, lse m, lse s], each (T', F), where the simulations run
         self._consts = None                      # link masks, parameters and the terms of l, on the accumulators' side
+
+    def _read_par(self):
+        """the links' parameters and the terms of l from the free neurons' regressions as they are now: once, in the constructor -- and again
+        before every sample of a model that learns xi, whose b(y) = y + xi and log c(y) move with the chain"""
+        regs = [self.model.regressions[n] for n in self.free]
+        models = observation_models(regs)
+        self._link = np.array([m.link for m in models], dtype=np.int64)
+        self._link_par = np.array([m.par(r) for m, r in zip(models, regs)], dtype=np.float64)
+        self._gauss = models[0].sim_kind == KIND_GAUSSIAN
+        if self._gauss:
+            self._terms = (self._Yw, np.array([float(r.eta) for r in regs]))
+        else:
+            self._terms = _reg.obs_terms(regs, self._Yw)
 
     def _setup(self, like):
         shape = (self.t1 - self.t0, self.free.size)
@@ -1165,7 +1170,12 @@ class ConditionalPrediction(object):
         else:
             import torch
             conv, zeros = (lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(like.device)), (lambda: torch.zeros(shape, dtype=torch.float64, device=like.device))
+        self._conv = conv
         self._acc = [zeros() for _ in range(4)]
+        self._put_consts()
+
+    def _put_consts(self):
+        conv = self._conv
         self._consts = dict(link=[conv(self._link == c) for c in range(4)], par=conv(self._link_par), terms=tuple(conv(v) for v in self._terms))
 
     def _fold(self, psi, k0):
@@ -1203,6 +1213,10 @@ class ConditionalPrediction(object):
                 lm[...] = m1
 
     def collect(self):
+        if self.model._learns_xi():
+            self._read_par()
+            if self._acc is not None:
+                self._put_consts()
         inp = self.model._conditional_inputs(self.free, self.data, self.t0, self.t1)
         conditional_simulate(inp["Wff"], inp["base"], inp["basis"], inp["kind"], inp["par"], self.free, self.R, self.seed, self.calls * self.R,
                              inp["hist"], self.t0, False, self.model._on_gpu(self.gpu, "conditional_check"), self.model._device, want_psi=self._fold)

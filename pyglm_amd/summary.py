@@ -37,6 +37,7 @@ class _HostAccumulators(object):
         regs = model.regressions[model.n0:model.n1]
         self.Y = [np.asarray(Y, dtype=np.float64)[:, model.n0:model.n1] for Y in Ys]
         self.terms = None if summary.obs == "gaussian" else [_regression.obs_terms(regs, Y) for Y in self.Y]
+        self._terms_xi = [float(getattr(r, "xi", 0.0)) for r in regs]
         self.reset()
 
     def reset(self):
@@ -68,6 +69,13 @@ class _HostAccumulators(object):
                     eta = np.array([r.eta for r in m.regressions[m.n0:m.n1]], dtype=np.float64)
                     l = -0.5 * np.log(2 * np.pi * eta) - (Y - psi) ** 2 / (2 * eta)
                 else:
+                    if i == 0 and m._learns_xi():
+                        # b(y) = y + xi and log c(y) move with a learned xi: the terms are formed again when it has moved, as the Gaussian
+                        # branch reads eta at every sample
+                        regs = m.regressions[m.n0:m.n1]
+                        xi_now = [float(getattr(r, "xi", 0.0)) for r in regs]
+                        if xi_now != self._terms_xi:
+                            self.terms, self._terms_xi = [_regression.obs_terms(regs, Yi) for Yi in self.Y], xi_now
                     A, Bv, logC = self.terms[i]
                     l = logC + A * psi - Bv * np.log1p(np.exp(psi))
                 lmean, lM2, lm, ls = self.pw[i]
@@ -157,11 +165,13 @@ class PosteriorSummary(object):
             self._acc = _HostAccumulators(self, Ys)
         self.count = 0
         self.log_likelihoods = []
+        self._xi = (np.zeros(model.n1 - model.n0), np.zeros(model.n1 - model.n0))
 
     def reset(self):
         self._acc.reset()
         self.count = 0
         self.log_likelihoods = []
+        self._xi = (np.zeros_like(self._xi[0]), np.zeros_like(self._xi[1]))
 
     def collect(self):
         """fold the model's current state into the accumulators -> the log-likelihood of the summarised data at that state, equal to
@@ -173,8 +183,14 @@ class PosteriorSummary(object):
         a, W, b = m._local_state()
         if self.obs == "gaussian":
             self._eng.set_noise([r.eta for r in m.regressions[m.n0:m.n1]])
+        elif m._learns_xi():
+            m._push_xi(self._eng)
         ll_loc = self._acc.fold(self._eng, a, W, b, self.count + 1)
         self.count += 1
+        # the dispersions are a handful of host numbers per sample: their moments stay on the host (NaN for a neuron without xi)
+        xi = np.array([getattr(r, "xi", np.nan) for r in m.regressions[m.n0:m.n1]], dtype=np.float64)
+        with np.errstate(invalid="ignore"):
+            _welford(self._xi[0], self._xi[1], xi, float(self.count))
         ll = float(np.sum(m._all_neurons(ll_loc)))
         self.log_likelihoods.append(ll)
         return ll
@@ -197,6 +213,13 @@ class PosteriorSummary(object):
     weight_var = property(lambda self: self._state("weight_var"), doc="(N, N, B) their population variance")
     bias_mean = property(lambda self: self._state("bias_mean"), doc="(N,)")
     bias_var = property(lambda self: self._state("bias_var"), doc="(N,)")
+
+    def _xi_moment(self, i, scale):
+        self._need()
+        return self.model._gather_rows(np.ascontiguousarray(self._xi[i] * scale))
+
+    xi_mean = property(lambda self: self._xi_moment(0, 1.0), doc="(N,) mean of the negative-binomial xi over the samples; NaN without xi")
+    xi_var = property(lambda self: self._xi_moment(1, 1.0 / self.count), doc="(N,) its population variance")
 
     def _rates(self, std):
         self._need(rates=True)
