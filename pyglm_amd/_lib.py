@@ -11,6 +11,8 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip.h")
 # the entries added beside ABI 11 (the dispersion fold): a header of the same regular shape, parsed into tables of its own -- FUNCTIONS,
 # SIGNATURES, PARAMS and CONSTANTS describe pyglm_hip.h alone
 HEADER_DISPERSION = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip_dispersion.h")
+# the entries of the chain diagnostics (batch means, conditional edge probabilities): a third header, tables of its own likewise
+HEADER_DIAGNOSTICS = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip_diagnostics.h")
 
 
 class PglError(RuntimeError):
@@ -95,12 +97,19 @@ with open(HEADER_DISPERSION) as _fh:
     DISPERSION_CONSTANTS, _, DISPERSION_FUNCTIONS = parse_header(_fh.read())
 globals().update(DISPERSION_CONSTANTS)                            # PGL_PURPOSE_DISPERSION, PGL_DISPERSION_ROWS, ...
 DISPERSION_PARAMS = {f: [p for p, _ in params] for f, (_, params) in DISPERSION_FUNCTIONS.items()}
+with open(HEADER_DIAGNOSTICS) as _fh:
+    DIAGNOSTICS_CONSTANTS, _, DIAGNOSTICS_FUNCTIONS = parse_header(_fh.read())
+globals().update(DIAGNOSTICS_CONSTANTS)                           # PGL_DIAG_MAX_LEVELS, PGL_DIAG_EDGE, ...
+DIAGNOSTICS_PARAMS = {f: [p for p, _ in params] for f, (_, params) in DIAGNOSTICS_FUNCTIONS.items()}
 _lib = None
 
 
 def _params(name):
     """the parameter names of entry `name`, of whichever header declares it"""
-    return PARAMS[name] if name in PARAMS else DISPERSION_PARAMS[name]
+    for table in (PARAMS, DISPERSION_PARAMS):
+        if name in table:
+            return table[name]
+    return DIAGNOSTICS_PARAMS[name]
 
 
 def load():
@@ -115,7 +124,7 @@ def load():
     #                      dependency on libamdhip64 has to resolve to the copy torch has loaded (loading the library first leaves
     #                      two runtimes in the process: "no ROCm-capable device is detected" at the first launch)
     lib = ctypes.CDLL(LIB_PATH)
-    for functions in (FUNCTIONS, DISPERSION_FUNCTIONS):
+    for functions in (FUNCTIONS, DISPERSION_FUNCTIONS, DIAGNOSTICS_FUNCTIONS):
         for name, (restype, params) in functions.items():
             fn = getattr(lib, name)     # AttributeError if the export is missing
             fn.argtypes = [t for _, t in params]
@@ -134,7 +143,7 @@ def source_hash():
     h = hashlib.sha256()
     src = os.path.join(_HERE, "csrc")
     files = [os.path.join(src, f) for f in sorted(os.listdir(src)) if f.endswith((".hip", ".h")) or f == "Makefile"]
-    files += [HEADER, HEADER_DISPERSION]
+    files += [HEADER, HEADER_DISPERSION, HEADER_DIAGNOSTICS]
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")
         with open(f, "rb") as fh:

@@ -108,6 +108,11 @@ class _Dispersion(object):
     """scratch and results of GibbsEngine.dispersion_stats: the fold's work, L and S per neuron"""
 
 
+class _Diag(object):
+    """device accumulators of one chain diagnostics object (GibbsEngine.diag_alloc): the pending / mean / M2 planes of the batch means, the
+    copies of the state the fold reads, the conditional edge probabilities p, and the serial number of the sweep p was last formed from"""
+
+
 class _I8Scratch(typing.NamedTuple):
     """the integer Gram's scratch (GibbsEngine._i8_reserve)"""
     bytes: int                           # held by the buffers below
@@ -206,6 +211,8 @@ class GibbsEngine(object):
         self.overlap_seconds = 0.0
         self.launch_seconds = 0.0      # inside the pgl_sweep call itself: ~3 000 launches at the headline size (and, when the queue is full, waiting)
         self._disp = None              # scratch and results of dispersion_stats, allocated at its first call
+        self._sweep_serial = 0         # sweeps queued so far, and where the last one's perm lies in _din (diag_fold: the conditional edge
+        self._perm_off = None          # probabilities are formed from the last sweep's log-odds and proposal order)
 
     def _obs_param(self, xi):
         """-> (scalar xi, None) or (1.0, [nloc] device array of the shard's per-neuron values), checked: > 0 (negative binomial), >= 0 (binomial)"""
@@ -916,6 +923,113 @@ class GibbsEngine(object):
             self._toc(h)
         return d.L.cpu().numpy(), d.S.cpu().numpy()
 
+    # ------------------------------------------------------------------ chain diagnostics (pyglm_amd/diagnostics.py)
+    DIAG_SECTIONS = ("edge", "edge_rb", "weight", "bias")      # in the order of the accumulators' entries; bit i of `what` names section i
+
+    def _diag_what(self, what):
+        """`what` as the bit mask of pgl_diag_fold: an int, or names out of DIAG_SECTIONS"""
+        if isinstance(what, (int, np.integer)):
+            mask = int(what)
+        else:
+            mask = sum(1 << self.DIAG_SECTIONS.index(w) for w in set(what))
+        if mask < 1 or mask > _lib.PGL_DIAG_ALL:
+            raise ValueError("diagnostics: no such sections: %r" % (what,))
+        return mask
+
+    def _diag_layout(self, mask):
+        """-> {section: (first entry, entries, shape)} of the sections in `mask`, and the number of entries"""
+        nl, N, B = self.nloc, self.N, self.B
+        shapes = dict(edge=(nl, N), edge_rb=(nl, N), weight=(nl, N, B), bias=(nl,))
+        out, off = {}, 0
+        for i, name in enumerate(self.DIAG_SECTIONS):
+            if mask >> i & 1:
+                cnt = int(np.prod(shapes[name]))
+                out[name] = (off, cnt, shapes[name])
+                off += cnt
+        assert off == _lib.load().pgl_diag_entries(N, B, nl, mask)
+        return out, off
+
+    def diag_bytes(self, levels, what):
+        """device bytes diag_alloc takes: three planes of `levels` doubles per entry (3 * levels * 8 * entries: at N = 1024, B = 5 and 8 levels
+        1.4 GB for all four sections), and the copies of the state the fold reads: a, and where asked for W, b and the conditionals p"""
+        mask = self._diag_what(what)
+        lib = _lib.load()
+        if not 1 <= int(levels) <= _lib.PGL_DIAG_MAX_LEVELS:
+            raise ValueError("diagnostics: levels = %r outside 1 .. %d" % (levels, _lib.PGL_DIAG_MAX_LEVELS))
+        state = 4 * self.nloc * self.N + 8 * (self.nloc * self.N * bool(mask & _lib.PGL_DIAG_EDGE_RB) + self.nloc * self.D * bool(mask & _lib.PGL_DIAG_WEIGHT)
+                                              + self.nloc * bool(mask & _lib.PGL_DIAG_BIAS))
+        return lib.pgl_diag_bytes(lib.pgl_diag_entries(self.N, self.B, self.nloc, mask), int(levels)) + state
+
+    @_on_device
+    def diag_alloc(self, levels, what):
+        """zeroed batch-means accumulators of `levels` dyadic levels for the sections `what` (a bit mask, or names out of DIAG_SECTIONS).
+        Checked against what this engine may still take on its GPU (_free_bytes; an engine built with mem_budget_bytes stays inside that
+        figure too) BEFORE anything is allocated: MemoryError otherwise."""
+        need, free = self.diag_bytes(levels, what), self._free_bytes()
+        if self._mem_budget is not None:
+            free = min(free, int(self._mem_budget))
+        if need > free:
+            raise MemoryError("chain diagnostics: the accumulators need %d bytes, %d are free on %s" % (need, free, self.dev))
+        s = _Diag()
+        s.levels, s.what = int(levels), self._diag_what(what)
+        s.layout, s.entries = self._diag_layout(s.what)
+        s.pending, s.mean, s.M2 = (self._z(s.levels, s.entries) for _ in range(3))
+        s.a = self._z(self.nloc, self.N, dtype=I32)
+        s.W = self._z(self.nloc, self.D) if s.what & _lib.PGL_DIAG_WEIGHT else None
+        s.b = self._z(self.nloc) if s.what & _lib.PGL_DIAG_BIAS else None
+        s.p = self._z(self.nloc, self.N) if s.what & _lib.PGL_DIAG_EDGE_RB else None
+        s.serial = self._sweep_serial          # the conditionals of a sweep queued before the allocation are not this chain's
+        return s
+
+    @_on_device
+    def diag_reset(self, s):
+        for t in (s.pending, s.mean, s.M2):
+            t.zero_()
+        s.serial = self._sweep_serial
+
+    @_on_device
+    def diag_fold(self, s, a, W, b, k):
+        """sample k (1-based) of the state (a, W, b) into the accumulators s: one upload of the state, then pgl_diag_fold.  With edge_rb among
+        the sections, pgl_diag_edge_conditional first forms p from the log-odds and the proposal order of the LAST sweep (keep_logodds must
+        have been on for it) and the given a: the conditionals belong to a sweep, so one fold per sweep is the rule -- RuntimeError where
+        the log-odds are absent or no sweep was queued since the previous fold."""
+        st = self._st()
+        rb = bool(s.what & _lib.PGL_DIAG_EDGE_RB)
+        if rb:
+            if self.logodds is None:
+                raise RuntimeError("diagnostics: the conditional edge probabilities need the last sweep's log-odds, and there are none "
+                                   "(engine.keep_logodds must be on before the sweep)")
+            if self._sweep_serial == s.serial:
+                raise RuntimeError("diagnostics: no sweep since the previous fold -- the conditional edge probabilities belong to a sweep, "
+                                   "one fold per sweep")
+        s.a.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(a).reshape(self.nloc, self.N), dtype=np.int32)))
+        if s.W is not None:
+            s.W.copy_(torch.from_numpy(np.ascontiguousarray(W, dtype=np.float64).reshape(self.nloc, self.D)))
+        if s.b is not None:
+            s.b.copy_(torch.from_numpy(np.ascontiguousarray(b, dtype=np.float64).reshape(self.nloc)))
+        if rb:
+            call("pgl_diag_edge_conditional", logodds=ptr(self.logodds), perm=ctypes.c_void_p(self._din.data_ptr() + self._perm_off), a=ptr(s.a),
+                 p=ptr(s.p), nloc=self.nloc, N=self.N, hip_stream=st)
+            s.serial = self._sweep_serial
+        h = self._tic("diag_fold", float(s.entries))
+        call("pgl_diag_fold", a=ptr(s.a), W=ptr(s.W), b=ptr(s.b), p=ptr(s.p), pending=ptr(s.pending), mean=ptr(s.mean), M2=ptr(s.M2), N=self.N,
+             B=self.B, nloc=self.nloc, levels=s.levels, k=int(k), what=s.what, hip_stream=st)
+        self._toc(h)
+
+    @_on_device
+    def diag_read(self, s, k, sections=None, levels=None):
+        """-> host {section: dict(pending, mean, M2)} after k samples, each array (number of levels read,) + the section's shape: edge and
+        edge_rb (nloc, N), weight (nloc, N, B), bias (nloc,).  sections: names (default: all of s); levels: the levels to read (default:
+        all) -- a read-out needs two of them, and a plane of the weights is 42 MB at N = 1024."""
+        lv = list(range(s.levels)) if levels is None else [int(l) for l in levels]
+        idx = torch.tensor(lv, dtype=torch.int64, device=self.dev)
+        out = {}
+        for name in (s.layout if sections is None else sections):
+            off, cnt, shape = s.layout[name]
+            out[name] = {key: t[:, off:off + cnt].index_select(0, idx).cpu().numpy().reshape((len(lv),) + shape)
+                         for key, t in (("pending", s.pending), ("mean", s.mean), ("M2", s.M2))}
+        return out
+
     # ------------------------------------------------------------------ one Gibbs sweep of the shard's regressions
     def _sweep_args(self, ovs=None):
         """the argument block of pgl_sweep and pgl_sweep_gram.  Every buffer is persistent, so the struct is built once -- again when the I/O
@@ -1015,6 +1129,7 @@ class GibbsEngine(object):
         sw = self._sweep_args(ovs)
         sw.rho, sw.Jw, sw.hw, sw.label, sw.Jb, sw.hb, sw.c0 = dp["rho"], dp["Jw"], dp["hw"], dp["label"], dp["Jb"], dp["hb"], dp["c0"]
         sw.perm, sw.u, sw.z = dp["perm"], dp["u"], dp["z"]
+        self._perm_off, self._sweep_serial = offs["perm"], self._sweep_serial + 1
         sw.logodds, sw.c0_dense = ptr(self.logodds), ptr(self._c0_dense)
         n_act = int(a.sum(axis=1).max()) if a.size else 0
         sw.nrun, sw.nfirst, sw.all_deterministic = int(nrun), int(nfirst), int(det.all())

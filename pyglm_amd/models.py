@@ -415,6 +415,15 @@ class NonlinearAutoregressiveModel(object):
         from .summary import PosteriorSummary
         return PosteriorSummary(self, rates=rates, pointwise=pointwise, datas=datas)
 
+    def diagnose(self, levels=8, weights=True, rb=True):
+        """chain diagnostics bound to this model (pyglm_amd/diagnostics.py: ChainDiagnostics): call its collect() after every sweep to be
+        kept, read mcse(...) / ess(...) / min_ess() / edge_prob_rb / rb_gain at the end, compare chains with diagnostics.rhat.  levels:
+        dyadic batch sizes kept, 1 .. 16 (3 x levels doubles per entry, on the device).  weights=False leaves the N x N x B effective weights
+        out.  rb: also average the sweep's conditional edge probabilities (the Rao-Blackwell estimator): turns the engine's keep_logodds
+        on, which changes nothing in the chain; refused for a model with an engine_factory."""
+        from .diagnostics import ChainDiagnostics
+        return ChainDiagnostics(self, levels=levels, weights=weights, rb=rb)
+
     def _heldout_engine(self, datas):
         """likelihood-only engine (X', Y, Psi: no sweep buffers, no residue planes) for data other than the stored data, on THIS shard's
         device; cached by content, so evaluating the same held-out set every iteration uploads it once"""
