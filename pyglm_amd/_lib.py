@@ -13,6 +13,8 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip.h")
 HEADER_DISPERSION = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip_dispersion.h")
 # the entries of the chain diagnostics (batch means, conditional edge probabilities): a third header, tables of its own likewise
 HEADER_DIAGNOSTICS = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip_diagnostics.h")
+# the entries of the learned network priors (block-assignment scan, block counts, partition fold): a fourth header, tables of its own likewise
+HEADER_SBM = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip_sbm.h")
 
 
 class PglError(RuntimeError):
@@ -21,7 +23,7 @@ class PglError(RuntimeError):
 
 _SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "long long": ctypes.c_longlong, "unsigned int": ctypes.c_uint,
             "unsigned long long": ctypes.c_ulonglong, "double": ctypes.c_double, "size_t": ctypes.c_size_t, "uint32_t": ctypes.c_uint32,
-            "uint64_t": ctypes.c_uint64}
+            "uint64_t": ctypes.c_uint64, "uint8_t": ctypes.c_uint8}
 _TYPE_WORDS = {w for t in _SCALARS for w in t.split()} | {"const", "void", "char"}
 _CLASS_NAMES = {"pgl_flip_t": "FlipState", "pgl_chol_t": "CholState", "pgl_dataset_t": "Dataset", "pgl_stage_times_t": "StageTimes",
                 "pgl_sweep_t": "Sweep"}
@@ -101,15 +103,19 @@ with open(HEADER_DIAGNOSTICS) as _fh:
     DIAGNOSTICS_CONSTANTS, _, DIAGNOSTICS_FUNCTIONS = parse_header(_fh.read())
 globals().update(DIAGNOSTICS_CONSTANTS)                           # PGL_DIAG_MAX_LEVELS, PGL_DIAG_EDGE, ...
 DIAGNOSTICS_PARAMS = {f: [p for p, _ in params] for f, (_, params) in DIAGNOSTICS_FUNCTIONS.items()}
+with open(HEADER_SBM) as _fh:
+    SBM_CONSTANTS, _, SBM_FUNCTIONS = parse_header(_fh.read())
+globals().update(SBM_CONSTANTS)                                   # PGL_SBM_MAX_BLOCKS, PGL_SBM_MAX_N, PGL_PURPOSE_SBM
+SBM_PARAMS = {f: [p for p, _ in params] for f, (_, params) in SBM_FUNCTIONS.items()}
 _lib = None
 
 
 def _params(name):
     """the parameter names of entry `name`, of whichever header declares it"""
-    for table in (PARAMS, DISPERSION_PARAMS):
+    for table in (PARAMS, DISPERSION_PARAMS, DIAGNOSTICS_PARAMS):
         if name in table:
             return table[name]
-    return DIAGNOSTICS_PARAMS[name]
+    return SBM_PARAMS[name]
 
 
 def load():
@@ -124,7 +130,7 @@ def load():
     #                      dependency on libamdhip64 has to resolve to the copy torch has loaded (loading the library first leaves
     #                      two runtimes in the process: "no ROCm-capable device is detected" at the first launch)
     lib = ctypes.CDLL(LIB_PATH)
-    for functions in (FUNCTIONS, DISPERSION_FUNCTIONS, DIAGNOSTICS_FUNCTIONS):
+    for functions in (FUNCTIONS, DISPERSION_FUNCTIONS, DIAGNOSTICS_FUNCTIONS, SBM_FUNCTIONS):
         for name, (restype, params) in functions.items():
             fn = getattr(lib, name)     # AttributeError if the export is missing
             fn.argtypes = [t for _, t in params]
@@ -137,13 +143,13 @@ def load():
 
 def source_hash():
     """sha256 (first 16 hex digits) over the kernel sources of the library -- pyglm_amd/csrc/*.hip, *.h and the Makefile, in name order, plus
-    include/pyglm_hip.h: committed hardware-counter summaries (profiles/*.json) record the hash they were taken at, and bench.py quotes them
+    the four headers under include/: committed hardware-counter summaries (profiles/*.json) record the hash they were taken at, and bench.py quotes them
     only while it still matches"""
     import hashlib
     h = hashlib.sha256()
     src = os.path.join(_HERE, "csrc")
     files = [os.path.join(src, f) for f in sorted(os.listdir(src)) if f.endswith((".hip", ".h")) or f == "Makefile"]
-    files += [HEADER, HEADER_DISPERSION, HEADER_DIAGNOSTICS]
+    files += [HEADER, HEADER_DISPERSION, HEADER_DIAGNOSTICS, HEADER_SBM]
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")
         with open(f, "rb") as fh:

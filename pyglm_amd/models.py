@@ -919,6 +919,7 @@ class HierarchicalNonlinearAutoregressiveModel(NonlinearAutoregressiveModel):
     def __init__(self, N, network, regressions, basis=None, B=10, **kw):
         super(HierarchicalNonlinearAutoregressiveModel, self).__init__(N, regressions, basis=basis, B=B, **kw)
         self.network = network
+        self.network_gpu = None          # where a learned adjacency prior scans its block assignments: the tri-state gpu= of simulate()
 
     def resample_model(self):
         self._fresh_stats = None
@@ -948,6 +949,11 @@ class HierarchicalNonlinearAutoregressiveModel(NonlinearAutoregressiveModel):
             # the package's own NIW networks draw from a generator keyed by (seed, sweep) -- identical on every rank, and 20 us to make where
             # re-seeding NumPy's global Mersenne twister and putting it back costs 110 (a sixth of a sweep at BASELINE configs[0])
             net._set_rng(np.random.RandomState(np.random.Philox(key=self.seed & (2 ** 64 - 1), counter=[self.sweeps_done, 0, 2, 0])))
+            # a learned adjacency prior (networks._StochasticBlockAdjacencyMixin) scans its block assignments on the Philox stream
+            # (seed, sweep), on this rank's device where there is one: the same update on every rank from the gathered state, no collective
+            scan_hook = getattr(net, "_set_scan", None)
+            if scan_hook is not None:
+                scan_hook(self.seed, self.sweeps_done, self._network_device())
             try:
                 if _row_stats is not None:
                     net.resample(self._adopt_state()[:2], stats=self._network_stats(_row_stats))
@@ -955,6 +961,8 @@ class HierarchicalNonlinearAutoregressiveModel(NonlinearAutoregressiveModel):
                     net.resample(self._adopt_state()[:2])         # (the network only reads them)
             finally:
                 net._set_rng(None)
+                if scan_hook is not None:
+                    scan_hook(None)
         else:
             state = npr.get_state()
             npr.seed((self.seed * 1000003 + self.sweeps_done) % (2 ** 32))      # a user's network class draws from NumPy's global generator: identical on every rank
@@ -977,6 +985,22 @@ class HierarchicalNonlinearAutoregressiveModel(NonlinearAutoregressiveModel):
             reg._set("_mu_w", np.array(mu[n]))
             reg._set("_rho", np.array(rho[n]))
         self._cache_pushed_hypers(sigma, mu, rho)
+
+    def _network_device(self):
+        """the device a learned adjacency prior updates on, or None for the host (an engine_factory, no GPU, network_gpu = False)"""
+        if not self._on_gpu(self.network_gpu, "resample_network"):
+            return None
+        import torch
+        return self._device or ("cuda:%d" % torch.cuda.current_device())
+
+    def block_structure(self, gpu=None):
+        """sbm.BlockStructure of this chain -- the co-assignment probabilities P(z_i = z_j), the mean of the pushed rho, the trace of
+        occupied blocks -- for a network that learns a partition (SBMSparseNetwork, BetaBernoulliSparseNetwork).  collect() once per
+        kept sweep.  gpu as for simulate(): the folds run on the device when there is one"""
+        from .sbm import BlockStructure
+        if not hasattr(self.network, "block_sizes"):
+            raise TypeError("block_structure(): %s learns no partition" % type(self.network).__name__)
+        return BlockStructure(self, device=self._device, gpu=self._on_gpu(gpu, "block_structure"))
 
     def _cache_block_hypers(self, mu_off, S_off, mu_self, S_self, rho):
         """natural-parameter terms of the shard's rows for a (shared block, self block) push: two table entries and the labels"""

@@ -264,8 +264,101 @@ class _DenseAdjacencyMixin(_NetworkModel):
     rho = property(lambda self: self._rho)
 
 
+class _StochasticBlockAdjacencyMixin(_NetworkModel):
+    """a learned prior on A (the reference's `# TODO: Define the stochastic block models`): K blocks, z_n ~ Cat(pi), A[n][m] ~ Bernoulli(P[z_n][z_m])
+    off the diagonal and Bernoulli(rho_self) on it; pyglm_amd/sbm.py states the law and the update.  State: z (N,), P (K, K), pi (K,), rho_self.
+    The initial state is drawn from the prior with NumPy's global generator unless z is given."""
+
+    def __init__(self, N, B, K=8, a_0=1.0, b_0=1.0, alpha=1.0, a_self=1.0, b_self=1.0, rho_self=None, z=None, **kwargs):
+        from . import sbm
+        _NetworkModel.__init__(self, N, B)
+        self.K = sbm.check_blocks(K)
+        self.a_0, self.b_0, self.alpha, self.a_self, self.b_self = float(a_0), float(b_0), float(alpha), float(a_self), float(b_self)
+        assert min(self.a_0, self.b_0, self.alpha, self.a_self, self.b_self) > 0
+        self._rho_self_fixed = None if rho_self is None else float(rho_self)
+        self.z = np.random.randint(self.K, size=N).astype(np.int64) if z is None else sbm._labels(z, self.K, N).copy()
+        self.P, self.pi = sbm.clamp(np.random.beta(self.a_0, self.b_0, size=(self.K, self.K)), np.random.dirichlet(np.full(self.K, self.alpha / self.K)))
+        self.rho_self = float(np.random.beta(self.a_self, self.b_self)) if rho_self is None else float(rho_self)
+        self._rng = self._scan_ctx = self._driver = None
+
+    def __deepcopy__(self, memo):
+        """the chain state without the device buffers (a driver is rebuilt when it is next needed)"""
+        import copy
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        new.__dict__.update({k: (None if k == "_driver" else copy.deepcopy(v, memo)) for k, v in self.__dict__.items()})
+        return new
+
+    def _set_rng(self, rng):
+        """generator of the conjugate draws (None: NumPy's global one); handed on to the weights' mixin, which draws first"""
+        self._rng = rng
+        up = getattr(super(_StochasticBlockAdjacencyMixin, self), "_set_rng", None)
+        if up is not None:
+            up(rng)
+
+    def _set_scan(self, seed, sweep=0, device=None):
+        """a population model's hook beside _set_rng: the scan of the next resample() takes its uniforms from the Philox stream (seed, sweep)
+        and runs on `device` (None: on the host).  _set_scan(None): back to NumPy's global generator and the host"""
+        self._scan_ctx = None if seed is None else (int(seed), int(sweep), device)
+
+    rho_diag = property(lambda self: self.rho_self, doc="what the diagonal of rho holds")
+    block_sizes = property(lambda self: np.bincount(self.z, minlength=self.K))
+
+    @property
+    def rho(self):
+        """(N, N) as pushed: P[z_n][z_m], rho_diag on the diagonal"""
+        from .sbm import rho_of
+        return rho_of(self.P, self.z, self.rho_diag)
+
+    def resample(self, data=[], **kw):
+        super(_StochasticBlockAdjacencyMixin, self).resample(data, **kw)      # the weights' draws first, exactly as without this mixin
+        self._resample_adjacency(data[0])
+
+    def _resample_adjacency(self, A):
+        from . import sbm
+        rng = np.random if self._rng is None else self._rng
+        kw = dict(a_0=self.a_0, b_0=self.b_0, alpha=self.alpha, a_self=self.a_self, b_self=self.b_self, rho_self=self._rho_self_fixed)
+        if self._scan_ctx is None:
+            kw["u"] = np.random.random_sample(self.N)
+        else:
+            seed, sweep, device = self._scan_ctx
+            kw.update(seed=seed, sweep=sweep)
+            if device is not None and self.K > 1:
+                if self._driver is None or str(self._driver.dev) != str(sbm._device("the block-model update", device)[0]):
+                    self._driver = sbm.DeviceSBM(self.N, self.K, device=device)
+                kw["driver"] = self._driver
+        out = sbm.sbm_host(A, self.z, self.K, rng, **kw)
+        self.z, self.P, self.pi, self.rho_self = out["z"], out["P"], out["pi"], out["rho_self"]
+
+
+class _IndependentBernoulliMixin(_StochasticBlockAdjacencyMixin):
+    """the reference's unfinished class (networks.py: `TODO: Implement the BetaBernoulli class`), finished: one learned connection
+    probability p ~ Beta(a_0, b_0) -- the block model with K = 1 -- and, where the diagonal is special, rho_self ~ Beta(a_0, b_0) of its
+    own; with the flag off the N self-connections pool with the rest"""
+
+    def __init__(self, N, B, a_0=1.0, b_0=1.0, is_diagonal_conn_special=True, **kwargs):
+        _StochasticBlockAdjacencyMixin.__init__(self, N, B, K=1, a_0=a_0, b_0=b_0, a_self=a_0, b_self=b_0)
+        self.is_diagonal_conn_special = bool(is_diagonal_conn_special)
+
+    p = property(lambda self: float(self.P[0, 0]), doc="the learned connection probability")
+    rho_diag = property(lambda self: self.rho_self if self.is_diagonal_conn_special else float(self.P[0, 0]))
+
+    def _resample_adjacency(self, A):
+        if self.is_diagonal_conn_special:
+            return _StochasticBlockAdjacencyMixin._resample_adjacency(self, A)
+        from . import sbm
+        rng = np.random if self._rng is None else self._rng
+        total, cells = int(np.count_nonzero(A)), self.N * self.N
+        self.P = sbm.clamp(np.reshape(rng.beta(self.a_0 + total, self.b_0 + cells - total), (1, 1)), self.pi)[0]
+        self.rho_self = float(self.P[0, 0])
+
+
 def _split(kw):
     return {k: v for k, v in kw.items() if k not in ("rho", "rho_self")}, {k: v for k, v in kw.items() if k in ("rho", "rho_self")}
+
+
+def _split_named(kw, names):
+    return {k: v for k, v in kw.items() if k not in names}, {k: v for k, v in kw.items() if k in names}
 
 
 class FixedMeanDenseNetwork(_DenseAdjacencyMixin, _FixedWeightsMixin):
@@ -306,3 +399,31 @@ class NIWSparseNetwork(_FixedAdjacencyMixin, _IndependentGaussianMixin):
             wkw = {}
         _IndependentGaussianMixin.__init__(self, N, B, **wkw)
         _FixedAdjacencyMixin.__init__(self, N, B, **akw)
+
+
+class BetaBernoulliSparseNetwork(_IndependentBernoulliMixin, _IndependentGaussianMixin):
+    """NIW weights under a learned connection probability.  The weight keywords are treated as for NIWSparseNetwork (REFERENCE_QUIRKS); the
+    adjacency keywords (a_0, b_0, is_diagonal_conn_special) always arrive"""
+    _ADJACENCY_KW = ("a_0", "b_0", "is_diagonal_conn_special")
+
+    def __init__(self, N, B, **kw):
+        wkw, akw = _split_named(kw, self._ADJACENCY_KW)
+        if REFERENCE_QUIRKS:
+            _dropped(type(self).__name__, wkw)
+            wkw = {}
+        _IndependentGaussianMixin.__init__(self, N, B, **wkw)
+        _IndependentBernoulliMixin.__init__(self, N, B, **akw)
+
+
+class SBMSparseNetwork(_StochasticBlockAdjacencyMixin, _IndependentGaussianMixin):
+    """NIW weights under a stochastic block model of the adjacency.  The weight keywords are treated as for NIWSparseNetwork
+    (REFERENCE_QUIRKS); the adjacency keywords (K, a_0, b_0, alpha, a_self, b_self, rho_self, z) always arrive"""
+    _ADJACENCY_KW = ("K", "a_0", "b_0", "alpha", "a_self", "b_self", "rho_self", "z")
+
+    def __init__(self, N, B, **kw):
+        wkw, akw = _split_named(kw, self._ADJACENCY_KW)
+        if REFERENCE_QUIRKS:
+            _dropped(type(self).__name__, wkw)
+            wkw = {}
+        _IndependentGaussianMixin.__init__(self, N, B, **wkw)
+        _StochasticBlockAdjacencyMixin.__init__(self, N, B, **akw)
