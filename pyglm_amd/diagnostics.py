@@ -30,9 +30,15 @@ and contributes its current value.
 R-hat (rhat).  For C >= 2 chains of equal n, from each chain's level-0 mean and variance (ddof = 1): Wv = mean of the variances, Bv = n x the
 variance (ddof = 1) of the means, R-hat = sqrt(((n - 1) / n Wv + Bv / n) / Wv); NaN where Wv = 0.
 """
-import numpy as np
+import ctypes
 
-from .summary import _welford
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import call, ptr
+from .engine import I32, _on_device
+from .summary import _welford, device_engine
 
 MAX_LEVELS = 16                                   # PGL_DIAG_MAX_LEVELS
 SECTIONS = ("edge", "edge_rb", "weight", "bias")  # the device sections, in the order of the accumulators' entries (bit i of `what`)
@@ -179,7 +185,7 @@ def rhat(chains, what=None):
 
 
 class _HostDiag(object):
-    """the accumulators in NumPy, for an engine without diag_alloc: one BatchMeans per section, the interface of _DeviceDiag"""
+    """the accumulators in NumPy, for an engine that is no device engine: one BatchMeans per section, the interface of _DeviceDiag"""
 
     def __init__(self, model, levels, sections):
         nl, N, B = model.n1 - model.n0, model.N, model.B
@@ -204,20 +210,106 @@ class _HostDiag(object):
 
 
 class _DeviceDiag(object):
-    """the same interface on GibbsEngine's device accumulators (engine.diag_alloc / diag_fold / diag_read)"""
+    """the same accumulators in the memory of a GibbsEngine's GPU: zeroed batch means of `levels` dyadic levels for the sections `what` (a bit
+    mask, or names out of SECTIONS) -- the pending / mean / M2 planes, the copies of the state the fold reads (a, and where asked for W, b
+    and the conditional edge probabilities p), and the serial number of the sweep p was last formed from.  Passes the engine's memory gate
+    (reserve; an engine built with mem_budget_bytes stays inside that figure too) BEFORE anything is allocated: MemoryError otherwise."""
 
-    def __init__(self, eng, levels, sections):
-        self.eng = eng
-        self.buf = eng.diag_alloc(levels, sections)
+    @staticmethod
+    def mask(what):
+        """`what` as the bit mask of pgl_diag_fold: an int, or names out of SECTIONS"""
+        if isinstance(what, (int, np.integer)):
+            mask = int(what)
+        else:
+            mask = sum(1 << SECTIONS.index(w) for w in set(what))
+        if mask < 1 or mask > _lib.PGL_DIAG_ALL:
+            raise ValueError("diagnostics: no such sections: %r" % (what,))
+        return mask
 
+    @staticmethod
+    def section_layout(eng, mask):
+        """-> {section: (first entry, entries, shape)} of the sections in `mask`, and the number of entries"""
+        nl, N, B = eng.nloc, eng.N, eng.B
+        shapes = dict(edge=(nl, N), edge_rb=(nl, N), weight=(nl, N, B), bias=(nl,))
+        out, off = {}, 0
+        for i, name in enumerate(SECTIONS):
+            if mask >> i & 1:
+                cnt = int(np.prod(shapes[name]))
+                out[name] = (off, cnt, shapes[name])
+                off += cnt
+        assert off == _lib.load().pgl_diag_entries(N, B, nl, mask)
+        return out, off
+
+    @classmethod
+    def bytes(cls, eng, levels, what):
+        """device bytes the accumulators take: three planes of `levels` doubles per entry (3 * levels * 8 * entries: at N = 1024, B = 5 and 8
+        levels 1.4 GB for all four sections), and the copies of the state the fold reads: a, and where asked for W, b and the conditionals p"""
+        mask = cls.mask(what)
+        lib = _lib.load()
+        if not 1 <= int(levels) <= _lib.PGL_DIAG_MAX_LEVELS:
+            raise ValueError("diagnostics: levels = %r outside 1 .. %d" % (levels, _lib.PGL_DIAG_MAX_LEVELS))
+        state = 4 * eng.nloc * eng.N + 8 * (eng.nloc * eng.N * bool(mask & _lib.PGL_DIAG_EDGE_RB) + eng.nloc * eng.D * bool(mask & _lib.PGL_DIAG_WEIGHT)
+                                            + eng.nloc * bool(mask & _lib.PGL_DIAG_BIAS))
+        return lib.pgl_diag_bytes(lib.pgl_diag_entries(eng.N, eng.B, eng.nloc, mask), int(levels)) + state
+
+    def __init__(self, eng, levels, what):
+        self.eng, self.dev = eng, eng.dev
+        eng.reserve("chain diagnostics: the accumulators need", self.bytes(eng, levels, what), cap=eng._mem_budget)
+        self.levels, self.what = int(levels), self.mask(what)
+        self.layout, self.entries = self.section_layout(eng, self.what)
+        self.pending, self.mean, self.M2 = (eng._z(self.levels, self.entries) for _ in range(3))
+        self.a = eng._z(eng.nloc, eng.N, dtype=I32)
+        self.W = eng._z(eng.nloc, eng.D) if self.what & _lib.PGL_DIAG_WEIGHT else None
+        self.b = eng._z(eng.nloc) if self.what & _lib.PGL_DIAG_BIAS else None
+        self.p = eng._z(eng.nloc, eng.N) if self.what & _lib.PGL_DIAG_EDGE_RB else None
+        self.serial = eng._sweep_serial        # the conditionals of a sweep queued before the allocation are not this chain's
+
+    @_on_device
     def reset(self):
-        self.eng.diag_reset(self.buf)
+        for t in (self.pending, self.mean, self.M2):
+            t.zero_()
+        self.serial = self.eng._sweep_serial
 
+    @_on_device
     def fold(self, a, W, b, k):
-        self.eng.diag_fold(self.buf, a, W, b, k)
+        """sample k (1-based) of the state (a, W, b): one upload of the state, then pgl_diag_fold.  With edge_rb among the sections,
+        pgl_diag_edge_conditional first forms p from the log-odds and the proposal order of the engine's LAST sweep (keep_logodds must
+        have been on for it) and the given a: the conditionals belong to a sweep, so one fold per sweep is the rule -- RuntimeError where
+        the log-odds are absent or no sweep was queued since the previous fold."""
+        eng = self.eng
+        st = eng._st()
+        rb = bool(self.what & _lib.PGL_DIAG_EDGE_RB)
+        if rb:
+            if eng.logodds is None:
+                raise RuntimeError("diagnostics: the conditional edge probabilities need the last sweep's log-odds, and there are none "
+                                   "(engine.keep_logodds must be on before the sweep)")
+            if eng._sweep_serial == self.serial:
+                raise RuntimeError("diagnostics: no sweep since the previous fold -- the conditional edge probabilities belong to a sweep, "
+                                   "one fold per sweep")
+        self.a.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(a).reshape(eng.nloc, eng.N), dtype=np.int32)))
+        if self.W is not None:
+            self.W.copy_(torch.from_numpy(np.ascontiguousarray(W, dtype=np.float64).reshape(eng.nloc, eng.D)))
+        if self.b is not None:
+            self.b.copy_(torch.from_numpy(np.ascontiguousarray(b, dtype=np.float64).reshape(eng.nloc)))
+        if rb:
+            call("pgl_diag_edge_conditional", logodds=ptr(eng.logodds), perm=ctypes.c_void_p(eng._din.data_ptr() + eng._perm_off), a=ptr(self.a),
+                 p=ptr(self.p), nloc=eng.nloc, N=eng.N, hip_stream=st)
+            self.serial = eng._sweep_serial
+        h = eng._tic("diag_fold", float(self.entries))
+        call("pgl_diag_fold", a=ptr(self.a), W=ptr(self.W), b=ptr(self.b), p=ptr(self.p), pending=ptr(self.pending), mean=ptr(self.mean),
+             M2=ptr(self.M2), N=eng.N, B=eng.B, nloc=eng.nloc, levels=self.levels, k=int(k), what=self.what, hip_stream=st)
+        eng._toc(h)
 
-    def read(self, k, section, levels):
-        return self.eng.diag_read(self.buf, k, sections=(section,), levels=levels)[section]
+    @_on_device
+    def read(self, k, section, levels=None):
+        """-> host dict(pending, mean, M2) of one section after k samples, each array (number of levels read,) + the section's shape: edge and
+        edge_rb (nloc, N), weight (nloc, N, B), bias (nloc,).  levels: the levels to read (default: all) -- a read-out needs two of them,
+        and a plane of the weights is 42 MB at N = 1024."""
+        lv = list(range(self.levels)) if levels is None else [int(l) for l in levels]
+        idx = torch.tensor(lv, dtype=torch.int64, device=self.eng.dev)
+        off, cnt, shape = self.layout[section]
+        return {key: t[:, off:off + cnt].index_select(0, idx).cpu().numpy().reshape((len(lv),) + shape)
+                for key, t in (("pending", self.pending), ("mean", self.mean), ("M2", self.M2))}
 
 
 class ChainDiagnostics(object):
@@ -231,7 +323,7 @@ class ChainDiagnostics(object):
         self.model, self.levels = model, _check_levels(levels)
         eng = model.engine
         sections = ["edge"] + (["edge_rb"] if rb else []) + (["weight"] if weights else []) + ["bias"]
-        if hasattr(eng, "diag_alloc"):
+        if device_engine(eng):
             self._acc = _DeviceDiag(eng, self.levels, sections)
             if rb:
                 eng.keep_logodds = True               # the sweeps from now on leave their log-odds (they are bit-equal either way)

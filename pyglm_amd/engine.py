@@ -95,24 +95,6 @@ class _Dataset(object):
     int8, planes, sA, PA, xmax, hooks = False, 0, None, None, None, None
 
 
-class _Summary(object):
-    """device accumulators of one posterior summary (GibbsEngine.summary_alloc): rate / pw per data set, edge, w, b of the state"""
-
-
-class _Rescale(object):
-    """device accumulators of one time-rescaling test (GibbsEngine.rescale_alloc): hist / zsum / ks of the last sample, the running
-    ks_mean, ks_M2, exceed, hist_sum, and the fold's scratch"""
-
-
-class _Dispersion(object):
-    """scratch and results of GibbsEngine.dispersion_stats: the fold's work, L and S per neuron"""
-
-
-class _Diag(object):
-    """device accumulators of one chain diagnostics object (GibbsEngine.diag_alloc): the pending / mean / M2 planes of the batch means, the
-    copies of the state the fold reads, the conditional edge probabilities p, and the serial number of the sweep p was last formed from"""
-
-
 class _I8Scratch(typing.NamedTuple):
     """the integer Gram's scratch (GibbsEngine._i8_reserve)"""
     bytes: int                           # held by the buffers below
@@ -131,7 +113,7 @@ class GibbsEngine(object):
     # observation models (include/pyglm_hip.h, pgl_pg_loglik_ex): the built-in Bernoulli, negative-binomial, Gaussian and binomial regressions,
     # and "hooks" -- any other Polya-gamma model, its a(y), b(y), log c(y) evaluated on the host and kept next to the data (add_data obs_terms)
     OBS = dict([(m.name, m.device) for m in MODELS.values()] + [("hooks", OBS_HOOKS)])
-    _LINK = dict([(m.device, m.link) for m in MODELS.values()] + [(OBS_HOOKS, 0)])     # link0 of pgl_summary_fold (hooks: per neuron, summary_alloc)
+    _LINK = dict([(m.device, m.link) for m in MODELS.values()] + [(OBS_HOOKS, 0)])     # link0 of pgl_summary_fold (hooks: per neuron, summary.py)
 
     def __init__(self, N, B, n0=0, n1=None, device=None, obs="bernoulli", xi=1.0, batch=None, mem_budget_bytes=None,
                  design_only=False, visit_order=True, gram=None, likelihood_only=False, planes=None, i8_group=None, i8_slice=None,
@@ -210,9 +192,9 @@ class GibbsEngine(object):
         self.wait_seconds = 0.0
         self.overlap_seconds = 0.0
         self.launch_seconds = 0.0      # inside the pgl_sweep call itself: ~3 000 launches at the headline size (and, when the queue is full, waiting)
-        self._disp = None              # scratch and results of dispersion_stats, allocated at its first call
-        self._sweep_serial = 0         # sweeps queued so far, and where the last one's perm lies in _din (diag_fold: the conditional edge
-        self._perm_off = None          # probabilities are formed from the last sweep's log-odds and proposal order)
+        self._disp = None              # (work, L, S): scratch and results of dispersion_stats, allocated at its first call
+        self._sweep_serial = 0         # sweeps queued so far, and where the last one's perm lies in _din (the chain diagnostics form the
+        self._perm_off = None          # conditional edge probabilities from the last sweep's log-odds and proposal order)
 
     def _obs_param(self, xi):
         """-> (scalar xi, None) or (1.0, [nloc] device array of the shard's per-neuron values), checked: > 0 (negative binomial), >= 0 (binomial)"""
@@ -653,24 +635,49 @@ class GibbsEngine(object):
              nloc=self.nloc, hip_stream=st)
         self._toc(h)
 
+    def fold_data(self, stage, launch, only=None):
+        """THE walk over the data sets, behind weights the caller has uploaded (_upload_weights): per data set ONE activation, then
+        launch(i, ds, st, first) as the timed stage `stage` (work: T * nloc cells) on the engine's stream st.  first: true for the first
+        data set visited -- the launch overwrites its sums there and adds to them behind it.  only = i: data set i alone.  Returns st, for
+        what the caller queues behind the walk.  Having this method is what makes an engine a device engine to the read-outs of the
+        chain (summary.device_engine)."""
+        st = self._st()
+        first = True
+        for i, ds in enumerate(self.datasets):
+            if only is not None and i != only:
+                continue
+            self._activation(ds, st)
+            h = self._tic(stage, float(ds.T) * self.nloc)
+            launch(i, ds, st, first)
+            self._toc(h)
+            first = False
+        return st
+
+    def reserve(self, what, nbytes, cap=None):
+        """THE memory gate, passed BEFORE anything is allocated: MemoryError where the nbytes that `what` ("<feature>: the ... need")
+        asks for exceed what this engine may still take on its GPU (_free_bytes) -- or cap, where that is less (the chain diagnostics
+        pass the engine's mem_budget_bytes; nobody else does)"""
+        free = self._free_bytes()
+        if cap is not None:
+            free = min(free, int(cap))
+        if nbytes > free:
+            raise MemoryError("%s %d bytes, %d are free on %s" % (what, nbytes, free, self.dev))
+
     def _psi_pass(self, draw, seed, sweep):
         """activation (regression.py:195-201) for the whole shard + PG/kappa/log-lik (:491-511). Returns ll (nloc,) device."""
-        st = self._st()
-        for i, ds in enumerate(self.datasets):
-            self._activation(ds, st)
-            h = self._tic("pg_loglik", float(ds.T) * self.nloc)
+        def launch(i, ds, st, first):
             om = ds.OK if draw else None
             kp = ctypes.c_void_p(ds.OK.data_ptr() + 8 * self.ldn) if draw else None
             if self.obs == OBS_GAUSSIAN:      # self.ll then holds the sums of squared residuals
                 call("pgl_gaussian_stats", Psi=ptr(ds.Psi), ldpsi=self.ldn, bias=ptr(self.bias), Y=ptr(ds.Y), ldy=self.ldn, inv_eta=ptr(self.inv_eta),
-                     Omega=ptr(om), ldo=2 * self.ldn, Kappa=kp, ldk=2 * self.ldn, part=ptr(ds.llpart), sse_out=ptr(self.ll), accumulate=int(i > 0),
-                     T=ds.T, nloc=self.nloc, hip_stream=st)
+                     Omega=ptr(om), ldo=2 * self.ldn, Kappa=kp, ldk=2 * self.ldn, part=ptr(ds.llpart), sse_out=ptr(self.ll),
+                     accumulate=int(not first), T=ds.T, nloc=self.nloc, hip_stream=st)
             else:
                 call("pgl_pg_loglik_ex", Psi=ptr(ds.Psi), ldpsi=self.ldn, bias=ptr(self.bias), Y=ptr(ds.Y), ldy=self.ldn, Omega=ptr(om),
-                     ldo=2 * self.ldn, Kappa=kp, ldk=2 * self.ldn, llpart=ptr(ds.llpart), ll_out=ptr(self.ll), accumulate=int(i > 0), T=ds.T,
-                     nloc=self.nloc, obs=self.obs, xi=self.xi, param=ptr(self.obs_param), hooks=ptr(ds.hooks), ldh=self.ldn, seed=int(seed),
-                     sweep=int(sweep), neuron0=self.n0, elem0=ds.elem0, hip_stream=st)
-            self._toc(h)
+                     ldo=2 * self.ldn, Kappa=kp, ldk=2 * self.ldn, llpart=ptr(ds.llpart), ll_out=ptr(self.ll), accumulate=int(not first),
+                     T=ds.T, nloc=self.nloc, obs=self.obs, xi=self.xi, param=ptr(self.obs_param), hooks=ptr(ds.hooks), ldh=self.ldn,
+                     seed=int(seed), sweep=int(sweep), neuron0=self.n0, elem0=ds.elem0, hip_stream=st)
+        self.fold_data("pg_loglik", launch)
         return self.ll
 
     @_on_device
@@ -711,324 +718,31 @@ class GibbsEngine(object):
         idx = torch.from_numpy(np.ascontiguousarray(cols, dtype=np.int64)).to(self.dev)
         return self.datasets[i].Psi[start:stop].index_select(1, idx).cpu().numpy()
 
-    # ------------------------------------------------------------------ posterior accumulators (pyglm_amd/summary.py)
-    def summary_bytes(self, rates=True, pointwise=False):
-        """device bytes summary_alloc takes: (T_i x ldn) doubles per data set x 2 (rates) + 4 (pointwise), and the state's moments"""
-        per = 2 * bool(rates) + 4 * bool(pointwise)
-        cells = sum(ds.T for ds in self.datasets) * self.ldn
-        return 8 * per * cells + 8 * (self.nloc * self.N + 2 * self.nloc * self.D + 2 * self.nloc) + 4 * self.nloc * self.N
-
-    @_on_device
-    def summary_alloc(self, rates=True, pointwise=False, link=None, link_par=None):
-        """zeroed accumulators for the data sets this engine holds now: per data set the Welford (mean, M2) of the rates and, pointwise, of
-        the log-likelihood term plus its streaming log-sum-exp (m, s); the edge counts and the moments of a * W and b.  Checked against
-        what this engine may still take on its GPU (_free_bytes) BEFORE anything is allocated: MemoryError otherwise.
-        link / link_par: per local neuron, the link code of pgl_summary_fold and its parameter -- required for the rates of the hooks mode,
-        where the engine does not know the neurons' models; the built-in modes take theirs from the observation model."""
-        need, free = self.summary_bytes(rates, pointwise), self._free_bytes()
-        if need > free:
-            raise MemoryError("posterior summary: the accumulators need %d bytes, %d are free on %s" % (need, free, self.dev))
-        s = _Summary()
-        s.ndatasets = len(self.datasets)
-        s.link0, s.link_par0, s.link, s.link_par = self._LINK[self.obs], float(self.xi), None, self.obs_param
-        if self.obs == OBS_HOOKS:
-            s.link_par = None
-            if rates:
-                if link is None:
-                    raise ValueError("the rates of the hooks mode need a link code per neuron")
-                s.link = torch.from_numpy(np.ascontiguousarray(link, dtype=np.int32).reshape(self.nloc)).to(self.dev)
-                s.link_par = torch.from_numpy(np.ascontiguousarray(link_par, dtype=np.float64).reshape(self.nloc)).to(self.dev)
-        s.rate = [(self._z(ds.T, self.ldn), self._z(ds.T, self.ldn)) for ds in self.datasets] if rates else None
-        s.pw = [tuple(self._z(ds.T, self.ldn) for _ in range(4)) for ds in self.datasets] if pointwise else None
-        s.a = self._z(self.nloc, self.N, dtype=I32)
-        s.edge = self._z(self.nloc, self.N)
-        s.w = (self._z(self.nloc, self.D), self._z(self.nloc, self.D))
-        s.b = (self._z(self.nloc), self._z(self.nloc))
-        return s
-
-    @_on_device
-    def summary_reset(self, s):
-        for t in [s.edge, *s.w, *s.b] + [x for grp in (s.rate or []) + (s.pw or []) for x in grp]:
-            t.zero_()
-
-    @_on_device
-    def summary_fold(self, s, a, W, b, k):
-        """sample k (1-based) of the state (a, W, b) into the accumulators s: one upload of the weights, per data set ONE activation and ONE
-        pgl_summary_fold, then pgl_summary_state.  Returns what log_likelihood(a, W, b) returns, to the last bit (the fold forms the
-        per-neuron totals as pgl_pg_loglik_ex / pgl_gaussian_stats do).  Gaussian: set_noise first, as for log_likelihood."""
-        if len(self.datasets) != s.ndatasets:
-            raise RuntimeError("data was added after the posterior summary was allocated: its accumulators cover %d data sets, the engine "
-                               "holds %d (build a new summary)" % (s.ndatasets, len(self.datasets)))
-        self._upload_weights(a, W, b)
-        s.a.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(a).reshape(self.nloc, self.N), dtype=np.int32)))
-        st = self._st()
-        none2, none4 = (None, None), (None,) * 4
-        for i, ds in enumerate(self.datasets):
-            self._activation(ds, st)
-            h = self._tic("summary_fold", float(ds.T) * self.nloc)
-            r, p = s.rate[i] if s.rate else none2, s.pw[i] if s.pw else none4
-            call("pgl_summary_fold", Psi=ptr(ds.Psi), ldn=self.ldn, bias=ptr(self.bias), Y=ptr(ds.Y), llpart=ptr(ds.llpart), ll_out=ptr(self.ll),
-                 accumulate=int(i > 0), T=ds.T, nloc=self.nloc, obs=self.obs, xi=self.xi, param=ptr(self.obs_param), hooks=ptr(ds.hooks),
-                 ldh=self.ldn, inv_eta=ptr(self.inv_eta) if self.obs == OBS_GAUSSIAN else None, rate_mean=ptr(r[0]), rate_M2=ptr(r[1]),
-                 link=ptr(s.link), link0=s.link0, link_par=ptr(s.link_par), link_par0=s.link_par0, l_mean=ptr(p[0]), l_M2=ptr(p[1]),
-                 lse_m=ptr(p[2]), lse_s=ptr(p[3]), k=int(k), hip_stream=st)
-            self._toc(h)
-        call("pgl_summary_state", a=ptr(s.a), Wt=ptr(self.Wt), ldw=self.ldn, bias=ptr(self.bias), edge=ptr(s.edge), w_mean=ptr(s.w[0]),
-             w_M2=ptr(s.w[1]), b_mean=ptr(s.b[0]), b_M2=ptr(s.b[1]), N=self.N, B=self.B, nloc=self.nloc, k=int(k), hip_stream=st)
-        return self._ll_host(self.ll)
-
-    @_on_device
-    def summary_state(self, s, k):
-        """-> host dict(edge_prob (nloc, N), weight_mean, weight_var (nloc, N, B), bias_mean, bias_var (nloc,)) after k samples"""
-        shp = (self.nloc, self.N, self.B)
-        host = lambda t: t.cpu().numpy()           # (the divisions on the host: a count / k there is the correctly rounded quotient)
-        return dict(edge_prob=host(s.edge) / k, weight_mean=host(s.w[0]).reshape(shp), weight_var=host(s.w[1]).reshape(shp) / k,
-                    bias_mean=host(s.b[0]), bias_var=host(s.b[1]) / k)
-
-    @_on_device
-    def summary_rates(self, s, i, k, std=False):
-        """-> host (T_i, nloc): the mean of the rates of data set i over k samples, or their standard deviation (population: M2 / k)"""
-        mean, M2 = s.rate[i]
-        out = torch.sqrt(M2[:, :self.nloc] / k) if std else mean[:, :self.nloc]
-        return out.cpu().numpy()
-
-    @_on_device
-    def summary_pointwise(self, s, k, var=False):
-        """-> host (nloc,): per neuron, the sum over all bins of log mean_s exp(l) = m + log s - log k, or (var) of the sample variance
-        M2 / (k - 1) of l.  Element-wise in torch; the sums over t through pgl_summary_colsum, in the fixed order of the log-likelihood's
-        reduction (torch.sum's order may follow the width of the array)."""
-        out = self._z(self.nloc)
-        st = self._st()
-        for i, ds in enumerate(self.datasets):
-            lmean, lM2, m, sm = s.pw[i]
-            V = lM2 / (k - 1) if var else m + torch.log(sm) - float(np.log(k))
-            call("pgl_summary_colsum", ptr(V), self.ldn, ds.T, self.nloc, ptr(ds.llpart), ptr(out), int(i > 0), st)
-            torch.cuda.current_stream(self.dev).synchronize()        # (V is released below; the launch must have read it)
-        return out.cpu().numpy()
-
-    # ------------------------------------------------------------------ time-rescaling goodness of fit (pyglm_amd/rescale.py)
-    def rescale_bytes(self, bins):
-        """device bytes rescale_alloc takes: the segments' records of the longest data set, and per neuron the two histograms, (sum z, sum z^2),
-        the KS statistic with its moments, and the count of exceedances"""
-        T = max([ds.T for ds in self.datasets] or [0])
-        return _lib.load().pgl_rescale_work_bytes(self.nloc, T) + self.nloc * (12 * int(bins) + 16 + 24 + 4 + 8)
-
-    @_on_device
-    def rescale_alloc(self, bins, par, coef=1.36):
-        """zeroed accumulators of one time-rescaling test with `bins` bins for the data sets this engine holds now.  par: per local neuron
-        (or a scalar) the factor of log1p(exp(psi)) in -log P(y = 0 | psi) -- 1 Bernoulli, xi negative binomial, n binomial: taken from the
-        caller, not from the engine's observation model, so the hooks mode works.  coef: the band is coef / sqrt(M).  Checked against what
-        this engine may still take on its GPU (_free_bytes) BEFORE anything is allocated: MemoryError otherwise."""
-        D = int(bins)
-        need, free = self.rescale_bytes(D), self._free_bytes()
-        if need > free:
-            raise MemoryError("time rescaling: the accumulators need %d bytes, %d are free on %s" % (need, free, self.dev))
-        s = _Rescale()
-        s.D, s.coef, s.ndatasets = D, float(coef), len(self.datasets)
-        par = np.broadcast_to(np.asarray(par, dtype=np.float64).reshape(-1), (self.nloc,))
-        s.qpar0, s.qpar = float(par[0]), None
-        if np.any(par != par[0]):
-            s.qpar = torch.from_numpy(np.array(par)).to(self.dev)
-        s.hist = self._z(self.nloc, D, dtype=I32)
-        s.hist_sum = self._z(self.nloc, D, dtype=torch.int64)
-        s.zsum = self._z(self.nloc, 2)
-        s.ks, s.ks_mean, s.ks_M2 = self._z(self.nloc), self._z(self.nloc), self._z(self.nloc)
-        s.exceed = self._z(self.nloc, dtype=I32)
-        T = max([ds.T for ds in self.datasets] or [0])
-        s.work = torch.empty(_lib.load().pgl_rescale_work_bytes(self.nloc, T), dtype=torch.uint8, device=self.dev)
-        return s
-
-    @_on_device
-    def rescale_reset(self, s):
-        for t in (s.hist, s.hist_sum, s.zsum, s.ks, s.ks_mean, s.ks_M2, s.exceed):
-            t.zero_()
-
-    @_on_device
-    def rescale_fold(self, s, a, W, b, k, seed, only=None):
-        """sample k (1-based) of the state (a, W, b) into the accumulators s: one upload of the weights, per data set ONE activation and ONE
-        pgl_rescale_fold (Philox call k - 1 of `seed`; the data sets behind the first add to the sample's histogram), then pgl_rescale_ks.
-        only = i: data set i alone."""
-        if len(self.datasets) != s.ndatasets:
-            raise RuntimeError("data was added after the time-rescaling test was allocated: its scratch covers %d data sets, the engine "
-                               "holds %d (build a new one)" % (s.ndatasets, len(self.datasets)))
-        self._upload_weights(a, W, b)
-        st = self._st()
-        more = 0
-        for i, ds in enumerate(self.datasets):
-            if only is not None and i != only:
-                continue
-            self._activation(ds, st)
-            h = self._tic("rescale_fold", float(ds.T) * self.nloc)
-            call("pgl_rescale_fold", Psi=ptr(ds.Psi), ldn=self.ldn, bias=ptr(self.bias), Y=ptr(ds.Y), T=ds.T, nloc=self.nloc, qpar=ptr(s.qpar),
-                 qpar0=s.qpar0, D=s.D, seed=int(seed) & (2 ** 64 - 1), draw=(int(k) - 1) & 0xFFFFFFFF, neuron0=self.n0, elem0=ds.elem0,
-                 hist=ptr(s.hist), zsum=ptr(s.zsum), accumulate=more, work=ptr(s.work), hip_stream=st)
-            self._toc(h)
-            more = 1
-        call("pgl_rescale_ks", hist=ptr(s.hist), nloc=self.nloc, D=s.D, coef=s.coef, ks=ptr(s.ks), ks_mean=ptr(s.ks_mean), ks_M2=ptr(s.ks_M2),
-             exceed=ptr(s.exceed), hist_sum=ptr(s.hist_sum), k=int(k), hip_stream=st)
-
-    @_on_device
-    def rescale_read(self, s):
-        """-> host dict: hist (nloc, D) and zsum (nloc, 2) of the last sample, ks of it, ks_mean, ks_M2, exceed over the samples, hist_sum"""
-        host = lambda t: t.cpu().numpy()
-        return dict(hist=host(s.hist).astype(np.int64), zsum=host(s.zsum), ks=host(s.ks), ks_mean=host(s.ks_mean), ks_M2=host(s.ks_M2),
-                    exceed=host(s.exceed).astype(np.int64), hist_sum=host(s.hist_sum))
-
-    @_on_device
-    def rescale_set_par(self, s, par):
-        """replace the factor of log1p(exp(psi)) of the accumulators s (a model that learns xi: the factor moves with the chain)"""
-        par = np.broadcast_to(np.asarray(par, dtype=np.float64).reshape(-1), (self.nloc,))
-        s.qpar0 = float(par[0])
-        if s.qpar is not None:
-            s.qpar.copy_(torch.from_numpy(np.array(par)))
-        elif np.any(par != par[0]):
-            s.qpar = torch.from_numpy(np.array(par)).to(self.dev)
-
     # ------------------------------------------------------------------ the negative-binomial dispersion (pyglm_amd/dispersion.py)
-    def dispersion_bytes(self):
-        """device bytes dispersion_stats takes: the workgroups' partials of the longest data set, and L and S per neuron"""
-        T = max([ds.T for ds in self.datasets] or [0])
-        return _lib.load().pgl_dispersion_work_bytes(self.nloc, T) + 16 * self.nloc
-
     @_on_device
     def dispersion_stats(self, a, W, b, seed, sweep):
         """the sufficient statistics of xi | y, psi at the state (a, W, b) -> (L int64, S float64), host arrays (nloc,): the CRT table counts
         under the engine's CURRENT per-neuron xi (set_obs_param) and sum_t log(1 + e^psi_t), over every data set.  One upload of the
-        weights; per data set ONE activation and ONE pgl_dispersion_fold (dispersion.dispersion_host states what it computes), the data
-        sets behind the first adding to the same sums.  The scratch is allocated at the first call and checked against what this engine
-        may still take on its GPU (_free_bytes) BEFORE that: MemoryError otherwise."""
+        weights, then the walk (fold_data) with ONE pgl_dispersion_fold per data set (dispersion.dispersion_host states what it computes),
+        the data sets behind the first adding to the same sums.  The scratch -- the workgroups' partials of the longest data set, and L and
+        S per neuron -- is allocated at the first call, behind the memory gate (reserve)."""
         if self.obs != OBS_NEGBIN or self.obs_param is None:
             raise ValueError("dispersion_stats(): an engine of the negative-binomial model with one xi per neuron is required")
         T = max([ds.T for ds in self.datasets] or [0])
         need = _lib.load().pgl_dispersion_work_bytes(self.nloc, T)
-        d = self._disp
-        if d is None or d.work.numel() < need:
-            self._disp = d = None
-            total, free = self.dispersion_bytes(), self._free_bytes()
-            if total > free:
-                raise MemoryError("dispersion: the scratch needs %d bytes, %d are free on %s" % (total, free, self.dev))
-            d = self._disp = _Dispersion()
-            d.work = torch.empty(need, dtype=torch.uint8, device=self.dev)
-            d.L, d.S = self._z(self.nloc, dtype=torch.int64), self._z(self.nloc)
+        if self._disp is None or self._disp[0].numel() < need:
+            self._disp = None
+            self.reserve("dispersion: the scratch needs", need + 16 * self.nloc)
+            self._disp = (torch.empty(need, dtype=torch.uint8, device=self.dev), self._z(self.nloc, dtype=torch.int64), self._z(self.nloc))
+        work, L, S = self._disp
         self._upload_weights(a, W, b)
-        st = self._st()
         if not self.datasets:
-            d.L.zero_(), d.S.zero_()              # (with data the first fold, accumulate = 0, overwrites both)
-        for i, ds in enumerate(self.datasets):
-            self._activation(ds, st)
-            h = self._tic("dispersion_fold", float(ds.T) * self.nloc)
-            call("pgl_dispersion_fold", Psi=ptr(ds.Psi), ldn=self.ldn, bias=ptr(self.bias), Y=ptr(ds.Y), T=ds.T, nloc=self.nloc,
-                 xi=ptr(self.obs_param), seed=int(seed) & (2 ** 64 - 1), sweep=int(sweep) & (2 ** 64 - 1), neuron0=self.n0, elem0=ds.elem0,
-                 L=ptr(d.L), S=ptr(d.S), accumulate=int(i > 0), work=ptr(d.work), hip_stream=st)
-            self._toc(h)
-        return d.L.cpu().numpy(), d.S.cpu().numpy()
-
-    # ------------------------------------------------------------------ chain diagnostics (pyglm_amd/diagnostics.py)
-    DIAG_SECTIONS = ("edge", "edge_rb", "weight", "bias")      # in the order of the accumulators' entries; bit i of `what` names section i
-
-    def _diag_what(self, what):
-        """`what` as the bit mask of pgl_diag_fold: an int, or names out of DIAG_SECTIONS"""
-        if isinstance(what, (int, np.integer)):
-            mask = int(what)
-        else:
-            mask = sum(1 << self.DIAG_SECTIONS.index(w) for w in set(what))
-        if mask < 1 or mask > _lib.PGL_DIAG_ALL:
-            raise ValueError("diagnostics: no such sections: %r" % (what,))
-        return mask
-
-    def _diag_layout(self, mask):
-        """-> {section: (first entry, entries, shape)} of the sections in `mask`, and the number of entries"""
-        nl, N, B = self.nloc, self.N, self.B
-        shapes = dict(edge=(nl, N), edge_rb=(nl, N), weight=(nl, N, B), bias=(nl,))
-        out, off = {}, 0
-        for i, name in enumerate(self.DIAG_SECTIONS):
-            if mask >> i & 1:
-                cnt = int(np.prod(shapes[name]))
-                out[name] = (off, cnt, shapes[name])
-                off += cnt
-        assert off == _lib.load().pgl_diag_entries(N, B, nl, mask)
-        return out, off
-
-    def diag_bytes(self, levels, what):
-        """device bytes diag_alloc takes: three planes of `levels` doubles per entry (3 * levels * 8 * entries: at N = 1024, B = 5 and 8 levels
-        1.4 GB for all four sections), and the copies of the state the fold reads: a, and where asked for W, b and the conditionals p"""
-        mask = self._diag_what(what)
-        lib = _lib.load()
-        if not 1 <= int(levels) <= _lib.PGL_DIAG_MAX_LEVELS:
-            raise ValueError("diagnostics: levels = %r outside 1 .. %d" % (levels, _lib.PGL_DIAG_MAX_LEVELS))
-        state = 4 * self.nloc * self.N + 8 * (self.nloc * self.N * bool(mask & _lib.PGL_DIAG_EDGE_RB) + self.nloc * self.D * bool(mask & _lib.PGL_DIAG_WEIGHT)
-                                              + self.nloc * bool(mask & _lib.PGL_DIAG_BIAS))
-        return lib.pgl_diag_bytes(lib.pgl_diag_entries(self.N, self.B, self.nloc, mask), int(levels)) + state
-
-    @_on_device
-    def diag_alloc(self, levels, what):
-        """zeroed batch-means accumulators of `levels` dyadic levels for the sections `what` (a bit mask, or names out of DIAG_SECTIONS).
-        Checked against what this engine may still take on its GPU (_free_bytes; an engine built with mem_budget_bytes stays inside that
-        figure too) BEFORE anything is allocated: MemoryError otherwise."""
-        need, free = self.diag_bytes(levels, what), self._free_bytes()
-        if self._mem_budget is not None:
-            free = min(free, int(self._mem_budget))
-        if need > free:
-            raise MemoryError("chain diagnostics: the accumulators need %d bytes, %d are free on %s" % (need, free, self.dev))
-        s = _Diag()
-        s.levels, s.what = int(levels), self._diag_what(what)
-        s.layout, s.entries = self._diag_layout(s.what)
-        s.pending, s.mean, s.M2 = (self._z(s.levels, s.entries) for _ in range(3))
-        s.a = self._z(self.nloc, self.N, dtype=I32)
-        s.W = self._z(self.nloc, self.D) if s.what & _lib.PGL_DIAG_WEIGHT else None
-        s.b = self._z(self.nloc) if s.what & _lib.PGL_DIAG_BIAS else None
-        s.p = self._z(self.nloc, self.N) if s.what & _lib.PGL_DIAG_EDGE_RB else None
-        s.serial = self._sweep_serial          # the conditionals of a sweep queued before the allocation are not this chain's
-        return s
-
-    @_on_device
-    def diag_reset(self, s):
-        for t in (s.pending, s.mean, s.M2):
-            t.zero_()
-        s.serial = self._sweep_serial
-
-    @_on_device
-    def diag_fold(self, s, a, W, b, k):
-        """sample k (1-based) of the state (a, W, b) into the accumulators s: one upload of the state, then pgl_diag_fold.  With edge_rb among
-        the sections, pgl_diag_edge_conditional first forms p from the log-odds and the proposal order of the LAST sweep (keep_logodds must
-        have been on for it) and the given a: the conditionals belong to a sweep, so one fold per sweep is the rule -- RuntimeError where
-        the log-odds are absent or no sweep was queued since the previous fold."""
-        st = self._st()
-        rb = bool(s.what & _lib.PGL_DIAG_EDGE_RB)
-        if rb:
-            if self.logodds is None:
-                raise RuntimeError("diagnostics: the conditional edge probabilities need the last sweep's log-odds, and there are none "
-                                   "(engine.keep_logodds must be on before the sweep)")
-            if self._sweep_serial == s.serial:
-                raise RuntimeError("diagnostics: no sweep since the previous fold -- the conditional edge probabilities belong to a sweep, "
-                                   "one fold per sweep")
-        s.a.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(a).reshape(self.nloc, self.N), dtype=np.int32)))
-        if s.W is not None:
-            s.W.copy_(torch.from_numpy(np.ascontiguousarray(W, dtype=np.float64).reshape(self.nloc, self.D)))
-        if s.b is not None:
-            s.b.copy_(torch.from_numpy(np.ascontiguousarray(b, dtype=np.float64).reshape(self.nloc)))
-        if rb:
-            call("pgl_diag_edge_conditional", logodds=ptr(self.logodds), perm=ctypes.c_void_p(self._din.data_ptr() + self._perm_off), a=ptr(s.a),
-                 p=ptr(s.p), nloc=self.nloc, N=self.N, hip_stream=st)
-            s.serial = self._sweep_serial
-        h = self._tic("diag_fold", float(s.entries))
-        call("pgl_diag_fold", a=ptr(s.a), W=ptr(s.W), b=ptr(s.b), p=ptr(s.p), pending=ptr(s.pending), mean=ptr(s.mean), M2=ptr(s.M2), N=self.N,
-             B=self.B, nloc=self.nloc, levels=s.levels, k=int(k), what=s.what, hip_stream=st)
-        self._toc(h)
-
-    @_on_device
-    def diag_read(self, s, k, sections=None, levels=None):
-        """-> host {section: dict(pending, mean, M2)} after k samples, each array (number of levels read,) + the section's shape: edge and
-        edge_rb (nloc, N), weight (nloc, N, B), bias (nloc,).  sections: names (default: all of s); levels: the levels to read (default:
-        all) -- a read-out needs two of them, and a plane of the weights is 42 MB at N = 1024."""
-        lv = list(range(s.levels)) if levels is None else [int(l) for l in levels]
-        idx = torch.tensor(lv, dtype=torch.int64, device=self.dev)
-        out = {}
-        for name in (s.layout if sections is None else sections):
-            off, cnt, shape = s.layout[name]
-            out[name] = {key: t[:, off:off + cnt].index_select(0, idx).cpu().numpy().reshape((len(lv),) + shape)
-                         for key, t in (("pending", s.pending), ("mean", s.mean), ("M2", s.M2))}
-        return out
+            L.zero_(), S.zero_()                  # (with data the first fold, accumulate = 0, overwrites both)
+        self.fold_data("dispersion_fold", lambda i, ds, st, first: call(
+            "pgl_dispersion_fold", Psi=ptr(ds.Psi), ldn=self.ldn, bias=ptr(self.bias), Y=ptr(ds.Y), T=ds.T, nloc=self.nloc,
+            xi=ptr(self.obs_param), seed=int(seed) & (2 ** 64 - 1), sweep=int(sweep) & (2 ** 64 - 1), neuron0=self.n0, elem0=ds.elem0,
+            L=ptr(L), S=ptr(S), accumulate=int(not first), work=ptr(work), hip_stream=st))
+        return L.cpu().numpy(), S.cpu().numpy()
 
     # ------------------------------------------------------------------ one Gibbs sweep of the shard's regressions
     def _sweep_args(self, ovs=None):

@@ -717,10 +717,10 @@ class NonlinearAutoregressiveModel(object):
         data = range(len(self.data_list))[data]
         eng = self.engine
         a, W, b = self._local_state()
-        if self._on_gpu(gpu, "rescaled_intervals", host_only=not hasattr(eng, "rescale_alloc")):
-            buf = eng.rescale_alloc(D, par)
-            eng.rescale_fold(buf, a, W, b, 1, seed, only=data)
-            out = eng.rescale_read(buf)
+        if self._on_gpu(gpu, "rescaled_intervals", host_only=not _rs.device_engine(eng)):
+            acc = _rs._DeviceFold(eng, D, par, seed=seed)
+            acc.fold(eng, a, W, b, 1, only=data)
+            out = acc.read()
             hist, zsum = out["hist"], out["zsum"]
         else:
             Y = np.asarray(self.data_list[data][1], dtype=np.float64)[:, self.n0:self.n1]

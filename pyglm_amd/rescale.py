@@ -21,10 +21,13 @@ rescale_host and ks_binned are THE DEFINITION of what pgl_rescale_fold / pgl_res
 with an engine_factory folds through them on the host from engine.psi(...).
 """
 import numpy as np
+import torch
 
 from . import _lib
 from . import simulate as _sim
-from .summary import _welford
+from ._lib import call, ptr
+from .engine import I32, _on_device
+from .summary import _welford, device_engine, model_data
 
 PURPOSE_RESCALE = 3
 PGL_RESCALE_MAX_BINS = _lib.PGL_RESCALE_MAX_BINS    # bins of the histogram of z at most
@@ -146,23 +149,68 @@ class _HostFold(object):
 
 
 class _DeviceFold(object):
-    """the same interface on GibbsEngine's device accumulators (engine.rescale_alloc / rescale_fold / rescale_read)"""
+    """the same accumulators in the memory of a GibbsEngine's GPU, for the data sets the engine holds now: hist / zsum / ks of the last sample,
+    the running ks_mean, ks_M2, exceed, hist_sum, and the fold's scratch.  par: per local neuron (or a scalar) the factor of
+    log1p(exp(psi)) in -log P(y = 0 | psi), taken from the caller, not from the engine's observation model, so the hooks mode works.
+    coef: the band is coef / sqrt(M).  Passes the engine's memory gate (reserve) BEFORE anything is allocated: MemoryError otherwise."""
 
-    def __init__(self, gof, eng):
-        self.g, self.eng = gof, eng
-        self.buf = eng.rescale_alloc(gof.D, gof.par, gof.coef)
+    @staticmethod
+    def bytes(eng, bins):
+        """device bytes the accumulators take: the segments' records of the longest data set, and per neuron the two histograms,
+        (sum z, sum z^2), the KS statistic with its moments, and the count of exceedances"""
+        T = max([ds.T for ds in eng.datasets] or [0])
+        return _lib.load().pgl_rescale_work_bytes(eng.nloc, T) + eng.nloc * (12 * int(bins) + 16 + 24 + 4 + 8)
 
+    def __init__(self, eng, bins, par, coef=1.36, seed=0):
+        self.eng, self.dev = eng, eng.dev
+        self.D, self.coef, self.seed = int(bins), float(coef), int(seed)
+        eng.reserve("time rescaling: the accumulators need", self.bytes(eng, self.D))
+        self.qpar = None
+        self.set_par(par)
+        nl, z = eng.nloc, eng._z
+        self.hist = z(nl, self.D, dtype=I32)
+        self.hist_sum = z(nl, self.D, dtype=torch.int64)
+        self.zsum = z(nl, 2)
+        self.ks, self.ks_mean, self.ks_M2 = z(nl), z(nl), z(nl)
+        self.exceed = z(nl, dtype=I32)
+        T = max([ds.T for ds in eng.datasets] or [0])
+        self.work = torch.empty(_lib.load().pgl_rescale_work_bytes(nl, T), dtype=torch.uint8, device=eng.dev)
+
+    @_on_device
     def reset(self):
-        self.eng.rescale_reset(self.buf)
+        for t in (self.hist, self.hist_sum, self.zsum, self.ks, self.ks_mean, self.ks_M2, self.exceed):
+            t.zero_()
 
+    @_on_device
     def set_par(self, par):
-        self.eng.rescale_set_par(self.buf, par)
+        """replace the factor of log1p(exp(psi)) (a model that learns xi: the factor moves with the chain)"""
+        par = np.broadcast_to(np.asarray(par, dtype=np.float64).reshape(-1), (self.eng.nloc,))
+        self.qpar0 = float(par[0])
+        if self.qpar is not None:
+            self.qpar.copy_(torch.from_numpy(np.array(par)))
+        elif np.any(par != par[0]):
+            self.qpar = torch.from_numpy(np.array(par)).to(self.eng.dev)
 
-    def fold(self, eng, a, W, b, k):
-        eng.rescale_fold(self.buf, a, W, b, k, self.g.seed)
+    @_on_device
+    def fold(self, eng, a, W, b, k, only=None):
+        """sample k (1-based) of the state (a, W, b): one upload of the weights, the walk (engine.fold_data) with ONE pgl_rescale_fold per
+        data set (Philox call k - 1 of the seed; the data sets behind the first add to the sample's histogram), then pgl_rescale_ks.
+        only = i: data set i alone."""
+        assert eng is self.eng
+        eng._upload_weights(a, W, b)
+        st = eng.fold_data("rescale_fold", lambda i, ds, st, first: call(
+            "pgl_rescale_fold", Psi=ptr(ds.Psi), ldn=eng.ldn, bias=ptr(eng.bias), Y=ptr(ds.Y), T=ds.T, nloc=eng.nloc, qpar=ptr(self.qpar),
+            qpar0=self.qpar0, D=self.D, seed=self.seed & (2 ** 64 - 1), draw=(int(k) - 1) & 0xFFFFFFFF, neuron0=eng.n0, elem0=ds.elem0,
+            hist=ptr(self.hist), zsum=ptr(self.zsum), accumulate=int(not first), work=ptr(self.work), hip_stream=st), only=only)
+        call("pgl_rescale_ks", hist=ptr(self.hist), nloc=eng.nloc, D=self.D, coef=self.coef, ks=ptr(self.ks), ks_mean=ptr(self.ks_mean),
+             ks_M2=ptr(self.ks_M2), exceed=ptr(self.exceed), hist_sum=ptr(self.hist_sum), k=int(k), hip_stream=st)
 
+    @_on_device
     def read(self):
-        return self.eng.rescale_read(self.buf)
+        """-> host dict: hist (nloc, D) and zsum (nloc, 2) of the last sample, ks of it, ks_mean, ks_M2, exceed over the samples, hist_sum"""
+        host = lambda t: t.cpu().numpy()
+        return dict(hist=host(self.hist).astype(np.int64), zsum=host(self.zsum), ks=host(self.ks), ks_mean=host(self.ks_mean),
+                    ks_M2=host(self.ks_M2), exceed=host(self.exceed).astype(np.int64), hist_sum=host(self.hist_sum))
 
 
 class TimeRescaling(object):
@@ -175,18 +223,10 @@ class TimeRescaling(object):
     def __init__(self, model, bins=64, seed=0, coef=1.36, datas=None, host=False):
         self.model, self.D, self.seed, self.coef = model, check_bins(bins), int(seed), float(coef)
         self.par = interval_par(model.regressions)[model.n0:model.n1]
-        self.heldout = datas is not None
-        if self.heldout:
-            self._eng = model._heldout_engine(datas)          # held on to: the model's cache keeps one held-out engine only
-            Ys = [np.asarray(d[1] if isinstance(d, tuple) else d) for d in datas]
-        else:
-            self._eng = model.engine
-            Ys = [d[1] for d in model.data_list]
-        if not Ys:
-            raise ValueError("time_rescaling(): the model has no data")
-        self._ndata = len(model.data_list)
-        if hasattr(self._eng, "rescale_alloc") and not host:
-            self._acc = _DeviceFold(self, self._eng)
+        self._eng, Ys = model_data(model, datas, "time_rescaling()")
+        self._nsets = len(Ys)
+        if device_engine(self._eng) and not host:
+            self._acc = _DeviceFold(self._eng, self.D, self.par, self.coef, self.seed)
         else:
             self._acc = _HostFold(self, Ys)
         self.count = 0
@@ -198,9 +238,9 @@ class TimeRescaling(object):
     def collect(self):
         """fold the model's current state: one histogram of z per neuron, its KS statistic into the running moments"""
         m = self.model
-        if not self.heldout and len(m.data_list) != self._ndata:
+        if len(self._eng.datasets) != self._nsets:             # (the accumulators, host or device, are laid out for the data sets of then)
             raise RuntimeError("data was added to the model after time_rescaling(): the test covers %d data sets, the model holds %d "
-                               "(build a new one)" % (self._ndata, len(m.data_list)))
+                               "(build a new one)" % (self._nsets, len(self._eng.datasets)))
         if m._learns_xi():
             # the factor of log1p(exp(psi)) is the CURRENT xi: read again at every sample, and the device copy with it (a fixed xi keeps
             # the single read of the constructor)

@@ -12,12 +12,18 @@ the running moments live on the device and each collected sample is folded into 
             acc.collect()
     acc.edge_prob, acc.weight_mean, acc.rate_mean[0], acc.lppd(), acc.waic()
 
-A model with an engine_factory has no device accumulators: the same class then folds on the host from engine.psi(...), with the update
-formulas of the kernels written in NumPy (_HostAccumulators) -- their specification, and what runs without a GPU.
+The accumulators are one of two classes with one interface: _DeviceAccumulators owns them in the memory of the engine's GPU and folds through
+the kernels; _HostAccumulators, for a model with an engine_factory, folds on the host from engine.psi(...), with the update formulas of the
+kernels written in NumPy -- their specification, and what runs without a GPU.  The time-rescaling test (rescale.py) and the chain
+diagnostics (diagnostics.py) are built the same way and share the three helpers below.
 """
 import numpy as np
+import torch
 
 from . import regression as _regression
+from ._lib import call, ptr
+from .engine import I32, _on_device
+from .regression import OBS_GAUSSIAN, OBS_HOOKS
 
 
 def _welford(mean, M2, x, k):
@@ -25,6 +31,25 @@ def _welford(mean, M2, x, k):
     d = x - mean
     mean += d / k
     M2 += d * (x - mean)
+
+
+def device_engine(eng):
+    """whether the read-outs of the chain keep their accumulators on eng's GPU: a GibbsEngine, which walks its data sets on the device
+    (fold_data); any other engine (an engine_factory's) gets the NumPy twins"""
+    return hasattr(eng, "fold_data")
+
+
+def model_data(model, datas, what):
+    """what a read-out of the chain folds over -> (engine, [Y of every data set]): the model's own engine and stored data, or (datas: a
+    list of held-out recordings) the model's held-out engine of them"""
+    if datas is not None:
+        eng = model._heldout_engine(datas)                   # held on to by the caller: the model's cache keeps one held-out engine only
+        Ys = [np.asarray(d[1] if isinstance(d, tuple) else d) for d in datas]
+    else:
+        eng, Ys = model.engine, [d[1] for d in model.data_list]
+    if not Ys:
+        raise ValueError("%s: the model has no data" % what)
+    return eng, Ys
 
 
 class _HostAccumulators(object):
@@ -107,26 +132,93 @@ class _HostAccumulators(object):
 
 
 class _DeviceAccumulators(object):
-    """the same interface on GibbsEngine's device accumulators (engine.summary_alloc / summary_fold)"""
+    """the same accumulators in the memory of a GibbsEngine's GPU, for the data sets the engine holds now: per data set the Welford (mean, M2)
+    of the rates and, pointwise, of the log-likelihood term plus its streaming log-sum-exp (m, s); the edge counts and the moments of a * W
+    and b.  Passes the engine's memory gate (reserve) BEFORE anything is allocated: MemoryError otherwise.
+    link / link_par: per local neuron, the link code of pgl_summary_fold and its parameter -- required for the rates of the hooks mode,
+    where the engine does not know the neurons' models; the built-in modes take theirs from the observation model."""
 
-    def __init__(self, summary, eng, link, link_par):
-        self.eng = eng
-        self.buf = eng.summary_alloc(rates=summary.rates, pointwise=summary.pointwise, link=link, link_par=link_par)
+    @staticmethod
+    def bytes(eng, rates=True, pointwise=False):
+        """device bytes the accumulators take: (T_i x ldn) doubles per data set x 2 (rates) + 4 (pointwise), and the state's moments"""
+        per = 2 * bool(rates) + 4 * bool(pointwise)
+        cells = sum(ds.T for ds in eng.datasets) * eng.ldn
+        return 8 * per * cells + 8 * (eng.nloc * eng.N + 2 * eng.nloc * eng.D + 2 * eng.nloc) + 4 * eng.nloc * eng.N
 
+    def __init__(self, eng, rates=True, pointwise=False, link=None, link_par=None):
+        self.eng, self.dev = eng, eng.dev
+        eng.reserve("posterior summary: the accumulators need", self.bytes(eng, rates, pointwise))
+        self.link0, self.link_par0, self.link, self.link_par = eng._LINK[eng.obs], float(eng.xi), None, eng.obs_param
+        if eng.obs == OBS_HOOKS:
+            self.link_par = None
+            if rates:
+                if link is None:
+                    raise ValueError("the rates of the hooks mode need a link code per neuron")
+                self.link = torch.from_numpy(np.ascontiguousarray(link, dtype=np.int32).reshape(eng.nloc)).to(eng.dev)
+                self.link_par = torch.from_numpy(np.ascontiguousarray(link_par, dtype=np.float64).reshape(eng.nloc)).to(eng.dev)
+        self.rate = [(eng._z(ds.T, eng.ldn), eng._z(ds.T, eng.ldn)) for ds in eng.datasets] if rates else None
+        self.pw = [tuple(eng._z(ds.T, eng.ldn) for _ in range(4)) for ds in eng.datasets] if pointwise else None
+        self.a = eng._z(eng.nloc, eng.N, dtype=I32)
+        self.edge = eng._z(eng.nloc, eng.N)
+        self.w = (eng._z(eng.nloc, eng.D), eng._z(eng.nloc, eng.D))
+        self.b = (eng._z(eng.nloc), eng._z(eng.nloc))
+
+    @_on_device
     def reset(self):
-        self.eng.summary_reset(self.buf)
+        for t in [self.edge, *self.w, *self.b] + [x for grp in (self.rate or []) + (self.pw or []) for x in grp]:
+            t.zero_()
 
+    @_on_device
     def fold(self, eng, a, W, b, k):
-        return np.asarray(eng.summary_fold(self.buf, a, W, b, k), dtype=np.float64).reshape(-1)
+        """sample k (1-based) of the state (a, W, b): one upload of the weights, the walk (engine.fold_data) with ONE pgl_summary_fold per
+        data set, then pgl_summary_state.  Returns what eng.log_likelihood(a, W, b) returns, to the last bit (the fold forms the
+        per-neuron totals as pgl_pg_loglik_ex / pgl_gaussian_stats do).  Gaussian: set_noise first, as for log_likelihood."""
+        assert eng is self.eng
+        eng._upload_weights(a, W, b)
+        self.a.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(a).reshape(eng.nloc, eng.N), dtype=np.int32)))
+        none2, none4 = (None, None), (None,) * 4
 
+        def launch(i, ds, st, first):
+            r, p = self.rate[i] if self.rate else none2, self.pw[i] if self.pw else none4
+            call("pgl_summary_fold", Psi=ptr(ds.Psi), ldn=eng.ldn, bias=ptr(eng.bias), Y=ptr(ds.Y), llpart=ptr(ds.llpart), ll_out=ptr(eng.ll),
+                 accumulate=int(not first), T=ds.T, nloc=eng.nloc, obs=eng.obs, xi=eng.xi, param=ptr(eng.obs_param), hooks=ptr(ds.hooks),
+                 ldh=eng.ldn, inv_eta=ptr(eng.inv_eta) if eng.obs == OBS_GAUSSIAN else None, rate_mean=ptr(r[0]), rate_M2=ptr(r[1]),
+                 link=ptr(self.link), link0=self.link0, link_par=ptr(self.link_par), link_par0=self.link_par0, l_mean=ptr(p[0]), l_M2=ptr(p[1]),
+                 lse_m=ptr(p[2]), lse_s=ptr(p[3]), k=int(k), hip_stream=st)
+        st = eng.fold_data("summary_fold", launch)
+        call("pgl_summary_state", a=ptr(self.a), Wt=ptr(eng.Wt), ldw=eng.ldn, bias=ptr(eng.bias), edge=ptr(self.edge), w_mean=ptr(self.w[0]),
+             w_M2=ptr(self.w[1]), b_mean=ptr(self.b[0]), b_M2=ptr(self.b[1]), N=eng.N, B=eng.B, nloc=eng.nloc, k=int(k), hip_stream=st)
+        return np.asarray(eng._ll_host(eng.ll), dtype=np.float64).reshape(-1)
+
+    @_on_device
     def state(self, k):
-        return self.eng.summary_state(self.buf, k)
+        """-> host dict(edge_prob (nloc, N), weight_mean, weight_var (nloc, N, B), bias_mean, bias_var (nloc,)) after k samples"""
+        shp = (self.eng.nloc, self.eng.N, self.eng.B)
+        host = lambda t: t.cpu().numpy()           # (the divisions on the host: a count / k there is the correctly rounded quotient)
+        return dict(edge_prob=host(self.edge) / k, weight_mean=host(self.w[0]).reshape(shp), weight_var=host(self.w[1]).reshape(shp) / k,
+                    bias_mean=host(self.b[0]), bias_var=host(self.b[1]) / k)
 
+    @_on_device
     def rates(self, i, k, std=False):
-        return self.eng.summary_rates(self.buf, i, k, std=std)
+        """-> host (T_i, nloc): the mean of the rates of data set i over k samples, or their standard deviation (population: M2 / k)"""
+        mean, M2 = self.rate[i]
+        out = torch.sqrt(M2[:, :self.eng.nloc] / k) if std else mean[:, :self.eng.nloc]
+        return out.cpu().numpy()
 
+    @_on_device
     def pointwise_sums(self, k, var=False):
-        return self.eng.summary_pointwise(self.buf, k, var=var)
+        """-> host (nloc,): per neuron, the sum over all bins of log mean_s exp(l) = m + log s - log k, or (var) of the sample variance
+        M2 / (k - 1) of l.  Element-wise in torch; the sums over t through pgl_summary_colsum, in the fixed order of the log-likelihood's
+        reduction (torch.sum's order may follow the width of the array)."""
+        eng = self.eng
+        out = eng._z(eng.nloc)
+        st = eng._st()
+        for i, ds in enumerate(eng.datasets):
+            lmean, lM2, m, sm = self.pw[i]
+            V = lM2 / (k - 1) if var else m + torch.log(sm) - float(np.log(k))
+            call("pgl_summary_colsum", ptr(V), eng.ldn, ds.T, eng.nloc, ptr(ds.llpart), ptr(out), int(i > 0), st)
+            torch.cuda.current_stream(eng.dev).synchronize()        # (V is released below; the launch must have read it)
+        return out.cpu().numpy()
 
 
 class PosteriorSummary(object):
@@ -137,7 +229,6 @@ class PosteriorSummary(object):
 
     def __init__(self, model, rates=True, pointwise=False, datas=None):
         self.model, self.rates, self.pointwise = model, bool(rates), bool(pointwise)
-        self.heldout = datas is not None
         self.obs = model.engine_obs()
         regs = model.regressions[model.n0:model.n1]
         link = link_par = None
@@ -149,18 +240,10 @@ class PosteriorSummary(object):
                                  "hooks mode need one of the built-in means; summarize(rates=False) works" % (model.n0 + j, type(regs[j]).__name__))
             link = [m.link for m in models]
             link_par = [m.par(r) for m, r in zip(models, regs)]
-        if self.heldout:
-            self._eng = model._heldout_engine(datas)         # held on to: the model's cache keeps one held-out engine only
-            Ys = [np.asarray(d[1] if isinstance(d, tuple) else d) for d in datas]
-        else:
-            self._eng = model.engine
-            Ys = [d[1] for d in model.data_list]
-        if not Ys:
-            raise ValueError("summarize(): the model has no data")
-        self._ndata = len(model.data_list)
+        self._eng, Ys = model_data(model, datas, "summarize()")
         self._nsets = len(Ys)
-        if hasattr(self._eng, "summary_alloc"):
-            self._acc = _DeviceAccumulators(self, self._eng, link, link_par)
+        if device_engine(self._eng):
+            self._acc = _DeviceAccumulators(self._eng, self.rates, self.pointwise, link, link_par)
         else:
             self._acc = _HostAccumulators(self, Ys)
         self.count = 0
@@ -177,9 +260,9 @@ class PosteriorSummary(object):
         """fold the model's current state into the accumulators -> the log-likelihood of the summarised data at that state, equal to
         model.log_likelihood(datas).  One collective (the all-reduce log_likelihood has) with several ranks."""
         m = self.model
-        if not self.heldout and len(m.data_list) != self._ndata:
+        if len(self._eng.datasets) != self._nsets:             # (the accumulators, host or device, are laid out for the data sets of then)
             raise RuntimeError("data was added to the model after summarize(): the accumulators cover %d data sets, the model holds %d "
-                               "(build a new summary)" % (self._ndata, len(m.data_list)))
+                               "(build a new summary)" % (self._nsets, len(self._eng.datasets)))
         a, W, b = m._local_state()
         if self.obs == "gaussian":
             self._eng.set_noise([r.eta for r in m.regressions[m.n0:m.n1]])

@@ -367,9 +367,9 @@ def test_third_header_binds():
     assert _lib.DIAGNOSTICS_CONSTANTS == dict(PGL_DIAG_MAX_LEVELS=16, PGL_DIAG_EDGE=1, PGL_DIAG_EDGE_RB=2, PGL_DIAG_WEIGHT=4, PGL_DIAG_BIAS=8,
                                               PGL_DIAG_ALL=15)
     assert _lib.PGL_DIAG_MAX_LEVELS == D.MAX_LEVELS
-    from pyglm_amd.engine import GibbsEngine
-    assert GibbsEngine.DIAG_SECTIONS == D.SECTIONS and [1 << i for i in range(4)] == [_lib.DIAGNOSTICS_CONSTANTS["PGL_DIAG_" + s.upper()]
-                                                                                      for s in D.SECTIONS]
+    # (the device accumulators take their sections from D.SECTIONS itself: _DeviceDiag.mask / section_layout)
+    assert D._DeviceDiag.mask(D.SECTIONS) == _lib.PGL_DIAG_ALL and [1 << i for i in range(4)] == [_lib.DIAGNOSTICS_CONSTANTS["PGL_DIAG_" + s.upper()]
+                                                                                                   for s in D.SECTIONS]
     # the tables of the other two headers describe those headers alone; pyglm_hip.h still declares its 65
     assert len(_lib.FUNCTIONS) == 65
     for other in (_lib.FUNCTIONS, _lib.DISPERSION_FUNCTIONS):

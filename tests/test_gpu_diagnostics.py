@@ -206,7 +206,7 @@ def test_model_readouts_against_the_definition(kind, B, engine_kwargs):
         A, W = model.adjacency, model.weights
         assert sorted(perm[0].tolist()) == list(range(N))
         # the conditionals the device formed, against the definition from the read-back log-odds, proposal order and state
-        p_dev = diag._acc.buf.p.cpu().numpy()
+        p_dev = diag._acc.p.cpu().numpy()
         p_host = D.edge_conditional_host(lo, perm, A)
         assert np.max(np.abs(p_dev - p_host)) <= 8 * EPS
         stacks["edge"].append(A.astype(float)), stacks["edge_rb"].append(p_dev), stacks["weight"].append(np.where(A[:, :, None], W, 0.0))
@@ -273,6 +273,7 @@ def test_the_device_accumulators_are_the_host_accumulators():
 def test_shards_give_the_rows_of_the_whole_bit_for_bit():
     import torch
     from oracle import pyglm_oracle as orc
+    from pyglm_amd.diagnostics import _DeviceDiag
     from pyglm_amd.engine import GibbsEngine, make_draws, prior_terms
     rng = np.random.default_rng(5)
     N, B, T, levels = 4, 2, 400, 3
@@ -286,7 +287,7 @@ def test_shards_give_the_rows_of_the_whole_bit_for_bit():
         eng = GibbsEngine(N, B, n0, n1, device="cuda:0")
         eng.add_data(Y, basis=basis)
         eng.keep_logodds = True
-        s = eng.diag_alloc(levels, ("edge", "edge_rb", "weight", "bias"))
+        s = _DeviceDiag(eng, levels, ("edge", "edge_rb", "weight", "bias"))
         srng = np.random.default_rng(6)
         a = srng.random((N, N)) < 0.5
         W = srng.standard_normal((N, N, B)) * a[:, :, None]
@@ -296,9 +297,9 @@ def test_shards_give_the_rows_of_the_whole_bit_for_bit():
         for k in range(1, 6):
             perm, u, z = make_draws(1, k, range(n0, n1), N, N * B)
             a, W, b, _ = eng.sweep(a, W, b, rho[sl], hyp[0][sl], hyp[1][sl], hyp[2][sl], hyp[3][sl], hyp[4][sl], perm, u, z, seed=1, sweep=k)
-            eng.diag_fold(s, a, W, b, k)
+            s.fold(a, W, b, k)
         torch.cuda.synchronize()
-        out[(n0, n1)] = (eng.diag_read(s, 5), s.p.cpu().numpy())
+        out[(n0, n1)] = ({what: s.read(5, what) for what in s.layout}, s.p.cpu().numpy())
     whole, p_whole = out[(0, 4)]
     assert np.isnan(p_whole).sum() == 0 and set(np.unique(p_whole[1, 2:3])) <= {0.0, 1.0}
     for (n0, n1) in ((0, 2), (2, 4)):
@@ -337,25 +338,26 @@ def test_one_fold_per_sweep_with_the_conditionals():
 
 def test_memory_is_checked_before_anything_is_allocated():
     import torch
+    from pyglm_amd.diagnostics import _DeviceDiag
     from pyglm_amd.engine import GibbsEngine
     probe = GibbsEngine(4, 2, device="cuda:0")
-    need = probe.diag_bytes(3, 15)
+    need = _DeviceDiag.bytes(probe, 3, 15)
     assert need == 3 * 3 * 8 * 4 * (2 * 4 + 2 * 4 + 1) + 4 * 16 + 8 * (16 + 32 + 4)
     tight = GibbsEngine(4, 2, device="cuda:0", mem_budget_bytes=need - 1)
     torch.cuda.synchronize()
     before = torch.cuda.memory_allocated()
     with pytest.raises(MemoryError, match=r"chain diagnostics: the accumulators need %d bytes, %d are free" % (need, need - 1)):
-        tight.diag_alloc(3, 15)
+        _DeviceDiag(tight, 3, 15)
     assert torch.cuda.memory_allocated() == before
-    assert GibbsEngine(4, 2, device="cuda:0", mem_budget_bytes=need).diag_alloc(3, 15).entries == 4 * 17
+    assert _DeviceDiag(GibbsEngine(4, 2, device="cuda:0", mem_budget_bytes=need), 3, 15).entries == 4 * 17
     from pyglm_amd import models as M
     model = M.SparseBernoulliGLM(4, B=2, seed=1, engine_kwargs=dict(mem_budget_bytes=1000))
     with pytest.raises(MemoryError, match="chain diagnostics"):
         model.diagnose(levels=3)
     with pytest.raises(ValueError, match="levels"):
-        probe.diag_alloc(17, 15)
+        _DeviceDiag(probe, 17, 15)
     with pytest.raises(ValueError, match="no such sections"):
-        probe.diag_alloc(3, 16)
+        _DeviceDiag(probe, 3, 16)
 
 
 # ------------------------------------------------------------------------------------------------ non-interference

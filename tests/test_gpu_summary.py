@@ -168,7 +168,8 @@ def test_memory_error_before_anything_is_allocated(monkeypatch):
     model, Ys = _model(0, 70)
     model.resample_model()
     eng = model.engine
-    need = eng.summary_bytes(True, True)
+    from pyglm_amd.summary import _DeviceAccumulators
+    need = _DeviceAccumulators.bytes(eng, True, True)
     assert need >= 8 * 6 * 500 * 70
     monkeypatch.setattr(type(eng), "_free_bytes", lambda self: need - 1)
     torch.cuda.synchronize()
@@ -324,6 +325,7 @@ def test_full_size_fold_on_a_likelihood_only_engine():
     import gc
     import torch
     from pyglm_amd.engine import GibbsEngine
+    from pyglm_amd.summary import _DeviceAccumulators
     from pyglm_amd.utils.basis import cosine_basis
     N, B, T = 1024, 5, 100000
     rng = np.random.default_rng(0)
@@ -331,7 +333,7 @@ def test_full_size_fold_on_a_likelihood_only_engine():
     Y = (rng.random((T, N)) < 0.08).astype(np.float64)
     eng = GibbsEngine(N, B, likelihood_only=True)
     eng.add_data(Y, basis=basis)
-    s = eng.summary_alloc(rates=True, pointwise=True)
+    s = _DeviceAccumulators(eng, rates=True, pointwise=True)
     ts, ns = rng.integers(0, T, 64), rng.integers(0, N, 64)
     ts[0], ns[0], ts[1], ns[1] = T - 1, N - 1, 0, 0
     Xs = eng.datasets[0].Xt[:N * B, torch.from_numpy(ts).to(eng.dev)].cpu().numpy().T         # (64, D)
@@ -341,7 +343,7 @@ def test_full_size_fold_on_a_likelihood_only_engine():
     mu, l = [], []
     for k in range(1, 4):
         W = W0 + 0.05 * rng.standard_normal((N, N, B))
-        ll = eng.summary_fold(s, a, W, b, k)
+        ll = s.fold(eng, a, W, b, k)
         np.testing.assert_array_equal(ll, eng.log_likelihood(a, W, b))
         aw = (a[:, :, None] * W).reshape(N, N * B)
         psi = np.einsum("cd,cd->c", Xs, aw[ns]) + b[ns]
@@ -356,9 +358,9 @@ def test_full_size_fold_on_a_likelihood_only_engine():
     np.testing.assert_allclose(cell(s.pw[0][0]), l.mean(0), rtol=1e-9)
     np.testing.assert_allclose(cell(s.pw[0][1]) / 2, l.var(0, ddof=1), rtol=0, atol=1e-9 * np.max(l ** 2))
     np.testing.assert_allclose(cell(s.pw[0][2]) + np.log(cell(s.pw[0][3])), logsumexp(l, axis=0), rtol=1e-9)
-    st = eng.summary_state(s, 3)
+    st = s.state(3)
     np.testing.assert_array_equal(st["edge_prob"], a.astype(float))
-    lp = eng.summary_pointwise(s, 3)
+    lp = s.pointwise_sums(3)
     assert lp.shape == (N,) and np.all(np.isfinite(lp)) and np.all(lp < 0)
     del s, eng
     gc.collect()

@@ -101,6 +101,7 @@ def kernels(N, B, levels, reps):
 
 
 def end_to_end(N, B, T, levels, reps):
+    from pyglm_amd.diagnostics import _DeviceDiag
     from pyglm_amd.models import SparseBernoulliGLM
     from pyglm_amd.utils.basis import cosine_basis
     Y = (np.random.default_rng(1).random((T, N)) < 0.05).astype(np.float64)
@@ -125,11 +126,11 @@ def end_to_end(N, B, T, levels, reps):
     plain = model.diagnose(levels=levels, rb=False)
     plain.collect(ll=0.0)
     out["ChainDiagnostics.collect(rb=False)"] = ms([wall(lambda: plain.collect(ll=0.0)) for _ in range(reps)])
-    out["accumulator_bytes_rb_False"] = int(model.engine.diag_bytes(levels, plain.sections))
+    out["accumulator_bytes_rb_False"] = int(_DeviceDiag.bytes(model.engine, levels, plain.sections))
     del plain
     torch.cuda.empty_cache()
     diag = model.diagnose(levels=levels)
-    out["accumulator_bytes"] = int(model.engine.diag_bytes(levels, diag.sections))
+    out["accumulator_bytes"] = int(_DeviceDiag.bytes(model.engine, levels, diag.sections))
     out["sweep_ms"], walls = [], []
     for _ in range(2):                                           # the conditionals belong to a sweep: one collect() per sweep
         out["sweep_ms"].append(wall(model.resample_model))
