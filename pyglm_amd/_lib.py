@@ -15,6 +15,9 @@ HEADER_DISPERSION = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip_d
 HEADER_DIAGNOSTICS = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip_diagnostics.h")
 # the entries of the learned network priors (block-assignment scan, block counts, partition fold): a fourth header, tables of its own likewise
 HEADER_SBM = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip_sbm.h")
+# the entries of the external covariates (offset, fold, draw, the sweep under an offset): a fifth header, tables of its own likewise; it takes
+# pgl_sweep_t from pyglm_hip.h (parse_header's `known`)
+HEADER_COVARIATES = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip_covariates.h")
 
 
 class PglError(RuntimeError):
@@ -29,17 +32,19 @@ _CLASS_NAMES = {"pgl_flip_t": "FlipState", "pgl_chol_t": "CholState", "pgl_datas
                 "pgl_sweep_t": "Sweep"}
 
 
-def parse_header(text):
+def parse_header(text, known=None, header="pyglm_hip.h"):
     """The declarations of a C header in the header's own regular style -> (constants {name: int}, structs {typedef name: ctypes.Structure
     class}, functions {name: (restype, [(parameter name, ctypes type), ...])}). A pointer to a struct typedef of the header is POINTER(its
-    class), every other pointer c_void_p. Raises PglError, naming the declaration, on whatever it cannot classify: no default type."""
+    class), every other pointer -- a pointer to pointers of a scalar type too -- c_void_p. known: the struct classes of a header this one
+    includes ({typedef name: class}); a pointer to one of them is POINTER(its class). header: the header's file name, for the errors. Raises
+    PglError, naming the header and the declaration, on whatever it cannot classify: no default type."""
     consts, structs, funcs = {}, {}, {}
 
     def directive(m):    # '#define PGL_<NAME> <integer>' is a constant and a define without a value an include guard; other directives drop out
         d = re.fullmatch(r"define\s+(\w+)(?:\s+(.*\S))?\s*", m.group(1))
         if d and d.group(2) is not None:
             if not (d.group(1).startswith("PGL_") and re.fullmatch(r"-?\d+", d.group(2))):
-                raise PglError("pyglm_hip.h: '#%s' does not define an integer PGL_ constant" % m.group(1).strip())
+                raise PglError("%s: '#%s' does not define an integer PGL_ constant" % (header, m.group(1).strip()))
             consts[d.group(1)] = int(d.group(2))
         return ""
 
@@ -48,19 +53,19 @@ def parse_header(text):
         base, stars = " ".join(w for w in words if w not in ("const", "*")), words.count("*")
         if stars == 0 and base in _SCALARS:
             return _SCALARS[base]
-        if stars == 1 and base in structs:
-            return ctypes.POINTER(structs[base])
-        if stars == 1 and (base in _SCALARS or base == "void"):
+        if stars == 1 and (base in structs or base in (known or {})):
+            return ctypes.POINTER(structs[base] if base in structs else known[base])
+        if (stars == 1 and (base in _SCALARS or base == "void")) or (stars == 2 and base in _SCALARS):
             return ctypes.c_void_p
-        raise PglError("pyglm_hip.h: unknown type '%s' in: %s" % (spec.strip(), decl))
+        raise PglError("%s: unknown type '%s' in: %s" % (header, spec.strip(), decl))
 
     def named(spec, decl):    # 'type name' or 'type name[DIM]' -> (type text, name, ctypes type)
         m = re.fullmatch(r"(.*[\s*])(\w+)\s*(?:\[\s*(\w+)\s*\])?", spec.strip(), flags=re.S)
         if not m or m.group(2) in _TYPE_WORDS:
-            raise PglError("pyglm_hip.h: no name for '%s' in: %s" % (spec.strip(), decl))
+            raise PglError("%s: no name for '%s' in: %s" % (header, spec.strip(), decl))
         t, dim = ctype(m.group(1), decl), m.group(3)
         if dim is not None and not (dim.isdigit() or dim in consts):
-            raise PglError("pyglm_hip.h: unknown array size '%s' in: %s" % (dim, decl))
+            raise PglError("%s: unknown array size '%s' in: %s" % (header, dim, decl))
         return m.group(1), m.group(2), t if dim is None else t * (int(dim) if dim.isdigit() else consts[dim])
 
     def struct(m):
@@ -69,7 +74,7 @@ def parse_header(text):
             first, *more = decl.split(",")
             spec, name, t = named(first, decl)
             if more and "*" in spec:
-                raise PglError("pyglm_hip.h: several declarators after a pointer type in: %s" % decl)
+                raise PglError("%s: several declarators after a pointer type in: %s" % (header, decl))
             fields += [(name, t)] + [named(spec + d, decl)[1:] for d in more]
         structs[m.group(2)] = type(_CLASS_NAMES.get(m.group(2), m.group(2)), (ctypes.Structure,), {"_fields_": fields})
         return ""
@@ -81,7 +86,7 @@ def parse_header(text):
     for decl in filter(None, (" ".join(d.split()) for d in text.split(";"))):
         m = re.fullmatch(r"(.*[\s*])(\w+)\s*\((.*)\)", decl)
         if not m:
-            raise PglError("pyglm_hip.h: text that is no declaration: %s" % decl)
+            raise PglError("%s: text that is no declaration: %s" % (header, decl))
         ret, name, params = m.groups()
         restype = ctypes.c_char_p if ret.replace("*", " * ").split() == ["const", "char", "*"] else ctype(ret, decl)
         funcs[name] = (restype, [] if params.strip() == "void" else [named(p, decl)[1:] for p in params.split(",")])
@@ -96,23 +101,27 @@ FlipState, CholState, Dataset, StageTimes, Sweep = (_structs[c] for c in _CLASS_
 SIGNATURES = {f: [t for _, t in params] for f, (_, params) in FUNCTIONS.items()}    # symbol -> argument types
 PARAMS = {f: [p for p, _ in params] for f, (_, params) in FUNCTIONS.items()}        # symbol -> parameter names, in the header's order
 with open(HEADER_DISPERSION) as _fh:
-    DISPERSION_CONSTANTS, _, DISPERSION_FUNCTIONS = parse_header(_fh.read())
+    DISPERSION_CONSTANTS, _, DISPERSION_FUNCTIONS = parse_header(_fh.read(), header=os.path.basename(HEADER_DISPERSION))
 globals().update(DISPERSION_CONSTANTS)                            # PGL_PURPOSE_DISPERSION, PGL_DISPERSION_ROWS, ...
 DISPERSION_PARAMS = {f: [p for p, _ in params] for f, (_, params) in DISPERSION_FUNCTIONS.items()}
 with open(HEADER_DIAGNOSTICS) as _fh:
-    DIAGNOSTICS_CONSTANTS, _, DIAGNOSTICS_FUNCTIONS = parse_header(_fh.read())
+    DIAGNOSTICS_CONSTANTS, _, DIAGNOSTICS_FUNCTIONS = parse_header(_fh.read(), header=os.path.basename(HEADER_DIAGNOSTICS))
 globals().update(DIAGNOSTICS_CONSTANTS)                           # PGL_DIAG_MAX_LEVELS, PGL_DIAG_EDGE, ...
 DIAGNOSTICS_PARAMS = {f: [p for p, _ in params] for f, (_, params) in DIAGNOSTICS_FUNCTIONS.items()}
 with open(HEADER_SBM) as _fh:
-    SBM_CONSTANTS, _, SBM_FUNCTIONS = parse_header(_fh.read())
+    SBM_CONSTANTS, _, SBM_FUNCTIONS = parse_header(_fh.read(), header=os.path.basename(HEADER_SBM))
 globals().update(SBM_CONSTANTS)                                   # PGL_SBM_MAX_BLOCKS, PGL_SBM_MAX_N, PGL_PURPOSE_SBM
 SBM_PARAMS = {f: [p for p, _ in params] for f, (_, params) in SBM_FUNCTIONS.items()}
+with open(HEADER_COVARIATES) as _fh:
+    COVARIATES_CONSTANTS, _, COVARIATES_FUNCTIONS = parse_header(_fh.read(), known=_structs, header=os.path.basename(HEADER_COVARIATES))
+globals().update(COVARIATES_CONSTANTS)                            # PGL_COVARIATE_MAX, PGL_COVARIATE_ROWS
+COVARIATES_PARAMS = {f: [p for p, _ in params] for f, (_, params) in COVARIATES_FUNCTIONS.items()}
 _lib = None
 
 
 def _params(name):
     """the parameter names of entry `name`, of whichever header declares it"""
-    for table in (PARAMS, DISPERSION_PARAMS, DIAGNOSTICS_PARAMS):
+    for table in (PARAMS, DISPERSION_PARAMS, DIAGNOSTICS_PARAMS, COVARIATES_PARAMS):
         if name in table:
             return table[name]
     return SBM_PARAMS[name]
@@ -130,7 +139,7 @@ def load():
     #                      dependency on libamdhip64 has to resolve to the copy torch has loaded (loading the library first leaves
     #                      two runtimes in the process: "no ROCm-capable device is detected" at the first launch)
     lib = ctypes.CDLL(LIB_PATH)
-    for functions in (FUNCTIONS, DISPERSION_FUNCTIONS, DIAGNOSTICS_FUNCTIONS, SBM_FUNCTIONS):
+    for functions in (FUNCTIONS, DISPERSION_FUNCTIONS, DIAGNOSTICS_FUNCTIONS, SBM_FUNCTIONS, COVARIATES_FUNCTIONS):
         for name, (restype, params) in functions.items():
             fn = getattr(lib, name)     # AttributeError if the export is missing
             fn.argtypes = [t for _, t in params]
@@ -143,13 +152,13 @@ def load():
 
 def source_hash():
     """sha256 (first 16 hex digits) over the kernel sources of the library -- pyglm_amd/csrc/*.hip, *.h and the Makefile, in name order, plus
-    the four headers under include/: committed hardware-counter summaries (profiles/*.json) record the hash they were taken at, and bench.py quotes them
+    the five headers under include/: committed hardware-counter summaries (profiles/*.json) record the hash they were taken at, and bench.py quotes them
     only while it still matches"""
     import hashlib
     h = hashlib.sha256()
     src = os.path.join(_HERE, "csrc")
     files = [os.path.join(src, f) for f in sorted(os.listdir(src)) if f.endswith((".hip", ".h")) or f == "Makefile"]
-    files += [HEADER, HEADER_DISPERSION, HEADER_DIAGNOSTICS, HEADER_SBM]
+    files += [HEADER, HEADER_DISPERSION, HEADER_DIAGNOSTICS, HEADER_SBM, HEADER_COVARIATES]
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")
         with open(f, "rb") as fh:

@@ -10,6 +10,7 @@
 // binder in any language gets the whole sweep from include/pyglm_hip.h, and pyglm_amd/engine.py is a thin caller of this function.
 #include "pgl_common.h"
 #include "pgl_obs.h"
+#include "../../include/pyglm_hip_covariates.h"
 #include <cmath>
 #include <tuple>
 #include <vector>
@@ -264,7 +265,11 @@ int pgl_stage_times_collect(pgl_stage_times_t* t) {
     return rc;
 }
 
-int pgl_sweep(const pgl_sweep_t* s, uint64_t seed, uint64_t sweep, void* hip_stream) {
+int pgl_sweep(const pgl_sweep_t* s, uint64_t seed, uint64_t sweep, void* hip_stream) { return pgl_sweep_offset(s, nullptr, seed, sweep, hip_stream); }
+
+// the sweep; offsets: NULL, or per data set NULL or the covariates' offset o [T][ldn] (include/pyglm_hip_covariates.h) -- then omega is drawn
+// and ll taken at psi + o, and Kappa leaves reduced by Omega * o: all the rest of the sweep sees of the covariates
+int pgl_sweep_offset(const pgl_sweep_t* s, const double* const* offsets, uint64_t seed, uint64_t sweep, void* hip_stream) {
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     RC(check_gram_args(s));
     PGL_CHECK_ARG(s->B <= 32 && s->n0 >= 0 && (s->obs_param != nullptr || s->obs != 1 || s->xi > 0) && (s->obs_param != nullptr || s->obs != 3 || s->xi >= 0));
@@ -308,6 +313,8 @@ int pgl_sweep(const pgl_sweep_t* s, uint64_t seed, uint64_t sweep, void* hip_str
             RC(pgl_launch_gemm(PGL_GEMM_PLAIN, q, st));
         }
         clk.toc(m);
+        const double* off = offsets ? offsets[i] : nullptr;
+        if (off) RC(pgl_covariate_add_offset(d.Psi + nf, ldn, off + nf, ldn, d.T, nrun, st));
         m = clk.tic(ST_PG, (double)d.T * nrun);
         {   // the neurons [nf, nf + nrun): omega and kappa are the two halves of a row of OK
             PgLlArgs q{};
@@ -323,6 +330,7 @@ int pgl_sweep(const pgl_sweep_t* s, uint64_t seed, uint64_t sweep, void* hip_str
             if (hipMemcpy2DAsync(d.OK, (size_t)2 * ldn * sizeof(double), d.omega_override, (size_t)nloc * sizeof(double), (size_t)nloc * sizeof(double),
                                  (size_t)d.T, hipMemcpyDeviceToDevice, st) != hipSuccess) { pgl_set_error("omega override copy failed"); return PGL_ERR_HIP; }
         }
+        if (off) RC(pgl_covariate_reduce_kappa(d.OK + ldn + nf, 2 * ldn, d.OK + nf, 2 * ldn, off + nf, ldn, d.T, nrun, st));
     }
     // ---- border sums [Omega|Kappa]' [X, 1]  (regression.py:253-260)
     for (int i = 0; i < s->ndatasets; ++i) {

@@ -91,8 +91,8 @@ class BlockPrior(object):
 
 
 class _Dataset(object):
-    # what add_data leaves unset on a data set without the integer Gram or without hooks
-    int8, planes, sA, PA, xmax, hooks = False, 0, None, None, None, None
+    # what add_data leaves unset on a data set without the integer Gram, without hooks or without covariates
+    int8, planes, sA, PA, xmax, hooks, S, Off = False, 0, None, None, None, None, None, None
 
 
 class _I8Scratch(typing.NamedTuple):
@@ -117,14 +117,18 @@ class GibbsEngine(object):
 
     def __init__(self, N, B, n0=0, n1=None, device=None, obs="bernoulli", xi=1.0, batch=None, mem_budget_bytes=None,
                  design_only=False, visit_order=True, gram=None, likelihood_only=False, planes=None, i8_group=None, i8_slice=None,
-                 i8_resident=None, device_share=1):
+                 i8_resident=None, device_share=1, n_covariates=0, covariate_prior=None):
         """device: torch device of this shard (default: the process's current GPU).  design_only: only the design matrix is kept (basis
         convolution).  likelihood_only: activation / log-likelihood / means only -- no sweep buffers, no residue planes (a held-out data
         set costs X', Y and Psi, nothing else).  i8_group / i8_slice / i8_resident: override the integer Gram's plan (_i8_plan) -- neurons
         per product launch, time bins per slice, X's planes kept (True) or converted per slice (False); tests and probes.  device_share: number of
         engines (ranks) that share this GPU -- each then stays inside an equal share of its memory (bench.py's one-GPU dry run of N ranks).
         xi: the negative-binomial xi (obs "negbin") or the binomial number of trials n (obs "binomial"): a scalar, or one value per neuron
-        of the model (N) or of this shard (n1 - n0)."""
+        of the model (N) or of this shard (n1 - n0).  n_covariates = K > 0: every data set carries covariates S (T, K) and an offset
+        Off = S beta' on the device (pyglm_amd/covariates.py); covariate_prior = (mu0, Sigma0) of beta_n, default (0, I)."""
+        from . import covariates as _cov
+        self.K = _cov.check_count(n_covariates)
+        self.cov_prior = _cov.prior_terms(self.K, covariate_prior) if self.K else None
         if not torch.cuda.is_available():
             raise _lib.PglError("pyglm_amd needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU fallback")
         _lib.load()
@@ -323,6 +327,11 @@ class GibbsEngine(object):
         self.Wt = self._z(self.Dp, self.ldn)          # k-major weights for the activation contraction
         self.bias = self._z(nl)
         self.border = self._z(2 * self.ldn, self.Dp)
+        self._cov = None                              # scratch and results of covariate_step, allocated at its first call
+        if self.K:
+            # covariate weights: k-major on the device like the activation's (pgl_covariate_offset), and the host's copy of what is there
+            self.beta_dev = self._z(self.K, self.ldn)
+            self.beta = np.zeros((nl, self.K))
         if self.obs == OBS_GAUSSIAN:
             # Gaussian observations: omega = 1/eta is constant in t, so X'X is formed once per dataset (add_data) and scaled per sweep
             self.G0 = self._z(self.ldj, self.ldj)
@@ -374,13 +383,17 @@ class GibbsEngine(object):
 
     # ------------------------------------------------------------------ data
     @_on_device
-    def add_data(self, Y, X=None, basis=None, obs_terms=None):
+    def add_data(self, Y, X=None, basis=None, obs_terms=None, covariates=None):
         """models.py:66-80: Y is (T, N) counts; X (T, N, B) optional, else built on the device from `basis` (L, B)
         by pgl_design_matrix (utils/basis.py:5-34).  obs_terms (obs "hooks" only, and required there): (A, Bv, logC), the host arrays
-        a(y), b(y), log c(y) of the LOCAL neurons, each (T, n1 - n0) -- kept on the device next to the data set (3 T ldn doubles)."""
+        a(y), b(y), log c(y) of the LOCAL neurons, each (T, n1 - n0) -- kept on the device next to the data set (3 T ldn doubles).
+        covariates (an engine with n_covariates = K > 0 only, and required there): S (T, K), kept on the device with the offset
+        Off = S beta' (T, ldn), which is formed here from the engine's current beta."""
         Y = np.ascontiguousarray(Y, dtype=np.float64)
         T = Y.shape[0]
         assert Y.shape == (T, self.N)
+        from .covariates import check_covariates
+        S_cov = check_covariates(covariates, T, 0 if self.design_only else self.K, "add_data")
         if (obs_terms is not None) != (self.obs == OBS_HOOKS) and not self.design_only:
             raise ValueError("obs_terms are the data of the hooks observation model: required with obs='hooks', and only there")
         if obs_terms is not None:
@@ -420,6 +433,12 @@ class GibbsEngine(object):
             ds.hooks = self._z(T, 3, self.ldn)
             for k in range(3):
                 ds.hooks[:, k, :self.nloc] = torch.from_numpy(np.require(terms[k], requirements=["C", "W"])).to(self.dev)
+        if self.K:
+            # like the hooks' terms, before the batch size and the integer Gram's plan are chosen from the memory left
+            self.reserve("covariates: S and the offset of a data set need", 8 * T * (self.K + self.ldn))
+            ds.S = torch.from_numpy(S_cov).to(self.dev)
+            ds.Off = self._z(T, self.ldn)
+            self._offset(ds, self._st())
         self._ensure_batch()
         ds.Psi = self._z(T, self.ldn)
         if not self.likelihood_only:
@@ -640,13 +659,16 @@ class GibbsEngine(object):
         launch(i, ds, st, first) as the timed stage `stage` (work: T * nloc cells) on the engine's stream st.  first: true for the first
         data set visited -- the launch overwrites its sums there and adds to them behind it.  only = i: data set i alone.  Returns st, for
         what the caller queues behind the walk.  Having this method is what makes an engine a device engine to the read-outs of the
-        chain (summary.device_engine)."""
+        chain (summary.device_engine).  An engine with covariates adds each data set's offset to Psi right behind the activation: the
+        read-outs that walk through here follow beta without knowing of it."""
         st = self._st()
         first = True
         for i, ds in enumerate(self.datasets):
             if only is not None and i != only:
                 continue
             self._activation(ds, st)
+            if self.K:
+                call("pgl_covariate_add_offset", Psi=ptr(ds.Psi), ldpsi=self.ldn, Off=ptr(ds.Off), ldo=self.ldn, T=ds.T, nloc=self.nloc, hip_stream=st)
             h = self._tic(stage, float(ds.T) * self.nloc)
             launch(i, ds, st, first)
             self._toc(h)
@@ -743,6 +765,90 @@ class GibbsEngine(object):
             xi=ptr(self.obs_param), seed=int(seed) & (2 ** 64 - 1), sweep=int(sweep) & (2 ** 64 - 1), neuron0=self.n0, elem0=ds.elem0,
             L=ptr(L), S=ptr(S), accumulate=int(not first), work=ptr(work), hip_stream=st))
         return L.cpu().numpy(), S.cpu().numpy()
+
+    # ------------------------------------------------------------------ external covariates (pyglm_amd/covariates.py)
+    def _offset(self, ds, st):
+        """queues Off = S beta' of data set ds from the weights on the device"""
+        call("pgl_covariate_offset", S=ptr(ds.S), lds=self.K, Beta=ptr(self.beta_dev), Off=ptr(ds.Off), ldn=self.ldn, T=ds.T, nloc=self.nloc,
+             K=self.K, hip_stream=st)
+
+    @_on_device
+    def set_covariate_weights(self, beta):
+        """beta (nloc, K) of this shard's neurons onto the device, and every data set's offset rebuilt from it"""
+        if not self.K:
+            raise ValueError("set_covariate_weights(): this engine was built with n_covariates=0")
+        beta = np.asarray(beta, dtype=np.float64).reshape(self.nloc, self.K)
+        bt = np.zeros((self.K, self.ldn))
+        bt[:, :self.nloc] = beta.T
+        self.beta_dev.copy_(torch.from_numpy(bt))
+        self.beta = beta.copy()
+        st = self._st()
+        for ds in self.datasets:
+            self._offset(ds, st)
+
+    @_on_device
+    def covariate_step(self, a, W, b, seed, sweep, keep=False):
+        """beta | omega, W, b for the shard's neurons, right behind a sweep (covariates.covariate_step_host states it): from the
+        [Omega | Kappa] that sweep left in every data set's OK -- Kappa the reduced one --, the offset it ran under (still in Off) and
+        psi_net at the state (a, W, b) the sweep returned.  One upload of the weights, then per data set one activation and ONE
+        pgl_covariate_fold (the data sets behind the first adding), then pgl_covariate_draw with the host's normals (covariates.
+        covariate_draws: lane 3 of (seed, sweep, global neuron)) and the offsets rebuilt from the new beta, which is returned, (nloc, K).
+        The scratch -- the workgroups' partials of the longest data set, Lambda, r, z, beta and the flags -- is allocated at the first
+        call, behind the memory gate.  keep=True: self.last_covariate_stats = (Lambda (nloc, K (K + 1) / 2), r (nloc, K), z) on the host
+        (tests).  A Lambda_n that is not positive definite (a bad prior) raises np.linalg.LinAlgError naming the neurons; beta and the
+        offsets are then left as they were."""
+        from . import covariates as _cov
+        if not self.K or self.likelihood_only or self.design_only:
+            raise ValueError("covariate_step(): an engine with n_covariates > 0 and sweep buffers is required")
+        K, nl = self.K, self.nloc
+        P = K * (K + 1) // 2
+        T = max([ds.T for ds in self.datasets] or [0])
+        need = _lib.load().pgl_covariate_work_bytes(nl, T, K)
+        if self._cov is None or self._cov["work"].numel() < need:
+            self._cov = None
+            self.reserve("covariates: the step's scratch needs", need + 8 * nl * (P + 3 * K) + 4 * nl + 8 * K * (K + 1))
+            _, _, Lambda0, h0 = self.cov_prior
+            self._cov = dict(work=torch.empty(need, dtype=torch.uint8, device=self.dev), Lam=self._z(nl, P), r=self._z(nl, K), z=self._z(nl, K),
+                             beta=self._z(nl, K), status=self._z(nl, dtype=I32), Lambda0=torch.from_numpy(np.ascontiguousarray(Lambda0)).to(self.dev),
+                             h0=torch.from_numpy(np.ascontiguousarray(h0)).to(self.dev))
+        c = self._cov
+        z = _cov.covariate_draws(seed, sweep, range(self.n0, self.n1), K)
+        c["z"].copy_(torch.from_numpy(z))
+        c["status"].zero_()
+        c["beta"].copy_(torch.from_numpy(self.beta))
+        self._upload_weights(a, W, b)
+        st = self._st()
+        if not self.datasets:
+            c["Lam"].zero_(), c["r"].zero_()
+        for i, ds in enumerate(self.datasets):       # (not fold_data: the fold takes the activation without the offset)
+            self._activation(ds, st)
+            h = self._tic("covariate_fold", float(ds.T) * nl)
+            call("pgl_covariate_fold", Psi=ptr(ds.Psi), ldn=self.ldn, bias=ptr(self.bias), Omega=ptr(ds.OK), ldo=2 * self.ldn,
+                 Kappa=ctypes.c_void_p(ds.OK.data_ptr() + 8 * self.ldn), ldk=2 * self.ldn, Off=ptr(ds.Off), S=ptr(ds.S), lds=K, T=ds.T, nloc=nl, K=K,
+                 Lambda=ptr(c["Lam"]), r=ptr(c["r"]), accumulate=int(i > 0), work=ptr(c["work"]), hip_stream=st)
+            self._toc(h)
+        h = self._tic("covariate_draw")
+        call("pgl_covariate_draw", Lambda=ptr(c["Lam"]), r=ptr(c["r"]), Lambda0=ptr(c["Lambda0"]), h0=ptr(c["h0"]), z=ptr(c["z"]),
+             Beta_out=ptr(c["beta"]), status=ptr(c["status"]), nloc=nl, K=K, hip_stream=st)
+        self._toc(h)
+        status = c["status"].cpu().numpy()
+        if keep:
+            self.last_covariate_stats = (c["Lam"].cpu().numpy(), c["r"].cpu().numpy(), z)
+        if status.any():
+            bad = np.nonzero(status)[0]
+            err = np.linalg.LinAlgError("covariate step: Lambda_n is not positive definite for neurons %s (is covariate_prior's Sigma0 "
+                                        "positive definite?)" % ((bad[:8] + self.n0).tolist(),))
+            err.neurons = (bad + self.n0).tolist()
+            err.beta = c["beta"].cpu().numpy()
+            raise err
+        # (the transposition into the k-major array the offset kernel reads is a strided device copy)
+        self.beta_dev[:, :nl].copy_(c["beta"].t())
+        h = self._tic("covariate_offset")
+        for ds in self.datasets:
+            self._offset(ds, st)
+        self._toc(h)
+        self.beta = c["beta"].cpu().numpy()
+        return self.beta.copy()
 
     # ------------------------------------------------------------------ one Gibbs sweep of the shard's regressions
     def _sweep_args(self, ovs=None):
@@ -851,7 +957,12 @@ class GibbsEngine(object):
         sw.active_rows_bound = (1 + B * int(np.round(rho).sum(axis=1).max())) if det.all() else 0
         sw.flip_single_pass = int(self.flip_single_pass)
         t_launch = time.perf_counter()
-        call("pgl_sweep", ctypes.byref(sw), int(seed), int(sweep), st)
+        if self.K:
+            # under the covariates' offsets: omega and ll at psi + o, Kappa left reduced by Omega * o
+            offs_arr = (ctypes.c_void_p * len(self.datasets))(*[ds.Off.data_ptr() for ds in self.datasets])
+            call("pgl_sweep_offset", ctypes.byref(sw), offs_arr, int(seed), int(sweep), st)
+        else:
+            call("pgl_sweep", ctypes.byref(sw), int(seed), int(sweep), st)
         self.launch_seconds += time.perf_counter() - t_launch
         self.last_row_stats = None
         if want_stats:

@@ -28,15 +28,16 @@ def _dist():
     return None
 
 
-def state_row_layout(N, B):
+def state_row_layout(N, B, K=0):
     """byte layout of one neuron's row of the packed state the ranks exchange: W (N*B doubles) | b (1 double) | eta (1 double: noise variance,
     Gaussian model; 0 otherwise) | row statistics (1 + B + B^2 doubles: count, sum and sum of outer products of the row's active off-diagonal
-    weight vectors -- the network prior's sufficient statistics, networks.py:132-149) | a (N bytes, padded to a multiple of 8)
+    weight vectors -- the network prior's sufficient statistics, networks.py:132-149) | a (N bytes, padded to a multiple of 8) | with K > 0
+    covariates, beta (K doubles: the last 8 K bytes of the row; K = 0 leaves the layout as it always was)
     ->  (offset of b, of eta, of the statistics, of a, bytes per row)"""
     D = N * B
     os_ = 8 * D + 16
     oa = os_ + 8 * (1 + B + B * B)
-    return 8 * D, 8 * D + 8, os_, oa, oa + -(-N // 8) * 8
+    return 8 * D, 8 * D + 8, os_, oa, oa + -(-N // 8) * 8 + 8 * K
 
 
 def host_row_stats(a, W, n0):
@@ -68,8 +69,22 @@ class NonlinearAutoregressiveModel(object):
     """(models.py:8-201) y_n[t] ~ p(f(w_n . x[t])), x = basis-filtered history of all neurons."""
     DRAW_AHEAD_MIN_SIZE = 0            # N*N*B from which the next sweep's host draws are made while the GPU is busy (every size: a small model's sweep leaves the host idle for most of a millisecond)
 
-    def __init__(self, N, regressions, basis=None, B=10, device=None, engine_factory=None, seed=None, engine_kwargs=None, shard=None):
+    def __init__(self, N, regressions, basis=None, B=10, device=None, engine_factory=None, seed=None, engine_kwargs=None, shard=None,
+                 n_covariates=0, covariate_prior=None):
+        """n_covariates = K > 0: every data set carries external covariates S (T, K) shared by all neurons (add_data(..., covariates=S)),
+        neuron n the weights beta_n (model.covariate_weights, (N, K)) with the prior beta_n ~ N(mu0, Sigma0), covariate_prior = (mu0,
+        Sigma0), default (0, I); psi = X . vec(a * W) + b + S beta_n, and resample_model() draws beta right behind the regressions'
+        sweep (pyglm_amd/covariates.py states the law)."""
+        from . import covariates as _cov
         self.N = N
+        self.K = _cov.check_count(n_covariates)
+        if self.K:
+            _cov.prior_terms(self.K, covariate_prior)     # (a mis-shaped prior is refused here, not at the first data set)
+        elif covariate_prior is not None:
+            raise ValueError("covariate_prior was given, but n_covariates=0")
+        self._covariate_prior = covariate_prior
+        self._beta = np.zeros((N, self.K))
+        self.covariates_list = []                        # S of every data set, parallel to data_list (None without covariates)
         assert len(regressions) == N
         self.regressions = regressions
         if basis is None:
@@ -125,6 +140,8 @@ class NonlinearAutoregressiveModel(object):
             self._engine_mode = _regression.device_obs(self.regressions)
             obs, xi = self._engine_mode
             kw = dict(obs=obs, xi=xi)
+            if self.K:
+                kw.update(n_covariates=self.K, covariate_prior=self._covariate_prior)
             kw.update(self._engine_kwargs)
             if self._engine_factory is not None:
                 self._engine = self._engine_factory(self.N, self.B, self.n0, self.n1, **kw)
@@ -163,15 +180,47 @@ class NonlinearAutoregressiveModel(object):
     def biases(self):
         return self._adopt_state()[2].ravel().copy()
 
-    def add_data(self, data, X=None):
-        """(models.py:66-80)"""
+    # ---- external covariates (pyglm_amd/covariates.py)
+    @property
+    def covariate_weights(self):
+        """(N, K) the covariate weights beta, row = neuron; a copy.  Assignable: model.covariate_weights = beta"""
+        return self._beta.copy()
+
+    @covariate_weights.setter
+    def covariate_weights(self, beta):
+        self._beta = np.array(np.broadcast_to(np.asarray(beta, dtype=np.float64), (self.N, self.K)))
+
+    def _sync_covariates(self, eng=None):
+        """this shard's beta onto engine eng (default: the model's own) where it holds another: after set_state(), an assignment to
+        covariate_weights, and for a held-out engine, which was built at an earlier beta.  N K numbers compared; nothing without covariates"""
+        if not self.K:
+            return
+        eng = self.engine if eng is None else eng
+        loc = self._beta[self.n0:self.n1]
+        if not hasattr(eng, "set_covariate_weights"):
+            raise ValueError("a model with covariates needs an engine that takes them: %s has no set_covariate_weights(beta)" % type(eng).__name__)
+        if not np.array_equal(eng.beta, loc):
+            eng.set_covariate_weights(loc)
+
+    def _refuse_covariates(self, what):
+        if self.K:
+            raise ValueError("%s: free-running simulation of a model with covariates (n_covariates=%d) is not supported -- it needs covariates "
+                             "for bins that were never recorded; conditional_simulate() / conditional_check() work" % (what, self.K))
+
+    def add_data(self, data, X=None, covariates=None):
+        """(models.py:66-80)  covariates: S (T, K) of this data set, required with n_covariates = K > 0 and refused without"""
+        from . import covariates as _cov
         N, B = self.N, self.B
         assert isinstance(data, np.ndarray) and data.ndim == 2 and data.shape[1] == self.N
         T = data.shape[0]
         if X is not None:
             assert X.shape == (T, N, B)
+        S = _cov.check_covariates(covariates, T, self.K, "add_data")
         _regression.check_counts(self.regressions, data)
-        ds = self.engine.add_data(data, X=X, basis=self.basis, **self._obs_terms_kw(data))
+        self._sync_covariates()
+        ckw = dict(covariates=S) if self.K else {}
+        ds = self.engine.add_data(data, X=X, basis=self.basis, **ckw, **self._obs_terms_kw(data))
+        self.covariates_list.append(S)
         dist = _dist()
         if dist is not None and hasattr(self.engine, "drop_int8"):
             # gram="auto" looks at the free memory of ITS GPU: make the choice collective (integer path only if every rank can take it), so
@@ -290,9 +339,10 @@ class NonlinearAutoregressiveModel(object):
         return out
 
     # ---- the per-sweep exchange: one packed all_gather
-    def _pack_rows_host(self, a, W, b, eta=None, stats=None):
-        """host (a, W, b[, eta]) of the local rows and their statistics -> packed uint8 rows (state_row_layout)"""
-        ob, oe, os_, oa, rb = state_row_layout(self.N, self.B)
+    def _pack_rows_host(self, a, W, b, eta=None, stats=None, beta=None):
+        """host (a, W, b[, eta]) of the local rows and their statistics -> packed uint8 rows (state_row_layout); beta (rows, K) rides behind
+        each row in a model with covariates"""
+        ob, oe, os_, oa, rb = state_row_layout(self.N, self.B, self.K)
         nl = a.shape[0]
         buf = np.zeros((nl, rb), dtype=np.uint8)
         buf[:, :ob] = np.ascontiguousarray(W, dtype=np.float64).reshape(nl, -1).view(np.uint8)
@@ -302,19 +352,25 @@ class NonlinearAutoregressiveModel(object):
         if stats is not None:
             buf[:, os_:oa] = np.ascontiguousarray(stats, dtype=np.float64).reshape(nl, -1).view(np.uint8)
         buf[:, oa:oa + self.N] = np.asarray(a).astype(np.uint8)
+        if self.K:
+            buf[:, rb - 8 * self.K:] = np.ascontiguousarray(beta, dtype=np.float64).reshape(nl, self.K).view(np.uint8)
         return buf
 
     def _unpack_rows(self, buf):
-        """-> (a, W, b, eta, row statistics) of the rows in buf (n, row bytes): a (n, N) as bytes and W (n, N*B) are strided VIEWS of buf -- the
-        caller stores them into the model's arrays in one pass (_store_rows) --, b, eta and the statistics small copies"""
-        ob, oe, os_, oa, rb = state_row_layout(self.N, self.B)
+        """-> (a, W, b, eta, row statistics, beta) of the rows in buf (n, row bytes): a (n, N) as bytes and W (n, N*B) are strided VIEWS of buf
+        -- the caller stores them into the model's arrays in one pass (_store_rows) --, b, eta and the statistics small copies; beta (n, K) a
+        copy in a model with covariates, None in one without"""
+        ob, oe, os_, oa, rb = state_row_layout(self.N, self.B, self.K)
         n = buf.shape[0]
         W = buf[:, :ob].view(np.float64)
         b = buf[:, ob:oe].view(np.float64).reshape(n).copy()
         eta = buf[:, oe:os_].view(np.float64).reshape(n).copy()
         stats = buf[:, os_:oa].view(np.float64).copy()
         a = buf[:, oa:oa + self.N]
-        return a, W, b, eta, stats
+        beta = None
+        if self.K:
+            beta = np.ascontiguousarray(buf[:, rb - 8 * self.K:rb]).view(np.float64).reshape(n, self.K).copy()
+        return a, W, b, eta, stats, beta
 
     def _gather_start(self, packed):
         """packed: torch uint8 (local rows, row bytes), on the shard's GPU or on the host.  Starts ONE all_gather_into_tensor of it (ranks
@@ -346,7 +402,7 @@ class NonlinearAutoregressiveModel(object):
         return work, out, counts, maxc, packed
 
     def _gather_finish(self, handle):
-        """-> (A, W, b, eta, row statistics) of ALL neurons as host arrays"""
+        """-> (A, W, b, eta, row statistics, beta or None) of ALL neurons as host arrays"""
         import time
         if handle[0] == "deferred":
             handle = self._gather_start(handle[1].cpu())         # (the wait for the sweep is the sweep's time, not the collective's)
@@ -370,13 +426,16 @@ class NonlinearAutoregressiveModel(object):
         self.comm_seconds += time.perf_counter() - t0
         return self._unpack_rows(rows)
 
-    def log_likelihood(self, datas=None):
+    def log_likelihood(self, datas=None, covariates=None):
         """(models.py:82-96) sum over datasets and neurons; `datas` other than the stored data is evaluated through a
-        temporary engine."""
+        temporary engine.  covariates: with datas, in a model with covariates: [S, ...] parallel to datas."""
         if datas is None:
+            if covariates is not None:
+                raise ValueError("log_likelihood(): covariates= goes with datas=; the stored data carry their own")
             eng = self.engine
         else:
-            eng = self._heldout_engine(datas)
+            eng = self._heldout_engine(datas, covariates)
+        self._sync_covariates(eng)
         a, W, b = self._local_state()
         if self.engine_obs() == "gaussian":
             eng.set_noise([r.eta for r in self.regressions[self.n0:self.n1]])
@@ -408,12 +467,13 @@ class NonlinearAutoregressiveModel(object):
         self.collectives += 1
         return out
 
-    def summarize(self, rates=True, pointwise=False, datas=None):
+    def summarize(self, rates=True, pointwise=False, datas=None, covariates=None):
         """a posterior accumulator bound to this model (pyglm_amd/summary.py): call its collect() after every sweep to be kept, read
         edge_prob / weight_mean / rate_mean / lppd() ... at the end.  Allocates its accumulators (on the device, next to the data);
-        changes nothing in the chain.  datas: as for log_likelihood -- None: the stored data; a list: held-out data."""
+        changes nothing in the chain.  datas, covariates: as for log_likelihood -- None: the stored data; a list: held-out data (and
+        their covariates).  In a model with covariates the summary also keeps covariate_mean / covariate_var, (N, K)."""
         from .summary import PosteriorSummary
-        return PosteriorSummary(self, rates=rates, pointwise=pointwise, datas=datas)
+        return PosteriorSummary(self, rates=rates, pointwise=pointwise, datas=datas, covariates=covariates)
 
     def diagnose(self, levels=8, weights=True, rb=True):
         """chain diagnostics bound to this model (pyglm_amd/diagnostics.py: ChainDiagnostics): call its collect() after every sweep to be
@@ -424,31 +484,40 @@ class NonlinearAutoregressiveModel(object):
         from .diagnostics import ChainDiagnostics
         return ChainDiagnostics(self, levels=levels, weights=weights, rb=rb)
 
-    def _heldout_engine(self, datas):
+    def _heldout_engine(self, datas, covariates=None):
         """likelihood-only engine (X', Y, Psi: no sweep buffers, no residue planes) for data other than the stored data, on THIS shard's
-        device; cached by content, so evaluating the same held-out set every iteration uploads it once"""
+        device; cached by content, so evaluating the same held-out set every iteration uploads it once.  covariates: [S, ...] parallel to
+        datas in a model with covariates (required there, refused elsewhere); the engine gets the model's current beta"""
         from .utils.utils import fingerprint
         from .engine import GibbsEngine
+        from . import covariates as _cov
         items = []
-        for d in datas:
+        if covariates is not None and len(covariates) != len(datas):
+            raise ValueError("covariates: %d entries for %d held-out data sets" % (len(covariates), len(datas)))
+        for j, d in enumerate(datas):
             X, Y = d if isinstance(d, tuple) else (None, d)
             if isinstance(X, _LazyX):
                 X = None
-            items.append((X, np.asarray(Y)))
-        key = tuple((None if X is None else fingerprint(X), fingerprint(Y)) for X, Y in items)
+            S = _cov.check_covariates(None if covariates is None else covariates[j], np.asarray(Y).shape[0], self.K, "held-out data set %d" % j)
+            items.append((X, np.asarray(Y), S))
+        key = tuple((None if X is None else fingerprint(X), fingerprint(Y), None if S is None else fingerprint(S)) for X, Y, S in items)
         cache = getattr(self, "_heldout_cache", None)
         if cache is None or cache[0] != key:
             self._heldout_cache = None
             obs, xi = self._engine_mode if self._engine is not None else _regression.device_obs(self.regressions)
             kw = dict(obs=obs, xi=xi, likelihood_only=True)
+            if self.K:
+                kw.update(n_covariates=self.K, covariate_prior=self._covariate_prior)
             if self._engine_factory is not None:
                 eng = self._engine_factory(self.N, self.B, self.n0, self.n1, **kw)
             else:
                 eng = GibbsEngine(self.N, self.B, self.n0, self.n1, device=self.engine.dev, **kw)
-            for X, Y in items:
+            for X, Y, S in items:
                 _regression.check_counts(self.regressions, Y)
-                eng.add_data(Y, X=X, basis=self.basis, **self._obs_terms_kw(Y))
+                ckw = dict(covariates=S) if self.K else {}
+                eng.add_data(Y, X=X, basis=self.basis, **ckw, **self._obs_terms_kw(Y))
             cache = self._heldout_cache = (key, eng)
+        self._sync_covariates(cache[1])
         if self._learns_xi():
             self._push_xi(cache[1])              # (the cached engine was built at an earlier xi)
         return cache[1]
@@ -463,6 +532,7 @@ class NonlinearAutoregressiveModel(object):
     def means(self):
         """(models.py:153-163) E[y | X] per dataset, (T, N): per neuron, from its own observation model"""
         a, W, b = self._local_state()
+        self._sync_covariates()
         obs, par = self._engine_mode if self._engine is not None else _regression.device_obs(self.regressions)
         if self._learns_xi():
             obs, par = _regression.device_obs(self.regressions)      # xi as it is now (a user may have set r.xi since the last sweep)
@@ -501,6 +571,7 @@ class NonlinearAutoregressiveModel(object):
         """(models.py:98-151) forward simulation, serial in t.  gpu=None: on the GPU (pyglm_amd/simulate.py, pgl_generate) whenever one is
         available and the observation model is the built-in Bernoulli or Gaussian one, else the host loop; gpu=True: on the GPU or an
         error; gpu=False: the host loop.  Both paths draw NumPy's global generator in the same order and return the same (X, Y)."""
+        self._refuse_covariates("generate()")
         if T == 0:
             return np.zeros((0, self.N))
         assert isinstance(T, int), "Size must be an integer number of time bins"
@@ -561,6 +632,7 @@ class NonlinearAutoregressiveModel(object):
         the history's last event.  On the device pgl_isi_fold folds them after every launch.
         On a sharded model every rank holds the gathered state: each rank computes the same result on its own device, with no collective."""
         from . import simulate as _sim
+        self._refuse_covariates("simulate()")
         A, W, b = self._adopt_state()
         kind, par = _sim.observation_kinds(self.regressions)
         if _sim.check_isi_bins(isi):
@@ -622,6 +694,7 @@ class NonlinearAutoregressiveModel(object):
         single train, which see refractoriness and bursting: pvalue("isi"), isi_mean, isi_std, each (N, D), and pvalue("cv"), cvs,
         cv_quantiles(q); a Gaussian neuron is refused by name.  Changes nothing in the chain."""
         from .simulate import PredictiveCheck, check_isi_bins
+        self._refuse_covariates("predictive_check()")
         if check_isi_bins(isi):
             self._refuse_gaussian_intervals("predictive_check(isi=%d)" % isi)
         return PredictiveCheck(self, replicates=replicates, seed=seed, data=data, gpu=gpu, lags=lags, isi=isi)
@@ -638,6 +711,7 @@ class NonlinearAutoregressiveModel(object):
         Wm = (W * A[:, :, None]).reshape(N, N * B)
         cols = (free[:, None] * B + np.arange(B)[None, :]).ravel()
         a, Wl, bl = self._local_state()
+        self._sync_covariates()                          # (base comes through fold_data: it carries the covariates' offset)
         a = np.array(a, dtype=bool)
         a[:, free] = False
         if _dist() is None or self._shard_override:     # every column is local: only the window's free columns leave the engine
@@ -697,15 +771,15 @@ class NonlinearAutoregressiveModel(object):
             raise ValueError("conditional_check(gpu=True): a model with an engine_factory takes the NumPy path (gpu=None or False)")
         return ConditionalPrediction(self, free, replicates=replicates, seed=seed, data=data, start=start, stop=stop, gpu=gpu)
 
-    def time_rescaling(self, bins=64, seed=0, coef=1.36, datas=None):
+    def time_rescaling(self, bins=64, seed=0, coef=1.36, datas=None, covariates=None):
         """the time-rescaling goodness-of-fit test of the data under this model's chain (pyglm_amd/rescale.py: TimeRescaling): call its
         collect() after every sweep to be kept -- it reads the recorded data against the current rates, no replicate is simulated --, read
         ks_mean / band / exceed_fraction / failing() at the end.  bins: of the histogram of the rescaled z per neuron, whose binned
         Kolmogorov-Smirnov distance from the uniform law is the statistic; coef / sqrt(M) is the band (1.36: 95 %).  datas: as for
-        summarize -- None: the stored data; a list: held-out recordings.  A Gaussian neuron is refused by name.  Changes nothing in the
-        chain."""
+        summarize -- None: the stored data; a list: held-out recordings (covariates: theirs, in a model with covariates).  A Gaussian
+        neuron is refused by name.  Changes nothing in the chain."""
         from .rescale import TimeRescaling
-        return TimeRescaling(self, bins=bins, seed=seed, coef=coef, datas=datas)
+        return TimeRescaling(self, bins=bins, seed=seed, coef=coef, datas=datas, covariates=covariates)
 
     def rescaled_intervals(self, data=0, bins=64, seed=0, gpu=None):
         """the rescaled intervals of data set `data` at the CURRENT state -> (hist (N, bins) int64, zsum (N, 2) = (sum z, sum z^2))
@@ -717,6 +791,7 @@ class NonlinearAutoregressiveModel(object):
         data = range(len(self.data_list))[data]
         eng = self.engine
         a, W, b = self._local_state()
+        self._sync_covariates()
         if self._on_gpu(gpu, "rescaled_intervals", host_only=not _rs.device_engine(eng)):
             acc = _rs._DeviceFold(eng, D, par, seed=seed)
             acc.fold(eng, a, W, b, 1, only=data)
@@ -780,10 +855,11 @@ class NonlinearAutoregressiveModel(object):
             self.engine.set_noise([r.eta for r in regs])
         elif learns:
             self._push_xi()
+        self._sync_covariates()
         kw = dict(host_overlap=draw_ahead) if self.N * self.N * self.B >= self.DRAW_AHEAD_MIN_SIZE else {}
         exchange = _dist() is not None and not self._shard_override
         handle = []
-        if exchange and not gaussian and not learns and hasattr(self.engine, "packed_state"):
+        if exchange and not gaussian and not learns and not self.K and hasattr(self.engine, "packed_state"):
             # the shard's new rows never visit the host on their own: packed from the sweep's device buffers, gathered, read back once
             kw.update(after_queue=lambda eng: handle.append(self._gather_start(eng.packed_state())), readback=False)
         need_stats = hasattr(getattr(self, "network", None), "weight_blocks")
@@ -793,7 +869,7 @@ class NonlinearAutoregressiveModel(object):
                 kw["want_stats"] = True    # (taken behind the sweep, back in the same wait as the state)
         a, W, b, self.last_loglik_local = self.engine.sweep(a, W, b, rho, Jw, hw, Jb, hb, c0, perm, u, z, self.seed, self.sweeps_done, **kw)
         if handle:
-            A_all, W_all, b_all, flags, stats_all = self._gather_finish(handle[0])
+            A_all, W_all, b_all, flags, stats_all, _ = self._gather_finish(handle[0])
             if np.any(flags != 0):
                 # (the eta slot of a non-Gaussian row carries the sweep's status flags: every rank sees them all and raises the same error,
                 # with its state as it was before the sweep -- regression.py:369-370 raises LinAlgError from np.linalg.cholesky)
@@ -806,6 +882,11 @@ class NonlinearAutoregressiveModel(object):
             self._store_rows(0, self.N, A_all, W_all, b_all)
             self._fresh_stats = stats_all
             return
+        cov_beta = None
+        if self.K:
+            # the covariate weights, directly behind the sweep and before every other step (eta, xi, the network): from the omega the sweep
+            # has just drawn and the weights it returned; the engine's offsets follow, so what comes next sees the new beta
+            cov_beta = self.engine.covariate_step(a, W, b, self.seed, self.sweeps_done)
         if gaussian:
             # noise variances (regression.py:433-445): residual sums of squares under the NEW weights from the device, gamma draws
             # keyed by the global neuron index
@@ -838,6 +919,8 @@ class NonlinearAutoregressiveModel(object):
                     keep = self._stats_kept = host_row_stats(A_, W_, 0)
                 keep[self.n0:self.n1] = stats
             self._store_rows(self.n0, self.n1, a, W, b)
+            if self.K:
+                self._beta[self.n0:self.n1] = cov_beta
             self._fresh_stats = keep if stats is not None else None
             if gaussian:
                 for i, r in enumerate(regs):
@@ -847,10 +930,14 @@ class NonlinearAutoregressiveModel(object):
             return
         if not exchange:
             A_all, W_all, b_all, eta_all, stats_all = a, W, b, (eta if gaussian or learns else None), stats
+            if self.K:
+                self._beta[self.n0:self.n1] = cov_beta
         else:
             import torch
-            packed = torch.from_numpy(self._pack_rows_host(a, W, b, eta if gaussian or learns else None, stats))
-            A_all, W_all, b_all, eta_all, stats_all = self._gather_finish(self._gather_start(packed))
+            packed = torch.from_numpy(self._pack_rows_host(a, W, b, eta if gaussian or learns else None, stats, cov_beta))
+            A_all, W_all, b_all, eta_all, stats_all, beta_all = self._gather_finish(self._gather_start(packed))
+            if self.K:
+                self._beta = beta_all
         self._store_rows(0, self.N, A_all, W_all, b_all)
         self._fresh_stats = stats_all
         if gaussian:
@@ -860,7 +947,7 @@ class NonlinearAutoregressiveModel(object):
             self._store_xi(0 if exchange else self.n0, eta_all)
 
     # ---- chain state (checkpoint / resume; also lets two samplers be run from one state)
-    _STATE_ATTRS = ("regressions", "sweeps_done", "_hyper_cache", "network")
+    _STATE_ATTRS = ("regressions", "sweeps_done", "_hyper_cache", "network", "_beta")
 
     def get_state(self):
         """deep copy of everything a sweep reads or writes on the host: the regressions (a, W, b, hyper-parameters, noise variances), the

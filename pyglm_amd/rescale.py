@@ -220,10 +220,10 @@ class TimeRescaling(object):
     neurons; the read-outs are collective (one gather each, as PosteriorSummary's).  host=True folds in NumPy from engine.psi(...) whatever
     the engine -- what a model with an engine_factory always does."""
 
-    def __init__(self, model, bins=64, seed=0, coef=1.36, datas=None, host=False):
+    def __init__(self, model, bins=64, seed=0, coef=1.36, datas=None, host=False, covariates=None):
         self.model, self.D, self.seed, self.coef = model, check_bins(bins), int(seed), float(coef)
         self.par = interval_par(model.regressions)[model.n0:model.n1]
-        self._eng, Ys = model_data(model, datas, "time_rescaling()")
+        self._eng, Ys = model_data(model, datas, "time_rescaling()", covariates)
         self._nsets = len(Ys)
         if device_engine(self._eng) and not host:
             self._acc = _DeviceFold(self._eng, self.D, self.par, self.coef, self.seed)
@@ -247,6 +247,8 @@ class TimeRescaling(object):
             self.par = interval_par(m.regressions)[m.n0:m.n1]
             self._acc.set_par(self.par)
         a, W, b = m._local_state()
+        if getattr(m, "K", 0):
+            m._sync_covariates(self._eng)
         self._acc.fold(self._eng, a, W, b, self.count + 1)
         self.count += 1
 

@@ -39,11 +39,13 @@ def device_engine(eng):
     return hasattr(eng, "fold_data")
 
 
-def model_data(model, datas, what):
+def model_data(model, datas, what, covariates=None):
     """what a read-out of the chain folds over -> (engine, [Y of every data set]): the model's own engine and stored data, or (datas: a
-    list of held-out recordings) the model's held-out engine of them"""
+    list of held-out recordings; covariates: theirs, in a model with covariates) the model's held-out engine of them"""
+    if datas is None and covariates is not None:
+        raise ValueError("%s: covariates= goes with datas=; the stored data carry their own" % what)
     if datas is not None:
-        eng = model._heldout_engine(datas)                   # held on to by the caller: the model's cache keeps one held-out engine only
+        eng = model._heldout_engine(datas, covariates)                   # held on to by the caller: the model's cache keeps one held-out engine only
         Ys = [np.asarray(d[1] if isinstance(d, tuple) else d) for d in datas]
     else:
         eng, Ys = model.engine, [d[1] for d in model.data_list]
@@ -227,7 +229,7 @@ class PosteriorSummary(object):
     (np.var, ddof = 0).  With several ranks every rank accumulates its own neurons; the per-neuron read-outs are collective (one gather
     each, like model.means), lppd() / waic() all-reduce the N per-neuron values once and sum them in neuron order."""
 
-    def __init__(self, model, rates=True, pointwise=False, datas=None):
+    def __init__(self, model, rates=True, pointwise=False, datas=None, covariates=None):
         self.model, self.rates, self.pointwise = model, bool(rates), bool(pointwise)
         self.obs = model.engine_obs()
         regs = model.regressions[model.n0:model.n1]
@@ -240,7 +242,9 @@ class PosteriorSummary(object):
                                  "hooks mode need one of the built-in means; summarize(rates=False) works" % (model.n0 + j, type(regs[j]).__name__))
             link = [m.link for m in models]
             link_par = [m.par(r) for m, r in zip(models, regs)]
-        self._eng, Ys = model_data(model, datas, "summarize()")
+        self._eng, Ys = model_data(model, datas, "summarize()", covariates)
+        Kc = getattr(model, "K", 0)
+        self._beta = (np.zeros((model.n1 - model.n0, Kc)), np.zeros((model.n1 - model.n0, Kc)))      # N K numbers per sample: host Welford
         self._nsets = len(Ys)
         if device_engine(self._eng):
             self._acc = _DeviceAccumulators(self._eng, self.rates, self.pointwise, link, link_par)
@@ -255,6 +259,7 @@ class PosteriorSummary(object):
         self.count = 0
         self.log_likelihoods = []
         self._xi = (np.zeros_like(self._xi[0]), np.zeros_like(self._xi[1]))
+        self._beta = (np.zeros_like(self._beta[0]), np.zeros_like(self._beta[1]))
 
     def collect(self):
         """fold the model's current state into the accumulators -> the log-likelihood of the summarised data at that state, equal to
@@ -268,8 +273,12 @@ class PosteriorSummary(object):
             self._eng.set_noise([r.eta for r in m.regressions[m.n0:m.n1]])
         elif m._learns_xi():
             m._push_xi(self._eng)
+        if getattr(m, "K", 0):
+            m._sync_covariates(self._eng)
         ll_loc = self._acc.fold(self._eng, a, W, b, self.count + 1)
         self.count += 1
+        if getattr(m, "K", 0):
+            _welford(self._beta[0], self._beta[1], m._beta[m.n0:m.n1], float(self.count))
         # the dispersions are a handful of host numbers per sample: their moments stay on the host (NaN for a neuron without xi)
         xi = np.array([getattr(r, "xi", np.nan) for r in m.regressions[m.n0:m.n1]], dtype=np.float64)
         with np.errstate(invalid="ignore"):
@@ -303,6 +312,13 @@ class PosteriorSummary(object):
 
     xi_mean = property(lambda self: self._xi_moment(0, 1.0), doc="(N,) mean of the negative-binomial xi over the samples; NaN without xi")
     xi_var = property(lambda self: self._xi_moment(1, 1.0 / self.count), doc="(N,) its population variance")
+
+    def _beta_moment(self, i, scale):
+        self._need()
+        return self.model._gather_rows(np.ascontiguousarray(self._beta[i] * scale))
+
+    covariate_mean = property(lambda self: self._beta_moment(0, 1.0), doc="(N, K) mean of the covariate weights beta over the samples")
+    covariate_var = property(lambda self: self._beta_moment(1, 1.0 / self.count), doc="(N, K) their population variance")
 
     def _rates(self, std):
         self._need(rates=True)
