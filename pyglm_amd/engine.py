@@ -117,7 +117,7 @@ class GibbsEngine(object):
 
     def __init__(self, N, B, n0=0, n1=None, device=None, obs="bernoulli", xi=1.0, batch=None, mem_budget_bytes=None,
                  design_only=False, visit_order=True, gram=None, likelihood_only=False, planes=None, i8_group=None, i8_slice=None,
-                 i8_resident=None, device_share=1, n_covariates=0, covariate_prior=None):
+                 i8_resident=None, device_share=1, n_covariates=0, covariate_prior=None, n_latents=0):
         """device: torch device of this shard (default: the process's current GPU).  design_only: only the design matrix is kept (basis
         convolution).  likelihood_only: activation / log-likelihood / means only -- no sweep buffers, no residue planes (a held-out data
         set costs X', Y and Psi, nothing else).  i8_group / i8_slice / i8_resident: override the integer Gram's plan (_i8_plan) -- neurons
@@ -125,9 +125,14 @@ class GibbsEngine(object):
         engines (ranks) that share this GPU -- each then stays inside an equal share of its memory (bench.py's one-GPU dry run of N ranks).
         xi: the negative-binomial xi (obs "negbin") or the binomial number of trials n (obs "binomial"): a scalar, or one value per neuron
         of the model (N) or of this shard (n1 - n0).  n_covariates = K > 0: every data set carries covariates S (T, K) and an offset
-        Off = S beta' on the device (pyglm_amd/covariates.py); covariate_prior = (mu0, Sigma0) of beta_n, default (0, I)."""
+        Off = S beta' on the device (pyglm_amd/covariates.py); covariate_prior = (mu0, Sigma0) of beta_n, default (0, I).  n_latents = Q > 0
+        (pyglm_amd/latents.py): Q further columns of S whose values are sampled (latent_step) -- K becomes n_covariates + Q, S is
+        [S_obs | X] with X zero at add_data, and covariate_prior is the prior of all K weights (latents.joint_prior)."""
         from . import covariates as _cov
-        self.K = _cov.check_count(n_covariates)
+        from . import latents as _lat
+        self.K_obs = _cov.check_count(n_covariates)
+        self.Q = _lat.check_count(n_latents, self.K_obs)
+        self.K = self.K_obs + self.Q
         self.cov_prior = _cov.prior_terms(self.K, covariate_prior) if self.K else None
         if not torch.cuda.is_available():
             raise _lib.PglError("pyglm_amd needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU fallback")
@@ -328,6 +333,7 @@ class GibbsEngine(object):
         self.bias = self._z(nl)
         self.border = self._z(2 * self.ldn, self.Dp)
         self._cov = None                              # scratch and results of covariate_step, allocated at its first call
+        self._lat = None                              # ... and of latent_step
         if self.K:
             # covariate weights: k-major on the device like the activation's (pgl_covariate_offset), and the host's copy of what is there
             self.beta_dev = self._z(self.K, self.ldn)
@@ -388,12 +394,12 @@ class GibbsEngine(object):
         by pgl_design_matrix (utils/basis.py:5-34).  obs_terms (obs "hooks" only, and required there): (A, Bv, logC), the host arrays
         a(y), b(y), log c(y) of the LOCAL neurons, each (T, n1 - n0) -- kept on the device next to the data set (3 T ldn doubles).
         covariates (an engine with n_covariates = K > 0 only, and required there): S (T, K), kept on the device with the offset
-        Off = S beta' (T, ldn), which is formed here from the engine's current beta."""
+        Off = S beta' (T, ldn), which is formed here from the engine's current beta.  An engine with latents appends their Q zero columns."""
         Y = np.ascontiguousarray(Y, dtype=np.float64)
         T = Y.shape[0]
         assert Y.shape == (T, self.N)
         from .covariates import check_covariates
-        S_cov = check_covariates(covariates, T, 0 if self.design_only else self.K, "add_data")
+        S_cov = check_covariates(covariates, T, 0 if self.design_only else self.K_obs, "add_data")
         if (obs_terms is not None) != (self.obs == OBS_HOOKS) and not self.design_only:
             raise ValueError("obs_terms are the data of the hooks observation model: required with obs='hooks', and only there")
         if obs_terms is not None:
@@ -436,7 +442,12 @@ class GibbsEngine(object):
         if self.K:
             # like the hooks' terms, before the batch size and the integer Gram's plan are chosen from the memory left
             self.reserve("covariates: S and the offset of a data set need", 8 * T * (self.K + self.ldn))
-            ds.S = torch.from_numpy(S_cov).to(self.dev)
+            if self.Q:                                # [S_obs | X]: the latent columns start at zero (the first step draws them from the prior)
+                ds.S = self._z(T, self.K)
+                if self.K_obs:
+                    ds.S[:, :self.K_obs] = torch.from_numpy(S_cov).to(self.dev)
+            else:
+                ds.S = torch.from_numpy(S_cov).to(self.dev)
             ds.Off = self._z(T, self.ldn)
             self._offset(ds, self._st())
         self._ensure_batch()
@@ -787,7 +798,7 @@ class GibbsEngine(object):
             self._offset(ds, st)
 
     @_on_device
-    def covariate_step(self, a, W, b, seed, sweep, keep=False):
+    def covariate_step(self, a, W, b, seed, sweep, keep=False, psi_ready=False):
         """beta | omega, W, b for the shard's neurons, right behind a sweep (covariates.covariate_step_host states it): from the
         [Omega | Kappa] that sweep left in every data set's OK -- Kappa the reduced one --, the offset it ran under (still in Off) and
         psi_net at the state (a, W, b) the sweep returned.  One upload of the weights, then per data set one activation and ONE
@@ -796,7 +807,8 @@ class GibbsEngine(object):
         The scratch -- the workgroups' partials of the longest data set, Lambda, r, z, beta and the flags -- is allocated at the first
         call, behind the memory gate.  keep=True: self.last_covariate_stats = (Lambda (nloc, K (K + 1) / 2), r (nloc, K), z) on the host
         (tests).  A Lambda_n that is not positive definite (a bad prior) raises np.linalg.LinAlgError naming the neurons; beta and the
-        offsets are then left as they were."""
+        offsets are then left as they were.  psi_ready=True: every data set's Psi already holds the activation at (a, W, b) and the device
+        the weights (latent_step has just run there): neither is done again."""
         from . import covariates as _cov
         if not self.K or self.likelihood_only or self.design_only:
             raise ValueError("covariate_step(): an engine with n_covariates > 0 and sweep buffers is required")
@@ -816,12 +828,14 @@ class GibbsEngine(object):
         c["z"].copy_(torch.from_numpy(z))
         c["status"].zero_()
         c["beta"].copy_(torch.from_numpy(self.beta))
-        self._upload_weights(a, W, b)
+        if not psi_ready:
+            self._upload_weights(a, W, b)
         st = self._st()
         if not self.datasets:
             c["Lam"].zero_(), c["r"].zero_()
         for i, ds in enumerate(self.datasets):       # (not fold_data: the fold takes the activation without the offset)
-            self._activation(ds, st)
+            if not psi_ready:
+                self._activation(ds, st)
             h = self._tic("covariate_fold", float(ds.T) * nl)
             call("pgl_covariate_fold", Psi=ptr(ds.Psi), ldn=self.ldn, bias=ptr(self.bias), Omega=ptr(ds.OK), ldo=2 * self.ldn,
                  Kappa=ctypes.c_void_p(ds.OK.data_ptr() + 8 * self.ldn), ldk=2 * self.ldn, Off=ptr(ds.Off), S=ptr(ds.S), lds=K, T=ds.T, nloc=nl, K=K,
@@ -849,6 +863,73 @@ class GibbsEngine(object):
         self._toc(h)
         self.beta = c["beta"].cpu().numpy()
         return self.beta.copy()
+
+    # ------------------------------------------------------------------ latent common input (pyglm_amd/latents.py)
+    def _need_latents(self, what):
+        if not self.Q:
+            raise ValueError("%s: this engine was built with n_latents=0" % what)
+
+    @_on_device
+    def latents(self, i=0):
+        """X (T_i, Q) of data set i: a host copy of the latent columns of its S"""
+        self._need_latents("latents()")
+        return self.datasets[i].S[:, self.K_obs:].cpu().numpy().copy()
+
+    @_on_device
+    def set_latents(self, i, X):
+        """X (T_i, Q) into the latent columns of data set i's S, and that data set's offset rebuilt from it"""
+        from .latents import check_latents
+        self._need_latents("set_latents()")
+        ds = self.datasets[i]
+        ds.S[:, self.K_obs:] = torch.from_numpy(check_latents(X, ds.T, self.Q)).to(self.dev)
+        self._offset(ds, self._st())
+
+    @_on_device
+    def latent_step(self, a, W, b, seed, sweep, keep=False):
+        """x_t | omega, W, b, beta for every time bin of every data set, right behind a sweep and BEFORE covariate_step (latents.
+        latent_step_host states it): from the [Omega | Kappa] that sweep left in every data set's OK -- Kappa the reduced one --, the
+        latent columns it ran under (still in S), the loadings in beta_dev and psi_net at the state (a, W, b) the sweep returned.  One
+        upload of the weights, then per data set one activation, ONE pgl_latent_fold and ONE pgl_latent_draw on the device's Philox
+        stream (seed, sweep, elem0 + t), which writes the new x_t into S.  Off is NOT touched: it still holds the offset the sweep ran
+        under, which covariate_step needs (call it with psi_ready=True: Psi and the weights are in place); that step rebuilds Off from
+        the new latents and the new beta.  The scratch -- Lambda and r, (Q (Q + 1) / 2 + Q) * 8 bytes per bin of the longest data set --
+        is allocated at the first call, behind the memory gate.  keep=True: self.last_latent_stats = [(Lambda (T, P), r (T, Q)), ...]
+        per data set on the host (tests).  A pivot that is not positive raises np.linalg.LinAlgError (non-finite input: I + Lambda_t
+        is positive definite otherwise)."""
+        self._need_latents("latent_step()")
+        if self.likelihood_only or self.design_only:
+            raise ValueError("latent_step(): an engine with sweep buffers is required")
+        Q, nl = self.Q, self.nloc
+        P = Q * (Q + 1) // 2
+        T = max([ds.T for ds in self.datasets] or [0])
+        if self._lat is None or self._lat["T"] < T:
+            self._lat = None
+            self.reserve("latents: the step's scratch needs", 8 * T * (P + Q) + 4)
+            self._lat = dict(T=T, Lam=self._z(max(T, 1), P), r=self._z(max(T, 1), Q), status=self._z(1, dtype=I32))
+        c = self._lat
+        c["status"].zero_()
+        self._upload_weights(a, W, b)
+        st = self._st()
+        kept = []
+        for ds in self.datasets:                     # (not fold_data: the fold takes the activation without the offset)
+            self._activation(ds, st)
+            h = self._tic("latent_fold", float(ds.T) * nl)
+            call("pgl_latent_fold", Psi=ptr(ds.Psi), ldn=self.ldn, bias=ptr(self.bias), Omega=ptr(ds.OK), ldo=2 * self.ldn,
+                 Kappa=ctypes.c_void_p(ds.OK.data_ptr() + 8 * self.ldn), ldk=2 * self.ldn, S=ptr(ds.S), lds=self.K, col0=self.K_obs,
+                 Beta=ptr(self.beta_dev), ldb=self.ldn, T=ds.T, nloc=nl, Q=Q, Lambda=ptr(c["Lam"]), r=ptr(c["r"]), hip_stream=st)
+            self._toc(h)
+            if keep:
+                kept.append((c["Lam"][:ds.T].cpu().numpy(), c["r"][:ds.T].cpu().numpy()))
+            h = self._tic("latent_draw", float(ds.T))
+            call("pgl_latent_draw", Lambda=ptr(c["Lam"]), r=ptr(c["r"]), z_override=None, seed=int(seed) & (2 ** 64 - 1),
+                 sweep=int(sweep) & (2 ** 64 - 1), elem0=ds.elem0, S=ptr(ds.S), lds=self.K, col0=self.K_obs, status=ptr(c["status"]), T=ds.T, Q=Q,
+                 hip_stream=st)
+            self._toc(h)
+        if keep:
+            self.last_latent_stats = kept
+        if int(c["status"].item()):
+            raise np.linalg.LinAlgError("latent step: I + Lambda_t is not positive definite for some time bin (are the loadings, omega and "
+                                        "the activation finite?)")
 
     # ------------------------------------------------------------------ one Gibbs sweep of the shard's regressions
     def _sweep_args(self, ovs=None):

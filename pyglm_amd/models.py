@@ -70,19 +70,29 @@ class NonlinearAutoregressiveModel(object):
     DRAW_AHEAD_MIN_SIZE = 0            # N*N*B from which the next sweep's host draws are made while the GPU is busy (every size: a small model's sweep leaves the host idle for most of a millisecond)
 
     def __init__(self, N, regressions, basis=None, B=10, device=None, engine_factory=None, seed=None, engine_kwargs=None, shard=None,
-                 n_covariates=0, covariate_prior=None):
+                 n_covariates=0, covariate_prior=None, n_latents=0, latent_loading_prior=None):
         """n_covariates = K > 0: every data set carries external covariates S (T, K) shared by all neurons (add_data(..., covariates=S)),
         neuron n the weights beta_n (model.covariate_weights, (N, K)) with the prior beta_n ~ N(mu0, Sigma0), covariate_prior = (mu0,
         Sigma0), default (0, I); psi = X . vec(a * W) + b + S beta_n, and resample_model() draws beta right behind the regressions'
-        sweep (pyglm_amd/covariates.py states the law)."""
+        sweep (pyglm_amd/covariates.py states the law).
+        n_latents = Q > 0 (1 .. 8, n_covariates + Q <= 32): Q latent factors shared by the population, x_t ~ N(0, I) per time bin, inferred
+        with the network -- the common input nobody recorded (pyglm_amd/latents.py states the law).  Neuron n's loadings C_n
+        (model.latent_loadings, (N, Q)) have the prior latent_loading_prior = (mu, Sigma), default (0, I), and are drawn by the covariate
+        step; resample_model() draws x | omega, W, b, beta between the sweep and that step.  model.latents, model.common_input()."""
         from . import covariates as _cov
+        from . import latents as _lat
         self.N = N
-        self.K = _cov.check_count(n_covariates)
-        if self.K:
-            _cov.prior_terms(self.K, covariate_prior)     # (a mis-shaped prior is refused here, not at the first data set)
+        self.K_obs = _cov.check_count(n_covariates)      # observed covariates; K: all columns of S, the latent ones behind the observed
+        self.Q = _lat.check_count(n_latents, self.K_obs)
+        self.K = self.K_obs + self.Q
+        if self.K_obs:
+            _cov.prior_terms(self.K_obs, covariate_prior)     # (a mis-shaped prior is refused here, not at the first data set)
         elif covariate_prior is not None:
             raise ValueError("covariate_prior was given, but n_covariates=0")
-        self._covariate_prior = covariate_prior
+        if not self.Q and latent_loading_prior is not None:
+            raise ValueError("latent_loading_prior was given, but n_latents=0")
+        # the engine's prior of all K weights: the user's own without latents, the two priors joined block-diagonally with them
+        self._covariate_prior = _lat.joint_prior(self.K_obs, self.Q, covariate_prior, latent_loading_prior) if self.Q else covariate_prior
         self._beta = np.zeros((N, self.K))
         self.covariates_list = []                        # S of every data set, parallel to data_list (None without covariates)
         assert len(regressions) == N
@@ -102,6 +112,10 @@ class NonlinearAutoregressiveModel(object):
         # shard=(n0, n1): this process sweeps neurons [n0, n1) only, whatever the process group says, and exchanges nothing -- the other
         # rows of (A, W, b) keep their values.  What ONE rank of a job too large for the GPUs at hand does (bench.py --neurons).
         self._shard_override = shard is not None
+        if self.Q and (self.world > 1 or shard is not None):
+            raise ValueError("n_latents=%d with %s: a time bin's sums run over ALL neurons, so sharded ranks would need an ordered all-reduce of "
+                             "T x %d numbers per sweep; latents across ranks are not supported"
+                             % (self.Q, "shard=%r" % (shard,) if shard is not None else "%d ranks" % self.world, self.Q * (self.Q + 3) // 2))
         if shard is not None:
             self.n0, self.n1 = int(shard[0]), int(shard[1])
             assert 0 <= self.n0 < self.n1 <= N
@@ -141,10 +155,16 @@ class NonlinearAutoregressiveModel(object):
             obs, xi = self._engine_mode
             kw = dict(obs=obs, xi=xi)
             if self.K:
-                kw.update(n_covariates=self.K, covariate_prior=self._covariate_prior)
+                kw.update(n_covariates=self.K_obs, covariate_prior=self._covariate_prior)
+            if self.Q:
+                kw.update(n_latents=self.Q)
             kw.update(self._engine_kwargs)
             if self._engine_factory is not None:
-                self._engine = self._engine_factory(self.N, self.B, self.n0, self.n1, **kw)
+                eng = self._engine_factory(self.N, self.B, self.n0, self.n1, **kw)
+                if self.Q and not hasattr(eng, "latent_step"):
+                    raise ValueError("a model with latents needs an engine that samples them: %s has no latent_step(a, W, b, seed, sweep)"
+                                     % type(eng).__name__)
+                self._engine = eng
             else:
                 from .engine import GibbsEngine
                 import torch
@@ -183,12 +203,49 @@ class NonlinearAutoregressiveModel(object):
     # ---- external covariates (pyglm_amd/covariates.py)
     @property
     def covariate_weights(self):
-        """(N, K) the covariate weights beta, row = neuron; a copy.  Assignable: model.covariate_weights = beta"""
-        return self._beta.copy()
+        """(N, K) the weights beta of the observed covariates, row = neuron; a copy.  Assignable: model.covariate_weights = beta"""
+        return self._beta[:, :self.K_obs].copy()
 
     @covariate_weights.setter
     def covariate_weights(self, beta):
-        self._beta = np.array(np.broadcast_to(np.asarray(beta, dtype=np.float64), (self.N, self.K)))
+        new = self._beta.copy()                      # (_beta: all K columns, the latents' loadings behind the observed covariates' weights)
+        new[:, :self.K_obs] = np.broadcast_to(np.asarray(beta, dtype=np.float64), (self.N, self.K_obs))
+        self._beta = new
+
+    # ---- latent common input (pyglm_amd/latents.py)
+    def _need_latents(self, what):
+        if not self.Q:
+            raise ValueError("%s: this model was built with n_latents=0" % what)
+
+    @property
+    def latents(self):
+        """[X_i (T_i, Q)]: the latent factors of every data set at the current state; copies.  X and the loadings are defined only up to
+        rotation and sign: common_input() is the identifiable quantity"""
+        self._need_latents("latents")
+        return [self.engine.latents(i) for i in range(len(self.data_list))]
+
+    def set_latents(self, i, X):
+        """X (T_i, Q) becomes the latent factors of data set i"""
+        self._need_latents("set_latents()")
+        self._sync_covariates()
+        self.engine.set_latents(range(len(self.data_list))[i], X)
+
+    @property
+    def latent_loadings(self):
+        """(N, Q) the loadings C, row = neuron; a copy"""
+        self._need_latents("latent_loadings")
+        return self._beta[:, self.K_obs:].copy()
+
+    def common_input(self, data=0):
+        """(T, N) = X C': the drive the latent factors give every neuron of data set `data` at the current state -- what they add to psi"""
+        from . import latents as _lat
+        self._need_latents("common_input()")
+        return _lat.common_input_host(self.engine.latents(range(len(self.data_list))[data]), self._beta[:, self.K_obs:])
+
+    def _refuse_heldout_latents(self, what, datas):
+        if self.Q and datas is not None:
+            raise ValueError("%s: held-out datas= in a model with latents (n_latents=%d) is not supported -- the latent factors of a recording "
+                             "the chain never saw are unknown" % (what, self.Q))
 
     def _sync_covariates(self, eng=None):
         """this shard's beta onto engine eng (default: the model's own) where it holds another: after set_state(), an assignment to
@@ -204,8 +261,9 @@ class NonlinearAutoregressiveModel(object):
 
     def _refuse_covariates(self, what):
         if self.K:
-            raise ValueError("%s: free-running simulation of a model with covariates (n_covariates=%d) is not supported -- it needs covariates "
-                             "for bins that were never recorded; conditional_simulate() / conditional_check() work" % (what, self.K))
+            raise ValueError("%s: free-running simulation of a model with covariates (n_covariates=%d%s) is not supported -- it needs covariates "
+                             "for bins that were never recorded; conditional_simulate() / conditional_check() work"
+                             % (what, self.K_obs, ", n_latents=%d" % self.Q if self.Q else ""))
 
     def add_data(self, data, X=None, covariates=None):
         """(models.py:66-80)  covariates: S (T, K) of this data set, required with n_covariates = K > 0 and refused without"""
@@ -215,10 +273,10 @@ class NonlinearAutoregressiveModel(object):
         T = data.shape[0]
         if X is not None:
             assert X.shape == (T, N, B)
-        S = _cov.check_covariates(covariates, T, self.K, "add_data")
+        S = _cov.check_covariates(covariates, T, self.K_obs, "add_data")
         _regression.check_counts(self.regressions, data)
         self._sync_covariates()
-        ckw = dict(covariates=S) if self.K else {}
+        ckw = dict(covariates=S) if self.K_obs else {}
         ds = self.engine.add_data(data, X=X, basis=self.basis, **ckw, **self._obs_terms_kw(data))
         self.covariates_list.append(S)
         dist = _dist()
@@ -429,6 +487,7 @@ class NonlinearAutoregressiveModel(object):
     def log_likelihood(self, datas=None, covariates=None):
         """(models.py:82-96) sum over datasets and neurons; `datas` other than the stored data is evaluated through a
         temporary engine.  covariates: with datas, in a model with covariates: [S, ...] parallel to datas."""
+        self._refuse_heldout_latents("log_likelihood()", datas)
         if datas is None:
             if covariates is not None:
                 raise ValueError("log_likelihood(): covariates= goes with datas=; the stored data carry their own")
@@ -473,6 +532,7 @@ class NonlinearAutoregressiveModel(object):
         changes nothing in the chain.  datas, covariates: as for log_likelihood -- None: the stored data; a list: held-out data (and
         their covariates).  In a model with covariates the summary also keeps covariate_mean / covariate_var, (N, K)."""
         from .summary import PosteriorSummary
+        self._refuse_heldout_latents("summarize()", datas)
         return PosteriorSummary(self, rates=rates, pointwise=pointwise, datas=datas, covariates=covariates)
 
     def diagnose(self, levels=8, weights=True, rb=True):
@@ -491,6 +551,7 @@ class NonlinearAutoregressiveModel(object):
         from .utils.utils import fingerprint
         from .engine import GibbsEngine
         from . import covariates as _cov
+        self._refuse_heldout_latents("held-out data", datas)
         items = []
         if covariates is not None and len(covariates) != len(datas):
             raise ValueError("covariates: %d entries for %d held-out data sets" % (len(covariates), len(datas)))
@@ -498,7 +559,7 @@ class NonlinearAutoregressiveModel(object):
             X, Y = d if isinstance(d, tuple) else (None, d)
             if isinstance(X, _LazyX):
                 X = None
-            S = _cov.check_covariates(None if covariates is None else covariates[j], np.asarray(Y).shape[0], self.K, "held-out data set %d" % j)
+            S = _cov.check_covariates(None if covariates is None else covariates[j], np.asarray(Y).shape[0], self.K_obs, "held-out data set %d" % j)
             items.append((X, np.asarray(Y), S))
         key = tuple((None if X is None else fingerprint(X), fingerprint(Y), None if S is None else fingerprint(S)) for X, Y, S in items)
         cache = getattr(self, "_heldout_cache", None)
@@ -779,6 +840,7 @@ class NonlinearAutoregressiveModel(object):
         summarize -- None: the stored data; a list: held-out recordings (covariates: theirs, in a model with covariates).  A Gaussian
         neuron is refused by name.  Changes nothing in the chain."""
         from .rescale import TimeRescaling
+        self._refuse_heldout_latents("time_rescaling()", datas)
         return TimeRescaling(self, bins=bins, seed=seed, coef=coef, datas=datas, covariates=covariates)
 
     def rescaled_intervals(self, data=0, bins=64, seed=0, gpu=None):
@@ -886,7 +948,11 @@ class NonlinearAutoregressiveModel(object):
         if self.K:
             # the covariate weights, directly behind the sweep and before every other step (eta, xi, the network): from the omega the sweep
             # has just drawn and the weights it returned; the engine's offsets follow, so what comes next sees the new beta
-            cov_beta = self.engine.covariate_step(a, W, b, self.seed, self.sweeps_done)
+            # -- with latents x | omega, W, b, beta first: Off must still hold the offset the sweep ran under when beta's fold recovers kappa,
+            # and beta is then drawn given the new x; the latent step leaves Psi and the weights in place for it
+            if self.Q:
+                self.engine.latent_step(a, W, b, self.seed, self.sweeps_done)
+            cov_beta = self.engine.covariate_step(a, W, b, self.seed, self.sweeps_done, **(dict(psi_ready=True) if self.Q else {}))
         if gaussian:
             # noise variances (regression.py:433-445): residual sums of squares under the NEW weights from the device, gamma draws
             # keyed by the global neuron index
@@ -963,6 +1029,8 @@ class NonlinearAutoregressiveModel(object):
             for r in self.regressions:
                 r._engine_cache, r._lik_engine_cache = keep[id(r)]
         st["seed"] = self.seed
+        if self.Q:
+            st["latents"] = self.latents             # (the one piece of chain state that lives on the device: read back here)
         return st
 
     def set_state(self, state):
@@ -980,6 +1048,10 @@ class NonlinearAutoregressiveModel(object):
         self._adopt_state()
         self._draws_ahead = None
         self._fresh_stats = self._stats_kept = None
+        if self.Q and "latents" in state:
+            self._sync_covariates()
+            for i, X in enumerate(state["latents"]):
+                self.engine.set_latents(i, X)
 
     def plot(self, *args, **kwargs):
         raise NotImplementedError("plotting is outside the scope of the MI355X hot path (SURVEY.md section 2, row 8)")

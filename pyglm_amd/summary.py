@@ -245,6 +245,8 @@ class PosteriorSummary(object):
         self._eng, Ys = model_data(model, datas, "summarize()", covariates)
         Kc = getattr(model, "K", 0)
         self._beta = (np.zeros((model.n1 - model.n0, Kc)), np.zeros((model.n1 - model.n0, Kc)))      # N K numbers per sample: host Welford
+        Qc = getattr(model, "Q", 0)                       # latents: ||C_n||^2, the variance of neuron n's common drive (x_t ~ N(0, I)) -- N numbers
+        self._common = (np.zeros(model.n1 - model.n0), np.zeros(model.n1 - model.n0)) if Qc else None      # per sample, rotation-invariant
         self._nsets = len(Ys)
         if device_engine(self._eng):
             self._acc = _DeviceAccumulators(self._eng, self.rates, self.pointwise, link, link_par)
@@ -260,6 +262,8 @@ class PosteriorSummary(object):
         self.log_likelihoods = []
         self._xi = (np.zeros_like(self._xi[0]), np.zeros_like(self._xi[1]))
         self._beta = (np.zeros_like(self._beta[0]), np.zeros_like(self._beta[1]))
+        if self._common is not None:
+            self._common = (np.zeros_like(self._common[0]), np.zeros_like(self._common[1]))
 
     def collect(self):
         """fold the model's current state into the accumulators -> the log-likelihood of the summarised data at that state, equal to
@@ -279,6 +283,8 @@ class PosteriorSummary(object):
         self.count += 1
         if getattr(m, "K", 0):
             _welford(self._beta[0], self._beta[1], m._beta[m.n0:m.n1], float(self.count))
+        if self._common is not None:
+            _welford(self._common[0], self._common[1], np.sum(m._beta[m.n0:m.n1, m.K_obs:] ** 2, axis=1), float(self.count))
         # the dispersions are a handful of host numbers per sample: their moments stay on the host (NaN for a neuron without xi)
         xi = np.array([getattr(r, "xi", np.nan) for r in m.regressions[m.n0:m.n1]], dtype=np.float64)
         with np.errstate(invalid="ignore"):
@@ -315,7 +321,18 @@ class PosteriorSummary(object):
 
     def _beta_moment(self, i, scale):
         self._need()
-        return self.model._gather_rows(np.ascontiguousarray(self._beta[i] * scale))
+        Ko = getattr(self.model, "K_obs", self._beta[i].shape[1])       # (the latents' loadings ride behind: not identifiable one by one)
+        return self.model._gather_rows(np.ascontiguousarray(self._beta[i][:, :Ko] * scale))
+
+    def _common_moment(self, i, scale):
+        self._need()
+        if self._common is None:
+            raise RuntimeError("this model has no latents: n_latents=0")
+        return self._common[i] * scale
+
+    common_input_var_mean = property(lambda self: self._common_moment(0, 1.0),
+                                     doc="(N,) mean over the samples of ||C_n||^2, the variance of neuron n's common drive; models with latents")
+    common_input_var_var = property(lambda self: self._common_moment(1, 1.0 / self.count), doc="(N,) its population variance")
 
     covariate_mean = property(lambda self: self._beta_moment(0, 1.0), doc="(N, K) mean of the covariate weights beta over the samples")
     covariate_var = property(lambda self: self._beta_moment(1, 1.0 / self.count), doc="(N, K) their population variance")
