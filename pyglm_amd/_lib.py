@@ -20,6 +20,8 @@ HEADER_SBM = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip_sbm.h")
 HEADER_COVARIATES = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip_covariates.h")
 # the entries of the latent common input (the fold over neurons per time bin, the draw of x_t): a sixth header, tables of its own likewise
 HEADER_LATENTS = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip_latents.h")
+# the entry of the latents' temporal prior (the block-tridiagonal draw): a seventh header, tables of its own likewise
+HEADER_LATENT_DYNAMICS = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip_latent_dynamics.h")
 
 
 class PglError(RuntimeError):
@@ -122,12 +124,15 @@ with open(HEADER_LATENTS) as _fh:
     LATENTS_CONSTANTS, _, LATENTS_FUNCTIONS = parse_header(_fh.read(), header=os.path.basename(HEADER_LATENTS))
 globals().update(LATENTS_CONSTANTS)                               # PGL_LATENT_MAX, PGL_LATENT_LDS_COLS, PGL_PURPOSE_LATENT
 LATENTS_PARAMS = {f: [p for p, _ in params] for f, (_, params) in LATENTS_FUNCTIONS.items()}
+with open(HEADER_LATENT_DYNAMICS) as _fh:
+    LATENT_DYNAMICS_CONSTANTS, _, LATENT_DYNAMICS_FUNCTIONS = parse_header(_fh.read(), header=os.path.basename(HEADER_LATENT_DYNAMICS))
+LATENT_DYNAMICS_PARAMS = {f: [p for p, _ in params] for f, (_, params) in LATENT_DYNAMICS_FUNCTIONS.items()}
 _lib = None
 
 
 def _params(name):
     """the parameter names of entry `name`, of whichever header declares it"""
-    for table in (PARAMS, DISPERSION_PARAMS, DIAGNOSTICS_PARAMS, COVARIATES_PARAMS, LATENTS_PARAMS):
+    for table in (PARAMS, DISPERSION_PARAMS, DIAGNOSTICS_PARAMS, COVARIATES_PARAMS, LATENTS_PARAMS, LATENT_DYNAMICS_PARAMS):
         if name in table:
             return table[name]
     return SBM_PARAMS[name]
@@ -145,7 +150,8 @@ def load():
     #                      dependency on libamdhip64 has to resolve to the copy torch has loaded (loading the library first leaves
     #                      two runtimes in the process: "no ROCm-capable device is detected" at the first launch)
     lib = ctypes.CDLL(LIB_PATH)
-    for functions in (FUNCTIONS, DISPERSION_FUNCTIONS, DIAGNOSTICS_FUNCTIONS, SBM_FUNCTIONS, COVARIATES_FUNCTIONS, LATENTS_FUNCTIONS):
+    for functions in (FUNCTIONS, DISPERSION_FUNCTIONS, DIAGNOSTICS_FUNCTIONS, SBM_FUNCTIONS, COVARIATES_FUNCTIONS, LATENTS_FUNCTIONS,
+                      LATENT_DYNAMICS_FUNCTIONS):
         for name, (restype, params) in functions.items():
             fn = getattr(lib, name)     # AttributeError if the export is missing
             fn.argtypes = [t for _, t in params]
@@ -158,13 +164,13 @@ def load():
 
 def source_hash():
     """sha256 (first 16 hex digits) over the kernel sources of the library -- pyglm_amd/csrc/*.hip, *.h and the Makefile, in name order, plus
-    the six headers under include/: committed hardware-counter summaries (profiles/*.json) record the hash they were taken at, and bench.py quotes them
+    the seven headers under include/: committed hardware-counter summaries (profiles/*.json) record the hash they were taken at, and bench.py quotes them
     only while it still matches"""
     import hashlib
     h = hashlib.sha256()
     src = os.path.join(_HERE, "csrc")
     files = [os.path.join(src, f) for f in sorted(os.listdir(src)) if f.endswith((".hip", ".h")) or f == "Makefile"]
-    files += [HEADER, HEADER_DISPERSION, HEADER_DIAGNOSTICS, HEADER_SBM, HEADER_COVARIATES, HEADER_LATENTS]
+    files += [HEADER, HEADER_DISPERSION, HEADER_DIAGNOSTICS, HEADER_SBM, HEADER_COVARIATES, HEADER_LATENTS, HEADER_LATENT_DYNAMICS]
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")
         with open(f, "rb") as fh:

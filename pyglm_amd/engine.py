@@ -117,7 +117,7 @@ class GibbsEngine(object):
 
     def __init__(self, N, B, n0=0, n1=None, device=None, obs="bernoulli", xi=1.0, batch=None, mem_budget_bytes=None,
                  design_only=False, visit_order=True, gram=None, likelihood_only=False, planes=None, i8_group=None, i8_slice=None,
-                 i8_resident=None, device_share=1, n_covariates=0, covariate_prior=None, n_latents=0):
+                 i8_resident=None, device_share=1, n_covariates=0, covariate_prior=None, n_latents=0, latent_ar=None):
         """device: torch device of this shard (default: the process's current GPU).  design_only: only the design matrix is kept (basis
         convolution).  likelihood_only: activation / log-likelihood / means only -- no sweep buffers, no residue planes (a held-out data
         set costs X', Y and Psi, nothing else).  i8_group / i8_slice / i8_resident: override the integer Gram's plan (_i8_plan) -- neurons
@@ -127,12 +127,15 @@ class GibbsEngine(object):
         of the model (N) or of this shard (n1 - n0).  n_covariates = K > 0: every data set carries covariates S (T, K) and an offset
         Off = S beta' on the device (pyglm_amd/covariates.py); covariate_prior = (mu0, Sigma0) of beta_n, default (0, I).  n_latents = Q > 0
         (pyglm_amd/latents.py): Q further columns of S whose values are sampled (latent_step) -- K becomes n_covariates + Q, S is
-        [S_obs | X] with X zero at add_data, and covariate_prior is the prior of all K weights (latents.joint_prior)."""
+        [S_obs | X] with X zero at add_data, and covariate_prior is the prior of all K weights (latents.joint_prior).  latent_ar = phi (a
+        scalar or Q values in [0, 1)): the latents' AR(1) prior -- where some phi_q > 0 latent_step draws a data set's X jointly
+        (pgl_latent_ar_draw); None or all zeros: the independent bins of pgl_latent_draw, launch for launch."""
         from . import covariates as _cov
         from . import latents as _lat
         self.K_obs = _cov.check_count(n_covariates)
         self.Q = _lat.check_count(n_latents, self.K_obs)
         self.K = self.K_obs + self.Q
+        self.latent_ar = _lat.check_ar(latent_ar, self.Q)
         self.cov_prior = _cov.prior_terms(self.K, covariate_prior) if self.K else None
         if not torch.cuda.is_available():
             raise _lib.PglError("pyglm_amd needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU fallback")
@@ -890,7 +893,9 @@ class GibbsEngine(object):
         latent_step_host states it): from the [Omega | Kappa] that sweep left in every data set's OK -- Kappa the reduced one --, the
         latent columns it ran under (still in S), the loadings in beta_dev and psi_net at the state (a, W, b) the sweep returned.  One
         upload of the weights, then per data set one activation, ONE pgl_latent_fold and ONE pgl_latent_draw on the device's Philox
-        stream (seed, sweep, elem0 + t), which writes the new x_t into S.  Off is NOT touched: it still holds the offset the sweep ran
+        stream (seed, sweep, elem0 + t), which writes the new x_t into S.  With a temporal prior (latent_ar, some phi_q > 0) the draw is
+        pgl_latent_ar_draw instead -- the data set's X jointly, on the same normals, stage "latent_ar_draw" -- and its scratch
+        (pgl_latent_ar_scratch of the longest data set) is allocated with Lambda and r.  Off is NOT touched: it still holds the offset the sweep ran
         under, which covariate_step needs (call it with psi_ready=True: Psi and the weights are in place); that step rebuilds Off from
         the new latents and the new beta.  The scratch -- Lambda and r, (Q (Q + 1) / 2 + Q) * 8 bytes per bin of the longest data set --
         is allocated at the first call, behind the memory gate.  keep=True: self.last_latent_stats = [(Lambda (T, P), r (T, Q)), ...]
@@ -902,10 +907,15 @@ class GibbsEngine(object):
         Q, nl = self.Q, self.nloc
         P = Q * (Q + 1) // 2
         T = max([ds.T for ds in self.datasets] or [0])
+        ar = bool(np.any(self.latent_ar > 0.0))
         if self._lat is None or self._lat["T"] < T:
             self._lat = None
-            self.reserve("latents: the step's scratch needs", 8 * T * (P + Q) + 4)
+            ar_bytes = int(_lib.load().pgl_latent_ar_scratch(T, Q, 0)) if ar else 0
+            self.reserve("latents: the step's scratch needs", 8 * T * (P + Q) + 4 + ar_bytes)
             self._lat = dict(T=T, Lam=self._z(max(T, 1), P), r=self._z(max(T, 1), Q), status=self._z(1, dtype=I32))
+            if ar:
+                self._lat.update(ar=torch.empty(max(ar_bytes // 8, 1), dtype=F64, device=self.dev), ar_bytes=ar_bytes,
+                                 phi=(ctypes.c_double * Q)(*self.latent_ar))
         c = self._lat
         c["status"].zero_()
         self._upload_weights(a, W, b)
@@ -920,16 +930,22 @@ class GibbsEngine(object):
             self._toc(h)
             if keep:
                 kept.append((c["Lam"][:ds.T].cpu().numpy(), c["r"][:ds.T].cpu().numpy()))
-            h = self._tic("latent_draw", float(ds.T))
-            call("pgl_latent_draw", Lambda=ptr(c["Lam"]), r=ptr(c["r"]), z_override=None, seed=int(seed) & (2 ** 64 - 1),
-                 sweep=int(sweep) & (2 ** 64 - 1), elem0=ds.elem0, S=ptr(ds.S), lds=self.K, col0=self.K_obs, status=ptr(c["status"]), T=ds.T, Q=Q,
-                 hip_stream=st)
+            if ar:
+                h = self._tic("latent_ar_draw", float(ds.T))
+                call("pgl_latent_ar_draw", Lambda=ptr(c["Lam"]), r=ptr(c["r"]), phi=ctypes.cast(c["phi"], ctypes.c_void_p), z_override=None,
+                     seed=int(seed) & (2 ** 64 - 1), sweep=int(sweep) & (2 ** 64 - 1), elem0=ds.elem0, S=ptr(ds.S), lds=self.K, col0=self.K_obs,
+                     status=ptr(c["status"]), T=ds.T, Q=Q, seg=0, scratch=ptr(c["ar"]), scratch_bytes=c["ar_bytes"], hip_stream=st)
+            else:
+                h = self._tic("latent_draw", float(ds.T))
+                call("pgl_latent_draw", Lambda=ptr(c["Lam"]), r=ptr(c["r"]), z_override=None, seed=int(seed) & (2 ** 64 - 1),
+                     sweep=int(sweep) & (2 ** 64 - 1), elem0=ds.elem0, S=ptr(ds.S), lds=self.K, col0=self.K_obs, status=ptr(c["status"]), T=ds.T, Q=Q,
+                     hip_stream=st)
             self._toc(h)
         if keep:
             self.last_latent_stats = kept
         if int(c["status"].item()):
-            raise np.linalg.LinAlgError("latent step: I + Lambda_t is not positive definite for some time bin (are the loadings, omega and "
-                                        "the activation finite?)")
+            raise np.linalg.LinAlgError("latent step: %s is not positive definite for some time bin (are the loadings, omega and "
+                                        "the activation finite?)" % ("the latents' precision" if ar else "I + Lambda_t"))
 
     # ------------------------------------------------------------------ one Gibbs sweep of the shard's regressions
     def _sweep_args(self, ovs=None):

@@ -23,6 +23,10 @@ latent ones, K = K_obs + Q <= COVARIATE_MAX, and every data set's S (T, K) on th
     normals          z_t[q] from the device's Philox stream: purpose PURPOSE_LATENT, key = seed, stream = sweep, element = elem0 + t; call q
                      yields (u0, u1) and z = sqrt(-2 log u0) cos(2 pi u1) (latent_normals_host).
 
+    temporal prior   latent_ar = phi replaces x_t ~ N(0, I_Q), independent over t, by a stationary AR(1) process per factor; the statistics
+                     stay, the draw becomes one joint Gaussian over a data set's bins (below: check_ar ... latent_ar_step_host;
+                     pgl_latent_dynamics.hip).  phi = 0 is the law above, launch for launch.
+
 X and C alone are defined only up to rotation and sign; the identifiable quantity is the common input X C' (T, N)."""
 import numpy as np
 
@@ -108,6 +112,155 @@ def latent_step_host(C, x_old, Omega, Kappa, psi_net, z):
     """the whole step of one data set on the host -> x_new (T, Q)"""
     Lam, r = latent_stats_host(C, x_old, Omega, Kappa, psi_net)
     return latent_draw_host(Lam, r, z)
+
+
+# ---- the temporal prior (include/pyglm_hip_latent_dynamics.h, pgl_latent_dynamics.hip; DESIGN.md section 21) ------------------------------
+# latent_ar = phi: per factor q and per data set x_0 ~ N(0, 1), x_t = phi_q x_{t-1} + sqrt(1 - phi_q^2) eps_t -- stationary with marginal
+# variance 1, so the loadings' prior and the common-input variances keep their meaning.  With s_q = 1 - phi_q^2 a factor's prior precision
+# is tridiagonal: (1 + phi_q^2) / s_q on the diagonal, 1 / s_q at t = 0 and t = T - 1 (T = 1: exactly 1), -phi_q / s_q beside it.  Lambda_t
+# and r_t are the statistics above, unchanged (their derivation does not use the prior), and a data set's X | rest is N(J^-1 h, J^-1) with
+# J[t][t] = Lambda_t + diag(prior diagonal at t), J[t + 1][t] = -diag(phi_q / s_q), h_t = r_t.  phi = 0 is the law above.
+
+def check_ar(phi, Q):
+    """latent_ar -> (Q,) float64 with 0 <= phi_q < 1 (None: zeros; a scalar: every factor's), or a ValueError that says what is required"""
+    if phi is None:
+        return np.zeros(int(Q))
+    if not int(Q):
+        raise ValueError("latent_ar was given, but n_latents=0")
+    try:
+        p = np.asarray(phi, dtype=np.float64)
+    except (TypeError, ValueError):
+        p = None
+    if p is None or p.ndim > 1 or (p.ndim == 1 and p.shape[0] != Q) or not np.all((p >= 0.0) & (p < 1.0)):
+        raise ValueError("latent_ar = %r: a scalar or a sequence of n_latents = %d numbers with 0 <= phi < 1 is required" % (phi, Q))
+    return np.ascontiguousarray(np.broadcast_to(p, (int(Q),)), dtype=np.float64)
+
+
+def ar_prior_blocks(T, phi):
+    """the prior precision of one data set's latents -> (its diagonal (T, Q), e (Q,)): the precision of factor q is tridiagonal with
+    diagonal[:, q] and e[q] beside it"""
+    phi = np.atleast_1d(np.asarray(phi, dtype=np.float64))
+    s = 1.0 - phi * phi
+    d = np.tile((1.0 + phi * phi) / s, (int(T), 1))
+    if T == 1:
+        d[0] = 1.0
+    elif T > 1:
+        d[0] = d[-1] = 1.0 / s
+    return d, -phi / s
+
+
+def ar_precision_dense(Lam, phi):
+    """J (T Q, T Q) of one data set, bin-major (row t Q + q), from Lam (T, Q, Q): tests"""
+    Lam = np.asarray(Lam)
+    T, Q = Lam.shape[0], Lam.shape[1]
+    d, e = ar_prior_blocks(T, check_ar(phi, Q))
+    J = np.zeros((T * Q, T * Q), dtype=Lam.dtype)
+    for t in range(T):
+        J[t * Q:(t + 1) * Q, t * Q:(t + 1) * Q] = Lam[t] + np.diag(d[t])
+        if t + 1 < T:
+            J[(t + 1) * Q:(t + 2) * Q, t * Q:(t + 1) * Q] = np.diag(e)
+            J[t * Q:(t + 1) * Q, (t + 1) * Q:(t + 2) * Q] = np.diag(e)
+    return J
+
+
+def _chain_serial(D, E, h, z):
+    """x of a block-tridiagonal chain (D (n, Q, Q), E (n - 1, Q, Q) = J[i + 1][i], h, z (n, Q)): block Cholesky forward, backward"""
+    n, Q = h.shape
+    Ls, Ws, ys = [], [], []
+    Dt, g = D[0], h[0]
+    for i in range(n):
+        L = np.linalg.cholesky(Dt)
+        y = np.linalg.solve(L, g)
+        Ls.append(L), ys.append(y)
+        if i + 1 < n:
+            W = np.linalg.solve(L, E[i].T).T
+            Ws.append(W)
+            Dt, g = D[i + 1] - W.dot(W.T), h[i + 1] - W.dot(y)
+    x = np.empty((n, Q))
+    nxt = np.zeros(Q)
+    for i in range(n - 1, -1, -1):
+        t = ys[i] + z[i] - (Ws[i].T.dot(nxt) if i + 1 < n else 0.0)
+        nxt = x[i] = np.linalg.solve(Ls[i].T, t)
+    return x
+
+
+def _chain_draw(D, E, h, z, seg):
+    """the same chain by segments and separators (the elimination order of pgl_latent_ar_draw, which decides the map z -> x; the law is
+    the same for every seg): bins seg - 1, 2 seg - 1, ... are separators, every interior is eliminated on its own (dense, which is the
+    block recursion: a Cholesky factor is unique), the separators' chain is drawn likewise until it has fewer than 2 seg blocks, and
+    every interior is drawn given its separators.  Only tests call it with a seg (they compare host and device on the same z), and it
+    has to track ar_plan and the kernels of pgl_latent_dynamics.hip in what decides the map: group g owns bins [g seg, g seg + seg - 2],
+    a chain of n < 2 seg blocks is the base, the next chain has floor(n / seg) blocks, and a separator takes its left segment's partial
+    before its right segment's."""
+    n, Q = h.shape
+    if seg is None or n < 2 * seg:
+        return _chain_serial(D, E, h, z)
+    ns = n // seg
+    sep = np.arange(ns) * seg + seg - 1
+    Dn, hn, En = D[sep].copy(), h[sep].copy(), np.zeros((ns - 1, Q, Q))
+    kept = []
+    for gi in range(ns + 1):
+        a, b = gi * seg, (gi * seg + seg - 2 if gi < ns else n - 1)
+        m = b - a + 1
+        if m <= 0:
+            kept.append(None)
+            continue
+        JI, hI = np.zeros((m * Q, m * Q)), h[a:b + 1].reshape(-1)
+        for i in range(m):
+            JI[i * Q:(i + 1) * Q, i * Q:(i + 1) * Q] = D[a + i]
+            if i + 1 < m:
+                JI[(i + 1) * Q:(i + 2) * Q, i * Q:(i + 1) * Q] = E[a + i]
+                JI[i * Q:(i + 1) * Q, (i + 1) * Q:(i + 2) * Q] = E[a + i].T
+        L = np.linalg.cholesky(JI)
+        BL, BR = np.zeros((m * Q, Q)), np.zeros((m * Q, Q))        # J[interior][left separator], J[interior][right separator]
+        if gi >= 1:
+            BL[:Q] = E[a - 1]
+        if gi < ns:
+            BR[-Q:] = E[b].T
+        UL, UR, y = np.linalg.solve(L, BL), np.linalg.solve(L, BR), np.linalg.solve(L, hI)
+        if gi < ns:                                                  # the left segment's partial first, then the right segment's
+            Dn[gi] -= UR.T.dot(UR)
+            hn[gi] -= UR.T.dot(y)
+        if gi >= 1:
+            Dn[gi - 1] -= UL.T.dot(UL)
+            hn[gi - 1] -= UL.T.dot(y)
+        if 1 <= gi < ns:
+            En[gi - 1] = -UR.T.dot(UL)
+        kept.append((a, b, L, UL, UR, y))
+    xs = _chain_draw(Dn, En, hn, z[sep], seg)
+    x = np.empty((n, Q))
+    x[sep] = xs
+    for gi, k in enumerate(kept):
+        if k is None:
+            continue
+        a, b, L, UL, UR, y = k
+        t = y + z[a:b + 1].reshape(-1)
+        if gi >= 1:
+            t = t - UL.dot(xs[gi - 1])
+        if gi < ns:
+            t = t - UR.dot(xs[gi])
+        x[a:b + 1] = np.linalg.solve(L.T, t).reshape(-1, Q)
+    return x
+
+
+def latent_ar_draw_host(Lam, r, z, phi, seg=None):
+    """x (T, Q) ~ N(J^-1 r, J^-1), J = ar_precision_dense(Lam, phi), as x = J^-1 r + M z with M M' = J^-1: a serial block-Cholesky forward
+    and backward pass over the T bins.  seg >= 2: the same law eliminated by segments and separators, which is the map z -> x of
+    pgl_latent_ar_draw(seg) (seg=None is the device's seg >= T).  np.linalg.LinAlgError where a pivot block is not positive definite."""
+    Lam, r, z = np.asarray(Lam, dtype=np.float64), np.asarray(r, dtype=np.float64), np.asarray(z, dtype=np.float64)
+    T, Q = r.shape
+    if T == 0:
+        return np.empty((0, Q))
+    d, e = ar_prior_blocks(T, check_ar(phi, Q))
+    D = Lam + d[:, :, None] * np.eye(Q)
+    E = np.tile(np.diag(e), (max(T - 1, 0), 1, 1))
+    return _chain_draw(D, E, r, z, seg)
+
+
+def latent_ar_step_host(C, x_old, Omega, Kappa, psi_net, z, phi, seg=None):
+    """the whole step of one data set under the temporal prior on the host -> x_new (T, Q)"""
+    Lam, r = latent_stats_host(C, x_old, Omega, Kappa, psi_net)
+    return latent_ar_draw_host(Lam, r, z, phi, seg=seg)
 
 
 def common_input_host(X, C):

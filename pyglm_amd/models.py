@@ -70,7 +70,7 @@ class NonlinearAutoregressiveModel(object):
     DRAW_AHEAD_MIN_SIZE = 0            # N*N*B from which the next sweep's host draws are made while the GPU is busy (every size: a small model's sweep leaves the host idle for most of a millisecond)
 
     def __init__(self, N, regressions, basis=None, B=10, device=None, engine_factory=None, seed=None, engine_kwargs=None, shard=None,
-                 n_covariates=0, covariate_prior=None, n_latents=0, latent_loading_prior=None):
+                 n_covariates=0, covariate_prior=None, n_latents=0, latent_loading_prior=None, latent_ar=None):
         """n_covariates = K > 0: every data set carries external covariates S (T, K) shared by all neurons (add_data(..., covariates=S)),
         neuron n the weights beta_n (model.covariate_weights, (N, K)) with the prior beta_n ~ N(mu0, Sigma0), covariate_prior = (mu0,
         Sigma0), default (0, I); psi = X . vec(a * W) + b + S beta_n, and resample_model() draws beta right behind the regressions'
@@ -78,13 +78,17 @@ class NonlinearAutoregressiveModel(object):
         n_latents = Q > 0 (1 .. 8, n_covariates + Q <= 32): Q latent factors shared by the population, x_t ~ N(0, I) per time bin, inferred
         with the network -- the common input nobody recorded (pyglm_amd/latents.py states the law).  Neuron n's loadings C_n
         (model.latent_loadings, (N, Q)) have the prior latent_loading_prior = (mu, Sigma), default (0, I), and are drawn by the covariate
-        step; resample_model() draws x | omega, W, b, beta between the sweep and that step.  model.latents, model.common_input()."""
+        step; resample_model() draws x | omega, W, b, beta between the sweep and that step.  model.latents, model.common_input().
+        latent_ar = phi (a scalar or Q values, 0 <= phi_q < 1; None: zeros): a temporal prior on the factors, per factor and data set
+        x_0 ~ N(0, 1), x_t = phi_q x_{t-1} + sqrt(1 - phi_q^2) eps_t -- stationary with variance 1, for common input that changes slowly.
+        A hyper-parameter (model.latent_ar), not chain state; all zeros is the model without it, bit for bit."""
         from . import covariates as _cov
         from . import latents as _lat
         self.N = N
         self.K_obs = _cov.check_count(n_covariates)      # observed covariates; K: all columns of S, the latent ones behind the observed
         self.Q = _lat.check_count(n_latents, self.K_obs)
         self.K = self.K_obs + self.Q
+        self.latent_ar = _lat.check_ar(latent_ar, self.Q)
         if self.K_obs:
             _cov.prior_terms(self.K_obs, covariate_prior)     # (a mis-shaped prior is refused here, not at the first data set)
         elif covariate_prior is not None:
@@ -158,9 +162,15 @@ class NonlinearAutoregressiveModel(object):
                 kw.update(n_covariates=self.K_obs, covariate_prior=self._covariate_prior)
             if self.Q:
                 kw.update(n_latents=self.Q)
+            ar = bool(np.any(self.latent_ar > 0.0))
+            if ar:                                   # (only then: a factory from before the temporal prior keeps working)
+                kw.update(latent_ar=self.latent_ar.copy())
             kw.update(self._engine_kwargs)
             if self._engine_factory is not None:
                 eng = self._engine_factory(self.N, self.B, self.n0, self.n1, **kw)
+                if ar and not np.array_equal(np.asarray(getattr(eng, "latent_ar", ()), dtype=np.float64), self.latent_ar):
+                    raise ValueError("a model with latent_ar needs an engine that takes it: %s does not accept the keyword latent_ar "
+                                     "(its attribute latent_ar does not hold the coefficients it was given)" % type(eng).__name__)
                 if self.Q and not hasattr(eng, "latent_step"):
                     raise ValueError("a model with latents needs an engine that samples them: %s has no latent_step(a, W, b, seed, sweep)"
                                      % type(eng).__name__)
