@@ -21,6 +21,10 @@ pgl_covariates.hip (include/pyglm_hip_covariates.h) are held to:
                      (covariate_draws), so a neuron's beta does not depend on the shard.
 """
 import numpy as np
+import torch
+
+from ._lib import call, load, ptr
+from .engine import I32, _StepScratch, _on_device
 
 COVARIATE_MAX = 32          # pgl_covariate_max()
 COV_LANE = 3                # the Philox counter lane of z_n (lanes 1 and 2: the noise variance eta and the dispersion xi)
@@ -134,3 +138,52 @@ def covariate_step_host(datasets, Lambda0, h0, z):
         Li, ri = covariate_stats_host(*d)
         Lam, r = (Li, ri) if Lam is None else (Lam + Li, r + ri)
     return covariate_draw_host(Lam, r, Lambda0, h0, z)
+
+
+class _DeviceStep(_StepScratch):
+    """the covariate step on a GibbsEngine's GPU, with its scratch (engine._StepScratch); an engine_factory's engine brings its own"""
+
+    def _alloc(self, T, eng):
+        K, nl, P = eng.K, eng.nloc, eng.K * (eng.K + 1) // 2
+        need = load().pgl_covariate_work_bytes(nl, T, K)
+        eng.reserve("covariates: the step's scratch needs", need + 8 * nl * (P + 3 * K) + 4 * nl + 8 * K * (K + 1))
+        Lambda0, h0 = (torch.from_numpy(np.ascontiguousarray(v)).to(eng.dev) for v in eng.cov_prior[2:])
+        return dict(work=torch.empty(need, dtype=torch.uint8, device=eng.dev), Lam=eng._z(nl, P), r=eng._z(nl, K), z=eng._z(nl, K),
+                    beta=eng._z(nl, K), status=eng._z(nl, dtype=I32), Lambda0=Lambda0, h0=h0)
+
+    @_on_device
+    def covariate_step(self, a, W, b, seed, sweep, keep=False, psi_ready=False):
+        """the module head's step right behind a sweep -> the new beta (nloc, K), the offsets rebuilt from it; a Lambda_n that is not positive
+        definite raises LinAlgError naming the neurons and leaves both.  keep=True (tests): self.last_covariate_stats = (Lambda (nloc, K (K + 1)
+        / 2), r (nloc, K), z) on the host.  psi_ready=True: Psi and the device's weights are at (a, W, b) (the latent step has just run)."""
+        eng = self.eng
+        if not eng.K or eng.likelihood_only or eng.design_only:
+            raise ValueError("covariate_step(): an engine with n_covariates > 0 and sweep buffers is required")
+        K, nl, c = eng.K, eng.nloc, self._scratch()
+        z = covariate_draws(seed, sweep, range(eng.n0, eng.n1), K)
+        c.z.copy_(torch.from_numpy(z)), c.status.zero_(), c.beta.copy_(torch.from_numpy(eng.beta))
+        if not psi_ready:
+            eng._upload_weights(a, W, b)
+        st = eng.fold_data("covariate_fold", lambda i, ds, st, first: call(
+            "pgl_covariate_fold", Psi=ptr(ds.Psi), ldn=eng.ldn, bias=ptr(eng.bias), Omega=ptr(ds.OK), ldo=2 * eng.ldn,
+            Kappa=ptr(ds.OK[:, eng.ldn:]), ldk=2 * eng.ldn, Off=ptr(ds.Off), S=ptr(ds.S), lds=K, T=ds.T, nloc=nl, K=K,
+            Lambda=ptr(c.Lam), r=ptr(c.r), accumulate=int(not first), work=ptr(c.work), hip_stream=st), offset=False, activate=not psi_ready)
+        h = eng._tic("covariate_draw")
+        call("pgl_covariate_draw", Lambda=ptr(c.Lam), r=ptr(c.r), Lambda0=ptr(c.Lambda0), h0=ptr(c.h0), z=ptr(c.z), Beta_out=ptr(c.beta),
+             status=ptr(c.status), nloc=nl, K=K, hip_stream=st)
+        eng._toc(h)
+        bad = np.nonzero(c.status.cpu().numpy())[0]
+        if keep:
+            self.last_covariate_stats = (c.Lam.cpu().numpy(), c.r.cpu().numpy(), z)
+        if bad.size:
+            err = np.linalg.LinAlgError("covariate step: Lambda_n is not positive definite for neurons %s (is covariate_prior's Sigma0 "
+                                        "positive definite?)" % ((bad[:8] + eng.n0).tolist(),))
+            err.neurons, err.beta = (bad + eng.n0).tolist(), c.beta.cpu().numpy()
+            raise err
+        eng.beta_dev[:, :nl].copy_(c.beta.t())           # (into the k-major array the offset kernel reads: a strided device copy)
+        h = eng._tic("covariate_offset")
+        for ds in eng.datasets:
+            eng._offset(ds, st)
+        eng._toc(h)
+        eng.beta = c.beta.cpu().numpy()
+        return eng.beta.copy()

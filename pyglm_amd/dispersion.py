@@ -11,13 +11,15 @@ make the conditional of xi conjugate:
 omega is redrawn from the new xi at the start of the next sweep, so (xi, omega) are updated as a block given the weights and the chain's
 target is the joint posterior.  A regression with xi_prior=(e0, f0) takes the step after every sweep (regression.py, models.py).
 
-dispersion_host is THE DEFINITION of what pgl_dispersion_fold (csrc/pgl_dispersion.hip) computes on the device; a model with an
-engine_factory folds through it on the host from engine.psi(...).
+dispersion_host is THE DEFINITION of what pgl_dispersion_fold (csrc/pgl_dispersion.hip) computes on the device (_DeviceStep); a model with
+an engine_factory folds through it on the host from engine.psi(...) (_HostStep).
 """
 import numpy as np
+import torch
 
-from . import _lib
-from . import simulate as _sim
+from . import _lib, simulate as _sim
+from ._lib import call, ptr
+from .engine import _StepScratch, _on_device, make_gamma_draws
 
 PURPOSE_DISPERSION = _lib.PGL_PURPOSE_DISPERSION          # 4
 MAX_COUNT = _lib.PGL_DISPERSION_MAX_COUNT                 # a larger count is taken as this one: call j of a cell's stream sits in 24 bits
@@ -89,6 +91,46 @@ def dispersion_host(psi, Y, xi, seed, sweep, neuron0, elem0):
     return L, S
 
 
+class _HostStep(object):
+    """the statistics of xi | y, psi where the engine is no device engine: dispersion_host of engine.psi(...) and the model's data and xi"""
+
+    def __init__(self, eng, model):
+        self.eng, self.model = eng, model
+
+    def stats(self, a, W, b, seed, sweep):
+        m, nl, elem0 = self.model, self.model.n1 - self.model.n0, 0
+        xi, L, S = np.array([r.xi for r in m.regressions[m.n0:m.n1]], dtype=np.float64), np.zeros(nl, dtype=np.int64), np.zeros(nl)
+        for i, (_, Y) in enumerate(m.data_list):
+            Yl = np.asarray(Y, dtype=np.float64)[:, m.n0:m.n1]
+            Li, Si = dispersion_host(np.asarray(self.eng.psi(a, W, b, i), dtype=np.float64), Yl, xi, seed, sweep, m.n0, elem0)
+            L, S, elem0 = L + Li, S + Si, elem0 + Yl.shape[0]
+        return L, S
+
+
+class _DeviceStep(_StepScratch):
+    """the same on a GibbsEngine's GPU, with its scratch: the workgroups' partials of the longest data set, L and S (engine._StepScratch)"""
+
+    def _alloc(self, T, eng):
+        need = _lib.load().pgl_dispersion_work_bytes(eng.nloc, T)
+        eng.reserve("dispersion: the scratch needs", need + 16 * eng.nloc)
+        return dict(work=torch.empty(need, dtype=torch.uint8, device=eng.dev), L=eng._z(eng.nloc, dtype=torch.int64), S=eng._z(eng.nloc))
+
+    @_on_device
+    def stats(self, a, W, b, seed, sweep):
+        """at the state (a, W, b) -> (L int64, S float64), host arrays (nloc,): the CRT table counts under the engine's CURRENT per-neuron
+        xi (set_obs_param) and sum_t log(1 + e^psi_t), over every data set (the first fold, accumulate = 0, overwrites both)"""
+        eng = self.eng
+        if eng.obs != eng.OBS["negbin"] or eng.obs_param is None:
+            raise ValueError("dispersion_stats(): an engine of the negative-binomial model with one xi per neuron is required")
+        c = self._scratch()
+        eng._upload_weights(a, W, b)
+        eng.fold_data("dispersion_fold", lambda i, ds, st, first: call(
+            "pgl_dispersion_fold", Psi=ptr(ds.Psi), ldn=eng.ldn, bias=ptr(eng.bias), Y=ptr(ds.Y), T=ds.T, nloc=eng.nloc,
+            xi=ptr(eng.obs_param), seed=int(seed) & (2 ** 64 - 1), sweep=int(sweep) & (2 ** 64 - 1), neuron0=eng.n0, elem0=ds.elem0,
+            L=ptr(c.L), S=ptr(c.S), accumulate=int(not first), work=ptr(c.work), hip_stream=st))
+        return c.L.cpu().numpy(), c.S.cpu().numpy()
+
+
 def table_mean(m, xi):
     """E[l] of a cell of count m: sum_{i < m} xi / (xi + i)"""
     i = np.arange(int(m), dtype=np.float64)
@@ -98,6 +140,5 @@ def table_mean(m, xi):
 def draw_xi(reg, L, S, seed, sweep, neuron):
     """xi ~ Gamma(e0 + L, rate f0 + S) of regression `reg` (its xi_posterior): the standard gamma variate from the host, as eta's is, on
     counter lane XI_LANE of (seed, sweep, GLOBAL neuron)"""
-    from .engine import make_gamma_draws
     alpha, rate = reg.xi_posterior(L, S)
     return float(make_gamma_draws(seed, sweep, [neuron], alpha, lane=XI_LANE)[0] / rate)

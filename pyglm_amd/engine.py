@@ -8,6 +8,7 @@ PyTorch is used for device memory and streams only; all arithmetic is in libpygl
 import ctypes
 import functools
 import time
+import types
 import typing
 
 import numpy as np
@@ -34,6 +35,21 @@ def _on_device(fn):
         with torch.cuda.device(self.dev):
             return fn(self, *args, **kwargs)
     return wrapped
+
+
+class _StepScratch(object):
+    """THE rule of the scratch of the Gibbs steps beside the sweep (dispersion, covariates, latents): owned by the step object, allocated at
+    its first call behind the memory gate (_alloc(T, eng) -> dict, after eng.reserve), kept, allocated again when the longest data set grew"""
+
+    def __init__(self, eng):
+        self.eng, self.dev, self.scratch, self.T = eng, eng.dev, None, -1
+
+    def _scratch(self):
+        T = max([ds.T for ds in self.eng.datasets] or [0])
+        if self.scratch is None or self.T < T:
+            self.scratch = None                       # (released first; a refusal at the gate leaves none, and the next call asks again)
+            self.scratch, self.T = types.SimpleNamespace(**self._alloc(T, self.eng)), T
+        return self.scratch
 
 
 def make_draws(seed, sweep, neuron_ids, N, D):
@@ -126,10 +142,10 @@ class GibbsEngine(object):
         xi: the negative-binomial xi (obs "negbin") or the binomial number of trials n (obs "binomial"): a scalar, or one value per neuron
         of the model (N) or of this shard (n1 - n0).  n_covariates = K > 0: every data set carries covariates S (T, K) and an offset
         Off = S beta' on the device (pyglm_amd/covariates.py); covariate_prior = (mu0, Sigma0) of beta_n, default (0, I).  n_latents = Q > 0
-        (pyglm_amd/latents.py): Q further columns of S whose values are sampled (latent_step) -- K becomes n_covariates + Q, S is
-        [S_obs | X] with X zero at add_data, and covariate_prior is the prior of all K weights (latents.joint_prior).  latent_ar = phi (a
-        scalar or Q values in [0, 1)): the latents' AR(1) prior -- where some phi_q > 0 latent_step draws a data set's X jointly
-        (pgl_latent_ar_draw); None or all zeros: the independent bins of pgl_latent_draw, launch for launch."""
+        (pyglm_amd/latents.py): Q further columns of S whose values are sampled (latents._DeviceStep) -- K becomes n_covariates + Q, S
+        is [S_obs | X] with X zero at add_data, and covariate_prior is the prior of all K weights (latents.joint_prior).  latent_ar =
+        phi (a scalar or Q values in [0, 1)): the latents' AR(1) prior -- where some phi_q > 0 the latent step draws a data set's X
+        jointly (pgl_latent_ar_draw); None or all zeros: the independent bins of pgl_latent_draw, launch for launch."""
         from . import covariates as _cov
         from . import latents as _lat
         self.K_obs = _cov.check_count(n_covariates)
@@ -204,7 +220,6 @@ class GibbsEngine(object):
         self.wait_seconds = 0.0
         self.overlap_seconds = 0.0
         self.launch_seconds = 0.0      # inside the pgl_sweep call itself: ~3 000 launches at the headline size (and, when the queue is full, waiting)
-        self._disp = None              # (work, L, S): scratch and results of dispersion_stats, allocated at its first call
         self._sweep_serial = 0         # sweeps queued so far, and where the last one's perm lies in _din (the chain diagnostics form the
         self._perm_off = None          # conditional edge probabilities from the last sweep's log-odds and proposal order)
 
@@ -335,8 +350,6 @@ class GibbsEngine(object):
         self.Wt = self._z(self.Dp, self.ldn)          # k-major weights for the activation contraction
         self.bias = self._z(nl)
         self.border = self._z(2 * self.ldn, self.Dp)
-        self._cov = None                              # scratch and results of covariate_step, allocated at its first call
-        self._lat = None                              # ... and of latent_step
         if self.K:
             # covariate weights: k-major on the device like the activation's (pgl_covariate_offset), and the host's copy of what is there
             self.beta_dev = self._z(self.K, self.ldn)
@@ -661,29 +674,27 @@ class GibbsEngine(object):
         self.Wt.copy_(torch.from_numpy(Wt))
         self.bias.copy_(torch.from_numpy(np.asarray(b, dtype=np.float64).reshape(self.nloc)))
 
-    def _activation(self, ds, st):
-        """queues Psi = X (a * W)' of data set ds for the whole shard (regression.py:195-201; bias not added), as its own stage"""
-        h = self._tic("activation", 2.0 * ds.T * self.D * self.nloc)
-        call("pgl_activation", Xt=ptr(ds.Xt), ldxt=ds.Tp, Wt=ptr(self.Wt), ldw=self.ldn, Psi=ptr(ds.Psi), ldpsi=self.ldn, T=ds.T, Dk=self.Dp,
-             nloc=self.nloc, hip_stream=st)
-        self._toc(h)
-
-    def fold_data(self, stage, launch, only=None):
-        """THE walk over the data sets, behind weights the caller has uploaded (_upload_weights): per data set ONE activation, then
-        launch(i, ds, st, first) as the timed stage `stage` (work: T * nloc cells) on the engine's stream st.  first: true for the first
-        data set visited -- the launch overwrites its sums there and adds to them behind it.  only = i: data set i alone.  Returns st, for
-        what the caller queues behind the walk.  Having this method is what makes an engine a device engine to the read-outs of the
-        chain (summary.device_engine).  An engine with covariates adds each data set's offset to Psi right behind the activation: the
-        read-outs that walk through here follow beta without knowing of it."""
-        st = self._st()
-        first = True
+    def fold_data(self, stage, launch, only=None, offset=True, activate=True):
+        """THE walk over the data sets, behind weights the caller has uploaded (_upload_weights): per data set ONE activation -- Psi =
+        X (a * W)' for the whole shard (regression.py:195-201; bias not added), a stage of its own --, then launch(i, ds, st, first) as
+        the timed stage `stage` (work: T * nloc cells; None: the launch times its stages itself) on the engine's stream st.  first: the
+        first data set visited -- the launch overwrites its sums there and adds to them behind it.  only = i: data set i alone.  Returns
+        st.  Having this method is what makes an engine a device engine (summary.device_engine).  An engine with covariates adds each
+        data set's offset to Psi right behind the activation: the read-outs follow beta without knowing of it; offset=False leaves Psi
+        the net activation (the covariate and latent folds), activate=False as a walk just before left it."""
+        st, first = self._st(), True
         for i, ds in enumerate(self.datasets):
             if only is not None and i != only:
                 continue
-            self._activation(ds, st)
-            if self.K:
-                call("pgl_covariate_add_offset", Psi=ptr(ds.Psi), ldpsi=self.ldn, Off=ptr(ds.Off), ldo=self.ldn, T=ds.T, nloc=self.nloc, hip_stream=st)
-            h = self._tic(stage, float(ds.T) * self.nloc)
+            if activate:
+                h = self._tic("activation", 2.0 * ds.T * self.D * self.nloc)
+                call("pgl_activation", Xt=ptr(ds.Xt), ldxt=ds.Tp, Wt=ptr(self.Wt), ldw=self.ldn, Psi=ptr(ds.Psi), ldpsi=self.ldn, T=ds.T,
+                     Dk=self.Dp, nloc=self.nloc, hip_stream=st)
+                self._toc(h)
+                if offset and self.K:
+                    call("pgl_covariate_add_offset", Psi=ptr(ds.Psi), ldpsi=self.ldn, Off=ptr(ds.Off), ldo=self.ldn, T=ds.T, nloc=self.nloc,
+                         hip_stream=st)
+            h = self._tic(stage, float(ds.T) * self.nloc) if stage else None
             launch(i, ds, st, first)
             self._toc(h)
             first = False
@@ -754,32 +765,6 @@ class GibbsEngine(object):
         idx = torch.from_numpy(np.ascontiguousarray(cols, dtype=np.int64)).to(self.dev)
         return self.datasets[i].Psi[start:stop].index_select(1, idx).cpu().numpy()
 
-    # ------------------------------------------------------------------ the negative-binomial dispersion (pyglm_amd/dispersion.py)
-    @_on_device
-    def dispersion_stats(self, a, W, b, seed, sweep):
-        """the sufficient statistics of xi | y, psi at the state (a, W, b) -> (L int64, S float64), host arrays (nloc,): the CRT table counts
-        under the engine's CURRENT per-neuron xi (set_obs_param) and sum_t log(1 + e^psi_t), over every data set.  One upload of the
-        weights, then the walk (fold_data) with ONE pgl_dispersion_fold per data set (dispersion.dispersion_host states what it computes),
-        the data sets behind the first adding to the same sums.  The scratch -- the workgroups' partials of the longest data set, and L and
-        S per neuron -- is allocated at the first call, behind the memory gate (reserve)."""
-        if self.obs != OBS_NEGBIN or self.obs_param is None:
-            raise ValueError("dispersion_stats(): an engine of the negative-binomial model with one xi per neuron is required")
-        T = max([ds.T for ds in self.datasets] or [0])
-        need = _lib.load().pgl_dispersion_work_bytes(self.nloc, T)
-        if self._disp is None or self._disp[0].numel() < need:
-            self._disp = None
-            self.reserve("dispersion: the scratch needs", need + 16 * self.nloc)
-            self._disp = (torch.empty(need, dtype=torch.uint8, device=self.dev), self._z(self.nloc, dtype=torch.int64), self._z(self.nloc))
-        work, L, S = self._disp
-        self._upload_weights(a, W, b)
-        if not self.datasets:
-            L.zero_(), S.zero_()                  # (with data the first fold, accumulate = 0, overwrites both)
-        self.fold_data("dispersion_fold", lambda i, ds, st, first: call(
-            "pgl_dispersion_fold", Psi=ptr(ds.Psi), ldn=self.ldn, bias=ptr(self.bias), Y=ptr(ds.Y), T=ds.T, nloc=self.nloc,
-            xi=ptr(self.obs_param), seed=int(seed) & (2 ** 64 - 1), sweep=int(sweep) & (2 ** 64 - 1), neuron0=self.n0, elem0=ds.elem0,
-            L=ptr(L), S=ptr(S), accumulate=int(not first), work=ptr(work), hip_stream=st))
-        return L.cpu().numpy(), S.cpu().numpy()
-
     # ------------------------------------------------------------------ external covariates (pyglm_amd/covariates.py)
     def _offset(self, ds, st):
         """queues Off = S beta' of data set ds from the weights on the device"""
@@ -800,73 +785,6 @@ class GibbsEngine(object):
         for ds in self.datasets:
             self._offset(ds, st)
 
-    @_on_device
-    def covariate_step(self, a, W, b, seed, sweep, keep=False, psi_ready=False):
-        """beta | omega, W, b for the shard's neurons, right behind a sweep (covariates.covariate_step_host states it): from the
-        [Omega | Kappa] that sweep left in every data set's OK -- Kappa the reduced one --, the offset it ran under (still in Off) and
-        psi_net at the state (a, W, b) the sweep returned.  One upload of the weights, then per data set one activation and ONE
-        pgl_covariate_fold (the data sets behind the first adding), then pgl_covariate_draw with the host's normals (covariates.
-        covariate_draws: lane 3 of (seed, sweep, global neuron)) and the offsets rebuilt from the new beta, which is returned, (nloc, K).
-        The scratch -- the workgroups' partials of the longest data set, Lambda, r, z, beta and the flags -- is allocated at the first
-        call, behind the memory gate.  keep=True: self.last_covariate_stats = (Lambda (nloc, K (K + 1) / 2), r (nloc, K), z) on the host
-        (tests).  A Lambda_n that is not positive definite (a bad prior) raises np.linalg.LinAlgError naming the neurons; beta and the
-        offsets are then left as they were.  psi_ready=True: every data set's Psi already holds the activation at (a, W, b) and the device
-        the weights (latent_step has just run there): neither is done again."""
-        from . import covariates as _cov
-        if not self.K or self.likelihood_only or self.design_only:
-            raise ValueError("covariate_step(): an engine with n_covariates > 0 and sweep buffers is required")
-        K, nl = self.K, self.nloc
-        P = K * (K + 1) // 2
-        T = max([ds.T for ds in self.datasets] or [0])
-        need = _lib.load().pgl_covariate_work_bytes(nl, T, K)
-        if self._cov is None or self._cov["work"].numel() < need:
-            self._cov = None
-            self.reserve("covariates: the step's scratch needs", need + 8 * nl * (P + 3 * K) + 4 * nl + 8 * K * (K + 1))
-            _, _, Lambda0, h0 = self.cov_prior
-            self._cov = dict(work=torch.empty(need, dtype=torch.uint8, device=self.dev), Lam=self._z(nl, P), r=self._z(nl, K), z=self._z(nl, K),
-                             beta=self._z(nl, K), status=self._z(nl, dtype=I32), Lambda0=torch.from_numpy(np.ascontiguousarray(Lambda0)).to(self.dev),
-                             h0=torch.from_numpy(np.ascontiguousarray(h0)).to(self.dev))
-        c = self._cov
-        z = _cov.covariate_draws(seed, sweep, range(self.n0, self.n1), K)
-        c["z"].copy_(torch.from_numpy(z))
-        c["status"].zero_()
-        c["beta"].copy_(torch.from_numpy(self.beta))
-        if not psi_ready:
-            self._upload_weights(a, W, b)
-        st = self._st()
-        if not self.datasets:
-            c["Lam"].zero_(), c["r"].zero_()
-        for i, ds in enumerate(self.datasets):       # (not fold_data: the fold takes the activation without the offset)
-            if not psi_ready:
-                self._activation(ds, st)
-            h = self._tic("covariate_fold", float(ds.T) * nl)
-            call("pgl_covariate_fold", Psi=ptr(ds.Psi), ldn=self.ldn, bias=ptr(self.bias), Omega=ptr(ds.OK), ldo=2 * self.ldn,
-                 Kappa=ctypes.c_void_p(ds.OK.data_ptr() + 8 * self.ldn), ldk=2 * self.ldn, Off=ptr(ds.Off), S=ptr(ds.S), lds=K, T=ds.T, nloc=nl, K=K,
-                 Lambda=ptr(c["Lam"]), r=ptr(c["r"]), accumulate=int(i > 0), work=ptr(c["work"]), hip_stream=st)
-            self._toc(h)
-        h = self._tic("covariate_draw")
-        call("pgl_covariate_draw", Lambda=ptr(c["Lam"]), r=ptr(c["r"]), Lambda0=ptr(c["Lambda0"]), h0=ptr(c["h0"]), z=ptr(c["z"]),
-             Beta_out=ptr(c["beta"]), status=ptr(c["status"]), nloc=nl, K=K, hip_stream=st)
-        self._toc(h)
-        status = c["status"].cpu().numpy()
-        if keep:
-            self.last_covariate_stats = (c["Lam"].cpu().numpy(), c["r"].cpu().numpy(), z)
-        if status.any():
-            bad = np.nonzero(status)[0]
-            err = np.linalg.LinAlgError("covariate step: Lambda_n is not positive definite for neurons %s (is covariate_prior's Sigma0 "
-                                        "positive definite?)" % ((bad[:8] + self.n0).tolist(),))
-            err.neurons = (bad + self.n0).tolist()
-            err.beta = c["beta"].cpu().numpy()
-            raise err
-        # (the transposition into the k-major array the offset kernel reads is a strided device copy)
-        self.beta_dev[:, :nl].copy_(c["beta"].t())
-        h = self._tic("covariate_offset")
-        for ds in self.datasets:
-            self._offset(ds, st)
-        self._toc(h)
-        self.beta = c["beta"].cpu().numpy()
-        return self.beta.copy()
-
     # ------------------------------------------------------------------ latent common input (pyglm_amd/latents.py)
     def _need_latents(self, what):
         if not self.Q:
@@ -886,66 +804,6 @@ class GibbsEngine(object):
         ds = self.datasets[i]
         ds.S[:, self.K_obs:] = torch.from_numpy(check_latents(X, ds.T, self.Q)).to(self.dev)
         self._offset(ds, self._st())
-
-    @_on_device
-    def latent_step(self, a, W, b, seed, sweep, keep=False):
-        """x_t | omega, W, b, beta for every time bin of every data set, right behind a sweep and BEFORE covariate_step (latents.
-        latent_step_host states it): from the [Omega | Kappa] that sweep left in every data set's OK -- Kappa the reduced one --, the
-        latent columns it ran under (still in S), the loadings in beta_dev and psi_net at the state (a, W, b) the sweep returned.  One
-        upload of the weights, then per data set one activation, ONE pgl_latent_fold and ONE pgl_latent_draw on the device's Philox
-        stream (seed, sweep, elem0 + t), which writes the new x_t into S.  With a temporal prior (latent_ar, some phi_q > 0) the draw is
-        pgl_latent_ar_draw instead -- the data set's X jointly, on the same normals, stage "latent_ar_draw" -- and its scratch
-        (pgl_latent_ar_scratch of the longest data set) is allocated with Lambda and r.  Off is NOT touched: it still holds the offset the sweep ran
-        under, which covariate_step needs (call it with psi_ready=True: Psi and the weights are in place); that step rebuilds Off from
-        the new latents and the new beta.  The scratch -- Lambda and r, (Q (Q + 1) / 2 + Q) * 8 bytes per bin of the longest data set --
-        is allocated at the first call, behind the memory gate.  keep=True: self.last_latent_stats = [(Lambda (T, P), r (T, Q)), ...]
-        per data set on the host (tests).  A pivot that is not positive raises np.linalg.LinAlgError (non-finite input: I + Lambda_t
-        is positive definite otherwise)."""
-        self._need_latents("latent_step()")
-        if self.likelihood_only or self.design_only:
-            raise ValueError("latent_step(): an engine with sweep buffers is required")
-        Q, nl = self.Q, self.nloc
-        P = Q * (Q + 1) // 2
-        T = max([ds.T for ds in self.datasets] or [0])
-        ar = bool(np.any(self.latent_ar > 0.0))
-        if self._lat is None or self._lat["T"] < T:
-            self._lat = None
-            ar_bytes = int(_lib.load().pgl_latent_ar_scratch(T, Q, 0)) if ar else 0
-            self.reserve("latents: the step's scratch needs", 8 * T * (P + Q) + 4 + ar_bytes)
-            self._lat = dict(T=T, Lam=self._z(max(T, 1), P), r=self._z(max(T, 1), Q), status=self._z(1, dtype=I32))
-            if ar:
-                self._lat.update(ar=torch.empty(max(ar_bytes // 8, 1), dtype=F64, device=self.dev), ar_bytes=ar_bytes,
-                                 phi=(ctypes.c_double * Q)(*self.latent_ar))
-        c = self._lat
-        c["status"].zero_()
-        self._upload_weights(a, W, b)
-        st = self._st()
-        kept = []
-        for ds in self.datasets:                     # (not fold_data: the fold takes the activation without the offset)
-            self._activation(ds, st)
-            h = self._tic("latent_fold", float(ds.T) * nl)
-            call("pgl_latent_fold", Psi=ptr(ds.Psi), ldn=self.ldn, bias=ptr(self.bias), Omega=ptr(ds.OK), ldo=2 * self.ldn,
-                 Kappa=ctypes.c_void_p(ds.OK.data_ptr() + 8 * self.ldn), ldk=2 * self.ldn, S=ptr(ds.S), lds=self.K, col0=self.K_obs,
-                 Beta=ptr(self.beta_dev), ldb=self.ldn, T=ds.T, nloc=nl, Q=Q, Lambda=ptr(c["Lam"]), r=ptr(c["r"]), hip_stream=st)
-            self._toc(h)
-            if keep:
-                kept.append((c["Lam"][:ds.T].cpu().numpy(), c["r"][:ds.T].cpu().numpy()))
-            if ar:
-                h = self._tic("latent_ar_draw", float(ds.T))
-                call("pgl_latent_ar_draw", Lambda=ptr(c["Lam"]), r=ptr(c["r"]), phi=ctypes.cast(c["phi"], ctypes.c_void_p), z_override=None,
-                     seed=int(seed) & (2 ** 64 - 1), sweep=int(sweep) & (2 ** 64 - 1), elem0=ds.elem0, S=ptr(ds.S), lds=self.K, col0=self.K_obs,
-                     status=ptr(c["status"]), T=ds.T, Q=Q, seg=0, scratch=ptr(c["ar"]), scratch_bytes=c["ar_bytes"], hip_stream=st)
-            else:
-                h = self._tic("latent_draw", float(ds.T))
-                call("pgl_latent_draw", Lambda=ptr(c["Lam"]), r=ptr(c["r"]), z_override=None, seed=int(seed) & (2 ** 64 - 1),
-                     sweep=int(sweep) & (2 ** 64 - 1), elem0=ds.elem0, S=ptr(ds.S), lds=self.K, col0=self.K_obs, status=ptr(c["status"]), T=ds.T, Q=Q,
-                     hip_stream=st)
-            self._toc(h)
-        if keep:
-            self.last_latent_stats = kept
-        if int(c["status"].item()):
-            raise np.linalg.LinAlgError("latent step: %s is not positive definite for some time bin (are the loadings, omega and "
-                                        "the activation finite?)" % ("the latents' precision" if ar else "I + Lambda_t"))
 
     # ------------------------------------------------------------------ one Gibbs sweep of the shard's regressions
     def _sweep_args(self, ovs=None):

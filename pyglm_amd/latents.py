@@ -28,9 +28,13 @@ latent ones, K = K_obs + Q <= COVARIATE_MAX, and every data set's S (T, K) on th
                      pgl_latent_dynamics.hip).  phi = 0 is the law above, launch for launch.
 
 X and C alone are defined only up to rotation and sign; the identifiable quantity is the common input X C' (T, N)."""
+import ctypes
+
 import numpy as np
 
 from . import covariates as _cov
+from ._lib import call, load, ptr
+from .engine import I32, _StepScratch, _on_device
 
 LATENT_MAX = 8              # pgl_latent_max(): one 8 x 8 diagonal block of the covariate fold
 PURPOSE_LATENT = 6          # PGL_PURPOSE_LATENT (purposes 1 .. 5: pgl_rng.h, the dispersion header, the SBM header)
@@ -266,3 +270,49 @@ def latent_ar_step_host(C, x_old, Omega, Kappa, psi_net, z, phi, seg=None):
 def common_input_host(X, C):
     """(T, N) = X C': the drive the latents give every neuron, by covariates.offset_host's rule (what the device adds to psi)"""
     return _cov.offset_host(X, C)
+
+
+class _DeviceStep(_StepScratch):
+    """the latent step on a GibbsEngine's GPU under either prior, with its scratch (engine._StepScratch); an engine_factory's engine brings its own"""
+
+    def _alloc(self, T, eng):
+        Q, P = eng.Q, eng.Q * (eng.Q + 1) // 2
+        ar_bytes = int(load().pgl_latent_ar_scratch(T, Q, 0)) if np.any(eng.latent_ar > 0.0) else 0
+        eng.reserve("latents: the step's scratch needs", 8 * T * (P + Q) + 4 + ar_bytes)
+        return dict(Lam=eng._z(max(T, 1), P), r=eng._z(max(T, 1), Q), status=eng._z(1, dtype=I32), ar_bytes=ar_bytes,
+                    ar=eng._z(ar_bytes // 8) if ar_bytes else None, phi=(ctypes.c_double * Q)(*eng.latent_ar))
+
+    @_on_device
+    def latent_step(self, a, W, b, seed, sweep, keep=False):
+        """the module head's step right behind a sweep and BEFORE the covariate step: per data set ONE fold and ONE draw (the joint one
+        where some phi_q > 0) into S -- the draw in front of the next data set's fold (Lambda and r are ONE buffer), so the launch holds
+        both stages and times each itself.  Off is NOT touched: the covariate step (psi_ready=True) needs the offset the sweep ran under.
+        keep=True (tests): self.last_latent_stats = [(Lambda (T, P), r (T, Q)), ...] on the host.  A bad pivot raises LinAlgError."""
+        eng = self.eng
+        eng._need_latents("latent_step()")
+        if eng.likelihood_only or eng.design_only:
+            raise ValueError("latent_step(): an engine with sweep buffers is required")
+        Q, nl, c, kept, ar = eng.Q, eng.nloc, self._scratch(), [], bool(np.any(eng.latent_ar > 0.0))
+        draw = "latent_ar_draw" if ar else "latent_draw"
+        more = dict(phi=ctypes.cast(c.phi, ctypes.c_void_p), seg=0, scratch=ptr(c.ar), scratch_bytes=c.ar_bytes) if ar else {}
+        c.status.zero_()
+        eng._upload_weights(a, W, b)
+
+        def launch(i, ds, st, first):
+            h = eng._tic("latent_fold", float(ds.T) * nl)
+            call("pgl_latent_fold", Psi=ptr(ds.Psi), ldn=eng.ldn, bias=ptr(eng.bias), Omega=ptr(ds.OK), ldo=2 * eng.ldn,
+                 Kappa=ptr(ds.OK[:, eng.ldn:]), ldk=2 * eng.ldn, S=ptr(ds.S), lds=eng.K, col0=eng.K_obs,
+                 Beta=ptr(eng.beta_dev), ldb=eng.ldn, T=ds.T, nloc=nl, Q=Q, Lambda=ptr(c.Lam), r=ptr(c.r), hip_stream=st)
+            eng._toc(h)
+            if keep:
+                kept.append((c.Lam[:ds.T].cpu().numpy(), c.r[:ds.T].cpu().numpy()))
+            h = eng._tic(draw, float(ds.T))
+            call("pgl_" + draw, Lambda=ptr(c.Lam), r=ptr(c.r), z_override=None, seed=int(seed) & (2 ** 64 - 1), sweep=int(sweep) & (2 ** 64 - 1),
+                 elem0=ds.elem0, S=ptr(ds.S), lds=eng.K, col0=eng.K_obs, status=ptr(c.status), T=ds.T, Q=Q, hip_stream=st, **more)
+            eng._toc(h)
+        eng.fold_data(None, launch, offset=False)
+        if keep:
+            self.last_latent_stats = kept
+        if int(c.status.item()):
+            raise np.linalg.LinAlgError("latent step: %s is not positive definite for some time bin (are the loadings, omega and "
+                                        "the activation finite?)" % ("the latents' precision" if ar else "I + Lambda_t"))

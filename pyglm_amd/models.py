@@ -180,6 +180,12 @@ class NonlinearAutoregressiveModel(object):
                 import torch
                 dev = self._device or ("cuda:%d" % torch.cuda.current_device())
                 self._engine = GibbsEngine(self.N, self.B, self.n0, self.n1, device=dev, **kw)
+            # the Gibbs steps, held (scratch and all) as long as the engine: device classes, or (engine_factory) xi's host twin and the engine's own
+            from . import covariates as _cov, dispersion as _disp, latents as _lat
+            from .summary import device_engine
+            eng, dev = self._engine, device_engine(self._engine)
+            self._xi_step = _disp._DeviceStep(eng) if dev else _disp._HostStep(eng, self)
+            self._cov_step, self._lat_step = (_cov._DeviceStep(eng), _lat._DeviceStep(eng)) if dev else (eng, eng)
         return self._engine
 
     # ---- chain state: three arrays of the model, of which every regression's (a, W, b) are row views (regression._adopt)
@@ -335,21 +341,10 @@ class NonlinearAutoregressiveModel(object):
 
     def _resample_xi(self, a, W, b):
         """xi of the shard's regressions after the CRT step under the weights (a, W, b) the sweep just drew -> (nloc,): the table counts and
-        sum_t log(1 + e^psi) from the device (engine.dispersion_stats), or through dispersion.dispersion_host from engine.psi for an
-        engine without it; the gamma variates from the host, keyed by the global neuron.  A regression without xi_prior keeps its xi."""
+        sum_t log(1 + e^psi) from self._xi_step; the gamma variates from the host, keyed by the global neuron.  Without xi_prior xi stays."""
         from . import dispersion as _disp
         regs = self.regressions[self.n0:self.n1]
-        eng = self.engine
-        if hasattr(eng, "dispersion_stats"):
-            L, S = eng.dispersion_stats(a, W, b, self.seed, self.sweeps_done)
-        else:
-            xi_now = np.array([r.xi for r in regs], dtype=np.float64)
-            L, S, elem0 = np.zeros(len(regs), dtype=np.int64), np.zeros(len(regs)), 0
-            for i, (_, Y) in enumerate(self.data_list):
-                Yl = np.asarray(Y, dtype=np.float64)[:, self.n0:self.n1]
-                Li, Si = _disp.dispersion_host(np.asarray(eng.psi(a, W, b, i), dtype=np.float64), Yl, xi_now, self.seed, self.sweeps_done,
-                                               self.n0, elem0)
-                L, S, elem0 = L + Li, S + Si, elem0 + Yl.shape[0]
+        L, S = self._xi_step.stats(a, W, b, self.seed, self.sweeps_done)
         xi = np.array([r.xi for r in regs], dtype=np.float64)
         for i, r in enumerate(regs):
             if getattr(r, "xi_prior", None) is not None:
@@ -961,8 +956,8 @@ class NonlinearAutoregressiveModel(object):
             # -- with latents x | omega, W, b, beta first: Off must still hold the offset the sweep ran under when beta's fold recovers kappa,
             # and beta is then drawn given the new x; the latent step leaves Psi and the weights in place for it
             if self.Q:
-                self.engine.latent_step(a, W, b, self.seed, self.sweeps_done)
-            cov_beta = self.engine.covariate_step(a, W, b, self.seed, self.sweeps_done, **(dict(psi_ready=True) if self.Q else {}))
+                self._lat_step.latent_step(a, W, b, self.seed, self.sweeps_done)
+            cov_beta = self._cov_step.covariate_step(a, W, b, self.seed, self.sweeps_done, **(dict(psi_ready=True) if self.Q else {}))
         if gaussian:
             # noise variances (regression.py:433-445): residual sums of squares under the NEW weights from the device, gamma draws
             # keyed by the global neuron index

@@ -417,8 +417,10 @@ class SparseNegativeBinomialRegression(_SparsePGRegressionBase):
     def _after_sweep(self, eng, seed, sweep):
         if getattr(self, "xi_prior", None) is None:
             return
-        from .dispersion import draw_xi
-        L, S = eng.dispersion_stats(self.a[None], self.W[None], self.b, seed, sweep)      # under the NEW weights
+        from .dispersion import _DeviceStep, draw_xi
+        if len(self._engine_cache) < 3:            # (key, engine, the statistics' object: kept, scratch and all, as long as the engine is)
+            self._engine_cache += (_DeviceStep(eng),)
+        L, S = self._engine_cache[2].stats(self.a[None], self.W[None], self.b, seed, sweep)      # under the NEW weights
         self.xi = draw_xi(self, int(L[0]), float(S[0]), seed, sweep, 0)
 
     def a_func(self, data):

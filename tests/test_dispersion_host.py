@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 class XiOracleEngine(OracleEngine):
     """the oracle-backed engine with one xi per local neuron and set_obs_param: what a model that learns xi needs of an engine_factory
-    engine.  It has no dispersion_stats, so the model folds through dispersion.dispersion_host from psi(...)."""
+    engine.  It is no device engine (no fold_data), so the model folds through dispersion.dispersion_host from psi(...)."""
 
     def __init__(self, N, B, n0=0, n1=None, obs="bernoulli", xi=1.0, **kw):
         super(XiOracleEngine, self).__init__(N, B, n0, n1, obs=obs, xi=xi, **kw)

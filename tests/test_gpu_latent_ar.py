@@ -184,8 +184,9 @@ def test_bits_do_not_depend_on_the_launch(Q):
     from pyglm_amd import _lib
     T, phi, seed, sweep = 20011, 0.9, 7, 2
     eng, (a1, W1, b1) = _engine_with_two_sets(T, Q, phi)
-    eng.latent_step(a1, W1, b1, seed, sweep, keep=True)
-    LamP, r = eng.last_latent_stats[1]
+    step = lat._DeviceStep(eng)
+    step.latent_step(a1, W1, b1, seed, sweep, keep=True)
+    LamP, r = step.last_latent_stats[1]
     x_eng = eng.latents(1)
     ds = eng.datasets[1]
     assert ds.elem0 > 0 and np.all(np.isfinite(x_eng))
@@ -295,13 +296,14 @@ def test_engine_step_follows_the_law():
     a1, W1, b1, _ = eng.sweep(a, W, b, np.full((N, N), KW["rho"]), *hyp, perm, u, z, seed=seed, sweep=sweep)
     off_before = ds.Off.clone()
     eng.profile = True
-    eng.latent_step(a1, W1, b1, seed, sweep, keep=True)
+    step = lat._DeviceStep(eng)
+    step.latent_step(a1, W1, b1, seed, sweep, keep=True)
     tm = eng.collect_timings()
     assert tm["latent_fold"]["calls"] == 1 and tm["latent_ar_draw"]["calls"] == 1 and "latent_draw" not in tm
     assert torch.equal(off_before.view(torch.int64), ds.Off.view(torch.int64)), "the latent step touched Off"
     S_new = ds.S.cpu().numpy()
     np.testing.assert_array_equal(S_new[:, :K_obs], S_obs)
-    LamD, rD = eng.last_latent_stats[0]
+    LamD, rD = step.last_latent_stats[0]
     Lam = cov.tri_unpack(LamD, Q)
     J = lat.ar_precision_dense(Lam, phi)
     w = np.linalg.eigvalsh(J)

@@ -252,6 +252,7 @@ def test_engine_step_follows_the_host_law():
     beta0, X0 = rng.standard_normal((N, K)) * 0.7, rng.standard_normal((T, Q))
     eng = GibbsEngine(N, B, n_covariates=K_obs, n_latents=Q)
     eng.add_data(Y, X=X, covariates=S_obs)
+    lstep, cstep = lat._DeviceStep(eng), cov._DeviceStep(eng)
     ds = eng.datasets[0]
     assert eng.K == K and tuple(ds.S.shape) == (T, K) and not eng.latents(0).any()
     eng.set_covariate_weights(beta0)
@@ -264,7 +265,7 @@ def test_engine_step_follows_the_host_law():
     perm, u, z = make_draws(EN["seed"], EN["sweep"], range(N), N, N * B)
     a1, W1, b1, _ = eng.sweep(a, W, b, np.full((N, N), KW["rho"]), *hyp, perm, u, z, seed=EN["seed"], sweep=EN["sweep"])
     off_before = ds.Off.clone()
-    eng.latent_step(a1, W1, b1, EN["seed"], EN["sweep"], keep=True)
+    lstep.latent_step(a1, W1, b1, EN["seed"], EN["sweep"], keep=True)
     assert torch.equal(off_before.view(torch.int64), ds.Off.view(torch.int64)), "the latent step touched Off"
     OK = ds.OK[:T].cpu().numpy()
     Om, Kp = OK[:, :N], OK[:, eng.ldn:eng.ldn + N]
@@ -279,7 +280,7 @@ def test_engine_step_follows_the_host_law():
     aC = np.abs(C)
     mL = np.einsum("tn,nj,nk->tjk", Om, aC, aC)
     mr = (np.abs(Kp) + Om * (np.abs(X0).dot(aC.T) + np.abs(psi_net.astype(np.float64)))).dot(aC)
-    LamD, rD = eng.last_latent_stats[0]
+    LamD, rD = lstep.last_latent_stats[0]
     _check_fold((LamD, rD), (cov.tri_pack(Lr), rr, cov.tri_pack(mL), mr), N, Q, "engine fold")
     zs = lat.latent_normals_host(EN["seed"], EN["sweep"], ds.elem0, T, Q)
     LamF = cov.tri_unpack(LamD, Q)
@@ -288,7 +289,7 @@ def test_engine_step_follows_the_host_law():
         ref = _ld_draw(A, rD[t].astype(LD), zs[t])
         assert float(np.linalg.norm(S_new[t, K_obs:] - ref)) <= 8 * Q * U * np.linalg.cond(A) * float(np.linalg.norm(ref)) + np.sqrt(Q) * 2.0 ** -44
     np.testing.assert_allclose(S_new[:, K_obs:], lat.latent_step_host(C, X0, Om, Kp, Psi + bias, zs), rtol=1e-9, atol=1e-11)
-    beta1 = eng.covariate_step(a1, W1, b1, EN["seed"], EN["sweep"], psi_ready=True)
+    beta1 = cstep.covariate_step(a1, W1, b1, EN["seed"], EN["sweep"], psi_ready=True)
     assert beta1.shape == (N, K) and np.abs(beta1 - beta0).min() > 0
     np.testing.assert_array_equal(ds.Off[:, :N].cpu().numpy(), cov.offset_host(S_new, beta1))
     np.testing.assert_array_equal(ds.S.cpu().numpy(), S_new)                # the covariate step leaves S alone
@@ -296,11 +297,11 @@ def test_engine_step_follows_the_host_law():
     eng.set_covariate_weights(beta0)
     eng.set_latents(0, X0)
     eng.sweep(a, W, b, np.full((N, N), KW["rho"]), *hyp, perm, u, z, seed=EN["seed"], sweep=EN["sweep"])
-    eng.latent_step(a1, W1, b1, EN["seed"], EN["sweep"])
+    lstep.latent_step(a1, W1, b1, EN["seed"], EN["sweep"])
     np.testing.assert_array_equal(ds.S.cpu().numpy(), S_new)
-    np.testing.assert_array_equal(eng.covariate_step(a1, W1, b1, EN["seed"], EN["sweep"]), beta1)
+    np.testing.assert_array_equal(cstep.covariate_step(a1, W1, b1, EN["seed"], EN["sweep"]), beta1)
     eng.profile = True
-    eng.latent_step(a1, W1, b1, EN["seed"], EN["sweep"] + 1)
+    lstep.latent_step(a1, W1, b1, EN["seed"], EN["sweep"] + 1)
     tm = eng.collect_timings()
     assert tm["latent_fold"]["calls"] == 1 and tm["latent_draw"]["calls"] == 1 and tm["latent_fold"]["work"] == T * N
 

@@ -138,7 +138,7 @@ def end_to_end(name, cls, N, B, T, reps, K=2, **reg_kw):
         if k:
             eng = model.engine
             a, W, b = model._local_state()
-            step = lambda: eng.covariate_step(a, W, b, model.seed, model.sweeps_done)
+            step = lambda: model._cov_step.covariate_step(a, W, b, model.seed, model.sweeps_done)
             step()
             out["covariate_step"] = ms_stats([wall(step) for _ in range(reps)])
             eng.profile = True

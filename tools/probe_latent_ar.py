@@ -129,7 +129,7 @@ def end_to_end(name, cls, N, B, T, reps, **reg_kw):
         out["resample_model_" + label] = ms_stats([wall(model.resample_model) for _ in range(reps)])
         eng = model.engine
         a, W, b = model._local_state()
-        step = lambda: eng.latent_step(a, W, b, model.seed, model.sweeps_done)
+        step = lambda: model._lat_step.latent_step(a, W, b, model.seed, model.sweeps_done)
         step()
         eng.profile = True
         step()

@@ -121,7 +121,7 @@ def end_to_end(name, cls, N, B, T, reps, Q=1, **reg_kw):
         if q:
             eng = model.engine
             a, W, b = model._local_state()
-            step = lambda: eng.latent_step(a, W, b, model.seed, model.sweeps_done)
+            step = lambda: model._lat_step.latent_step(a, W, b, model.seed, model.sweeps_done)
             step()
             out["latent_step"] = ms_stats([wall(step) for _ in range(reps)])
             eng.profile = True
