@@ -6,8 +6,9 @@ probability between the populations (and within them) in both fits, and the post
 probability falls depends on the length of the chain and on the prior: an edge the data say nothing about stays near the prior's rho with
 a weight near zero, so "no coupling" shows as a lower probability and small weights, not as a probability of zero.
 
-The data are drawn here in NumPy (the truth has no coupling, so there is nothing to simulate serially): generate() and simulate() of a
-model with covariates are refused -- they would need covariates for bins that were never recorded.
+The data are drawn here in NumPy (the truth has no coupling, so there is nothing to simulate serially): generate() of a model with
+covariates is refused, and simulate() needs covariates= for the bins it simulates (examples/predictive_check_confound.py checks the
+fitted model that way).
 
     python examples/stimulus_confound.py [N_samples]
 """

@@ -22,6 +22,9 @@ HEADER_COVARIATES = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip_c
 HEADER_LATENTS = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip_latents.h")
 # the entry of the latents' temporal prior (the block-tridiagonal draw): a seventh header, tables of its own likewise
 HEADER_LATENT_DYNAMICS = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip_latent_dynamics.h")
+# the entries of free-running simulation under covariates and latents (pgl_simulate under an offset, the offset, the latents' prior paths):
+# an eighth header, tables of its own likewise
+HEADER_SIMULATE_OFFSET = os.path.join(os.path.dirname(_HERE), "include", "pyglm_hip_simulate_offset.h")
 
 
 class PglError(RuntimeError):
@@ -127,12 +130,17 @@ LATENTS_PARAMS = {f: [p for p, _ in params] for f, (_, params) in LATENTS_FUNCTI
 with open(HEADER_LATENT_DYNAMICS) as _fh:
     LATENT_DYNAMICS_CONSTANTS, _, LATENT_DYNAMICS_FUNCTIONS = parse_header(_fh.read(), header=os.path.basename(HEADER_LATENT_DYNAMICS))
 LATENT_DYNAMICS_PARAMS = {f: [p for p, _ in params] for f, (_, params) in LATENT_DYNAMICS_FUNCTIONS.items()}
+with open(HEADER_SIMULATE_OFFSET) as _fh:
+    SIMULATE_OFFSET_CONSTANTS, _, SIMULATE_OFFSET_FUNCTIONS = parse_header(_fh.read(), header=os.path.basename(HEADER_SIMULATE_OFFSET))
+globals().update(SIMULATE_OFFSET_CONSTANTS)                       # PGL_PURPOSE_SIM_LATENT, PGL_SIM_LATENT_MAX
+SIMULATE_OFFSET_PARAMS = {f: [p for p, _ in params] for f, (_, params) in SIMULATE_OFFSET_FUNCTIONS.items()}
 _lib = None
 
 
 def _params(name):
     """the parameter names of entry `name`, of whichever header declares it"""
-    for table in (PARAMS, DISPERSION_PARAMS, DIAGNOSTICS_PARAMS, COVARIATES_PARAMS, LATENTS_PARAMS, LATENT_DYNAMICS_PARAMS):
+    for table in (PARAMS, DISPERSION_PARAMS, DIAGNOSTICS_PARAMS, COVARIATES_PARAMS, LATENTS_PARAMS, LATENT_DYNAMICS_PARAMS,
+                  SIMULATE_OFFSET_PARAMS):
         if name in table:
             return table[name]
     return SBM_PARAMS[name]
@@ -151,7 +159,7 @@ def load():
     #                      two runtimes in the process: "no ROCm-capable device is detected" at the first launch)
     lib = ctypes.CDLL(LIB_PATH)
     for functions in (FUNCTIONS, DISPERSION_FUNCTIONS, DIAGNOSTICS_FUNCTIONS, SBM_FUNCTIONS, COVARIATES_FUNCTIONS, LATENTS_FUNCTIONS,
-                      LATENT_DYNAMICS_FUNCTIONS):
+                      LATENT_DYNAMICS_FUNCTIONS, SIMULATE_OFFSET_FUNCTIONS):
         for name, (restype, params) in functions.items():
             fn = getattr(lib, name)     # AttributeError if the export is missing
             fn.argtypes = [t for _, t in params]
@@ -164,13 +172,13 @@ def load():
 
 def source_hash():
     """sha256 (first 16 hex digits) over the kernel sources of the library -- pyglm_amd/csrc/*.hip, *.h and the Makefile, in name order, plus
-    the seven headers under include/: committed hardware-counter summaries (profiles/*.json) record the hash they were taken at, and bench.py quotes them
+    the eight headers under include/: committed hardware-counter summaries (profiles/*.json) record the hash they were taken at, and bench.py quotes them
     only while it still matches"""
     import hashlib
     h = hashlib.sha256()
     src = os.path.join(_HERE, "csrc")
     files = [os.path.join(src, f) for f in sorted(os.listdir(src)) if f.endswith((".hip", ".h")) or f == "Makefile"]
-    files += [HEADER, HEADER_DISPERSION, HEADER_DIAGNOSTICS, HEADER_SBM, HEADER_COVARIATES, HEADER_LATENTS, HEADER_LATENT_DYNAMICS]
+    files += [HEADER, HEADER_DISPERSION, HEADER_DIAGNOSTICS, HEADER_SBM, HEADER_COVARIATES, HEADER_LATENTS, HEADER_LATENT_DYNAMICS, HEADER_SIMULATE_OFFSET]
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")
         with open(f, "rb") as fh:

@@ -29,12 +29,16 @@
 // launch to launch: no atomics -- and all R replicates meet at the ONE grid barrier per bin: the exchange buffer is [2][R][N*B].  Within a
 // bin the replicates are independent: with the rows of Wm in registers (N*B <= GEN_KR * 64) x_{r+1} is fetched into registers while the
 // dot products of x_r run out of LDS (two LDS buffers, one workgroup barrier per replicate).
+// simulate_kernel also runs under a time-parallel offset (pgl_simulate_offset, include/pyglm_hip_simulate_offset.h: the covariates' and latents'
+// S beta of a model that has them), a template parameter that leaves the instances without an offset as they are.
 // A third kernel, conditional_kernel (pgl_conditional_simulate), is the one-workgroup form of the scheme run once per replicate on the free
 // neurons of a model whose other neurons are clamped to a recording: the same pieces, and no grid barrier at all.
 #include "pgl_common.h"
 #include "pgl_rng.h"
 #include "../../include/pyglm_hip.h"
+#include "../../include/pyglm_hip_simulate_offset.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -380,6 +384,16 @@ struct SimArgs {
     int psi_off;             // byte offset of the activation table in LDS
 };
 
+// pgl_simulate_offset: the same block with the offset behind it, so that the kernels without an offset keep the argument block they had
+struct SimOffArgs {
+    SimArgs s;
+    const double* Off; long ldo_t, ldo_r;     // [R][Tc][ldo_t], replicate stride ldo_r (0: shared by the replicates)
+};
+template <bool OFF> using SimArgsOf = typename std::conditional<OFF, SimOffArgs, SimArgs>::type;
+__device__ __forceinline__ const SimArgs& sim_args(const SimArgs& a) { return a; }
+__device__ __forceinline__ const SimArgs& sim_args(const SimOffArgs& a) { return a.s; }
+constexpr int SIM_OFF_PAIRS = SIM_PSI_MAX / GEN_THREADS;   // (replicate, neuron) pairs of a group a thread draws at most
+
 __device__ __forceinline__ void sim_cap_fail(int* status, long bin, long rep, int n) {
     int expect = 0;
     if (__hip_atomic_compare_exchange_strong(status, &expect, 2, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
@@ -434,8 +448,11 @@ __device__ double sim_draw(int kind, double par, double psi, PglPhilox& rng, boo
 // products, one replicate after the other, leave psi[r][n] in an LDS table; then the draws of ALL (replicate, neuron) pairs of the group run
 // side by side, one lane each.  The pair a thread takes first is the same in every bin: its model and its running sums stay in registers for
 // the whole launch.
-template <bool XLDS, int KR>
-__global__ __launch_bounds__(GEN_THREADS) void simulate_kernel(SimArgs s) {
+// OFF: psi = (Wm . x + bias) + Off[r][k][n], one rounded sum added last in the draw phase; a thread loads the offsets of the group's pairs it
+// will draw BEFORE the group's dot products, so that they arrive behind them.  OFF = false is the kernel without any of it.
+template <bool XLDS, int KR, bool OFF>
+__global__ __launch_bounds__(GEN_THREADS) void simulate_kernel(SimArgsOf<OFF> sa) {
+    const SimArgs& s = sim_args(sa);
     const GenArgs& g = s.g;
     const int R = s.R;
     const Wg w = wg_begin(g, R, blockIdx.x);                         // LDS x: 2 * KR * 64 (KR > 0) or N*B (XLDS); after the basis, psi: SIM_PSI_MAX
@@ -474,6 +491,16 @@ __global__ __launch_bounds__(GEN_THREADS) void simulate_kernel(SimArgs s) {
         }
         for (int rb = 0; rb < R; rb += RB) {
             const int rn = min(RB, R - rb);
+            [[maybe_unused]] double off[OFF ? SIM_OFF_PAIRS : 1];
+            if constexpr (OFF) {                                      // (rn * nown <= SIM_PSI_MAX = SIM_OFF_PAIRS * GEN_THREADS)
+#pragma unroll
+                for (int q = 0; q < SIM_OFF_PAIRS; ++q) {
+                    const int it = threadIdx.x + q * GEN_THREADS;
+                    const bool in = it < rn * nown;
+                    const int r = rb + (in ? it / nown : 0), i = in ? it % nown : 0;
+                    off[q] = in ? sa.Off[(long)r * sa.ldo_r + (long)k * sa.ldo_t + n_lo + i] : 0.0;
+                }
+            }
             for (int r = rb; r < rb + rn; ++r) {
                 const double* x = xt + (long)r * NB;
                 const double* xc = xs;                               // what the dot products read x_r from, when from LDS
@@ -510,7 +537,12 @@ __global__ __launch_bounds__(GEN_THREADS) void simulate_kernel(SimArgs s) {
                 PglPhilox rng;
                 pgl_rng_init(rng, s.seed, ((uint64_t)(s.rep0 + r) << 32) | (uint32_t)n, (uint64_t)t, PGL_PURPOSE_SIM);
                 bool cap = false;
-                const double y = sim_draw(first ? kind1 : s.kind[n], first ? par1 : s.par[n], psi_l[it], rng, cap);
+                double psi = psi_l[it];
+                if constexpr (OFF) {
+                    const int q = (it - (int)threadIdx.x) / GEN_THREADS;
+                    psi = __dadd_rn(psi, q == 0 ? off[0] : q == 1 ? off[1] : q == 2 ? off[2] : off[3]);
+                }
+                const double y = sim_draw(first ? kind1 : s.kind[n], first ? par1 : s.par[n], psi, rng, cap);
                 if (cap) { sim_cap_fail(g.status, t, s.rep0 + r, n); capped = 1; }
                 if (s.Y) s.Y[(long)r * s.ldr + (long)k * N + n] = y;
                 if (w.rl) w.rl[r * ringW + (long)row * nown + i] = y;
@@ -734,13 +766,18 @@ extern "C" size_t pgl_simulate_work_bytes(int N, int B, int R) {
     return GEN_BAR_BYTES + 2 * (size_t)R * N * B * sizeof(double);
 }
 
-extern "C" int pgl_simulate(const double* Wm, const double* bias, const double* basis, int N, int B, int L, const int* kind, const double* par,
-                            int R, long rep0, unsigned long long seed, double* ring, double* Y, long ldr, double* sum, double* sumsq, long t0,
-                            int Tc, void* work, int* status, void* hip_stream) {
+namespace {
+static_assert(SIM_OFF_PAIRS == 4, "the draw phase selects among four offsets");
+
+// pgl_simulate and pgl_simulate_offset: Off null queues the kernels without an offset
+int simulate_entry(const char* entry, const double* Wm, const double* bias, const double* basis, int N, int B, int L, const int* kind, const double* par,
+                   int R, long rep0, unsigned long long seed, double* ring, double* Y, long ldr, double* sum, double* sumsq, long t0, int Tc,
+                   void* work, int* status, const double* Off, long ldo_t, long ldo_r, void* hip_stream) {
     PGL_CHECK_ARG(Wm && bias && basis && kind && par && ring && sum && sumsq && work && status);
     PGL_CHECK_ARG(N > 0 && B > 0 && L > 0 && R > 0 && Tc > 0 && t0 >= 0 && rep0 >= 0);
     PGL_CHECK_ARG(t0 + Tc <= (1L << 31) - 1 && rep0 + R <= (1L << 31) - 1);           // the status word and the Philox counter hold them in 32 bits
     PGL_CHECK_ARG(!Y || ldr >= (long)Tc * N);
+    PGL_CHECK_ARG(!Off || (ldo_t >= N && (ldo_r == 0 || ldo_r >= (long)(Tc - 1) * ldo_t + N)));
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     SimArgs s{};
     GenPlan p;
@@ -750,9 +787,31 @@ extern "C" int pgl_simulate(const double* Wm, const double* bias, const double* 
     s.psi_off = (int)p.lds;                                          // the activation table at the end
     p.lds += SIM_PSI_MAX * sizeof(double);
     s.kind = kind; s.par = par; s.Y = Y; s.ldr = ldr; s.sum = sum; s.sumsq = sumsq; s.R = R; s.rep0 = rep0; s.seed = seed;
-    if (p.regs) return launch<simulate_kernel<true, GEN_KR>>("pgl_simulate", s, work, p.q.G, p.lds, st);
-    if (p.xlds) return launch<simulate_kernel<true, 0>>("pgl_simulate", s, work, p.q.G, p.lds, st);
-    return launch<simulate_kernel<false, 0>>("pgl_simulate", s, work, p.q.G, p.lds, st);
+    if (Off) {
+        SimOffArgs o{};
+        o.s = s; o.Off = Off; o.ldo_t = ldo_t; o.ldo_r = ldo_r;
+        if (p.regs) return launch<simulate_kernel<true, GEN_KR, true>>(entry, o, work, p.q.G, p.lds, st);
+        if (p.xlds) return launch<simulate_kernel<true, 0, true>>(entry, o, work, p.q.G, p.lds, st);
+        return launch<simulate_kernel<false, 0, true>>(entry, o, work, p.q.G, p.lds, st);
+    }
+    if (p.regs) return launch<simulate_kernel<true, GEN_KR, false>>(entry, s, work, p.q.G, p.lds, st);
+    if (p.xlds) return launch<simulate_kernel<true, 0, false>>(entry, s, work, p.q.G, p.lds, st);
+    return launch<simulate_kernel<false, 0, false>>(entry, s, work, p.q.G, p.lds, st);
+}
+}  // namespace
+
+extern "C" int pgl_simulate(const double* Wm, const double* bias, const double* basis, int N, int B, int L, const int* kind, const double* par,
+                            int R, long rep0, unsigned long long seed, double* ring, double* Y, long ldr, double* sum, double* sumsq, long t0,
+                            int Tc, void* work, int* status, void* hip_stream) {
+    return simulate_entry("pgl_simulate", Wm, bias, basis, N, B, L, kind, par, R, rep0, seed, ring, Y, ldr, sum, sumsq, t0, Tc, work, status,
+                          nullptr, 0, 0, hip_stream);
+}
+
+extern "C" int pgl_simulate_offset(const double* Wm, const double* bias, const double* basis, int N, int B, int L, const int* kind, const double* par,
+                                   int R, long rep0, unsigned long long seed, double* ring, double* Y, long ldr, double* sum, double* sumsq,
+                                   long t0, int Tc, void* work, int* status, const double* Off, long ldo_t, long ldo_r, void* hip_stream) {
+    return simulate_entry("pgl_simulate_offset", Wm, bias, basis, N, B, L, kind, par, R, rep0, seed, ring, Y, ldr, sum, sumsq, t0, Tc, work, status,
+                          Off, ldo_t, ldo_r, hip_stream);
 }
 
 extern "C" int pgl_conditional_max_free(void) { return PGL_COND_MAX_FREE; }

@@ -275,11 +275,61 @@ class NonlinearAutoregressiveModel(object):
         if not np.array_equal(eng.beta, loc):
             eng.set_covariate_weights(loc)
 
-    def _refuse_covariates(self, what):
-        if self.K:
+    def _refuse_covariates(self, what, covariates=None, latents=None, keywords=False):
+        """the first check of generate(), simulate() and predictive_check(): a model with observed covariates needs covariates=, one with
+        latents needs latents= (keywords: the caller takes the two, and the message says so); generate() takes neither"""
+        if (self.K_obs and covariates is None) or (self.Q and latents is None):
+            hint = ""
+            if keywords:
+                hint = "; or pass " + " and ".join(
+                    ["covariates=S (T, %d), one row per simulated bin" % self.K_obs] * bool(self.K_obs and covariates is None) +
+                    ["latents='prior', 'fitted' or an array (T, %d)" % self.Q] * bool(self.Q and latents is None))
             raise ValueError("%s: free-running simulation of a model with covariates (n_covariates=%d%s) is not supported -- it needs covariates "
-                             "for bins that were never recorded; conditional_simulate() / conditional_check() work"
-                             % (what, self.K_obs, ", n_latents=%d" % self.Q if self.Q else ""))
+                             "for bins that were never recorded; conditional_simulate() / conditional_check() work%s"
+                             % (what, self.K_obs, ", n_latents=%d" % self.Q if self.Q else "", hint))
+        if covariates is not None and not self.K_obs:
+            raise ValueError("%s: covariates= was given, but the model was built with n_covariates=0: there is no weight to apply them with" % what)
+        if latents is not None and not self.Q:
+            raise ValueError("%s: latents= was given, but the model was built with n_latents=0: there is no loading to apply them with" % what)
+
+    def _drive(self, what, T, R, covariates, latents, data):
+        """the checked covariates= / latents= / data= of simulate() -> simulate.Drive, or None for a model with neither term"""
+        from . import covariates as _cov
+        from . import latents as _lat
+        from . import simulate as _sim
+        if not self.K:
+            return None
+        T = int(T)
+        S = X = None
+        if self.K_obs:
+            if isinstance(covariates, str):
+                if covariates != "data":
+                    raise ValueError("%s: covariates=%r; an array (T, %d) or 'data' is required" % (what, covariates, self.K_obs))
+                S = self.covariates_list[range(len(self.data_list))[data]]
+                if T > S.shape[0]:
+                    raise ValueError("%s: covariates='data' covers the %d bins of data set %d; T = %d is more" % (what, S.shape[0], data, T))
+                S = S[:T]
+            S = _cov.check_covariates(covariates if S is None else S, T, self.K_obs, what)
+        if self.Q:
+            if isinstance(latents, str):
+                if latents not in ("prior", "fitted"):
+                    raise ValueError("%s: latents=%r; 'prior', 'fitted' or an array (T, %d) or (replicates, T, %d) is required"
+                                     % (what, latents, self.Q, self.Q))
+                X = latents
+                if latents == "fitted":
+                    X = self.engine.latents(range(len(self.data_list))[data])
+                    if T > X.shape[0]:
+                        raise ValueError("%s: latents='fitted' covers the %d bins of data set %d; T = %d is more" % (what, X.shape[0], data, T))
+                    X = X[:T][None]
+            else:
+                X = np.asarray(latents, dtype=np.float64)
+                if X.ndim == 2:
+                    X = X[None]
+                if X.ndim != 3 or X.shape[0] not in (1, int(R)):
+                    raise ValueError("%s: latents of shape %s; (%d, %d) or (replicates = %d, %d, %d) is required"
+                                     % (what, np.shape(latents), T, self.Q, R, T, self.Q))
+                X = np.stack([_lat.check_latents(x, T, self.Q, what) for x in X])
+        return _sim.Drive(self._beta, S_obs=S, latents=X, phi=self.latent_ar)
 
     def add_data(self, data, X=None, covariates=None):
         """(models.py:66-80)  covariates: S (T, K) of this data set, required with n_covariates = K > 0 and refused without"""
@@ -669,7 +719,7 @@ class NonlinearAutoregressiveModel(object):
         return X[L:], Y[L:]
 
     def simulate(self, T, replicates=1, seed=0, first_replicate=0, history=None, keep_paths=True, gpu=None, t0=None, lags=0, lagged_on_device=False,
-                 isi=0):
+                 isi=0, covariates=None, latents=None, data=0):
         """Posterior predictive simulation: `replicates` independent trajectories of T bins from the model's CURRENT state, every neuron
         drawing from its own regression's observation model (Bernoulli, Gaussian, negative binomial, binomial; mixed lists work).  Unlike
         generate() -- which stays the reference's loop, quirks included -- the activation is that of `means` and log_likelihood(),
@@ -696,9 +746,18 @@ class NonlinearAutoregressiveModel(object):
         A bin with a positive count is one event, whatever the count; a Gaussian neuron has no events and is refused by name.  The
         intervals are those between the events of the T bins of this call: continuing from a `history=` does not count the interval from
         the history's last event.  On the device pgl_isi_fold folds them after every launch.
+        A model with n_covariates = K_obs > 0 needs covariates=: an array (T, K_obs), finite, row k for the k-th simulated bin (bin t0 + k),
+        shared by all replicates ('data': the first T rows of data set `data`'s own).  A model with n_latents = Q > 0 needs latents=:
+        'prior' -- every replicate draws its own path from the model's prior, N(0, I) per bin or the stationary AR(1) process of latent_ar
+        (simulate.latent_prior_host; a forecast restarts the factors from the stationary law) --, 'fitted' -- the current sampled latents of
+        data set `data`, shared by all replicates, T <= its length --, or an array (T, Q) or (replicates, T, Q), used as given.  The
+        activation then is psi = ((a*W) . x + b) + o, o = covariates.offset_host([covariates | latents], [covariate_weights |
+        latent_loadings]).  The Simulation carries latents (with keep_paths=True) and latent_last; continuing from it with latents='prior'
+        continues the factors' paths as well.  Without the keyword its term needs, such a model raises the ValueError it always raised.
         On a sharded model every rank holds the gathered state: each rank computes the same result on its own device, with no collective."""
         from . import simulate as _sim
-        self._refuse_covariates("simulate()")
+        self._refuse_covariates("simulate()", covariates, latents, keywords=True)
+        drive = self._drive("simulate()", T, replicates, covariates, latents, data)
         A, W, b = self._adopt_state()
         kind, par = _sim.observation_kinds(self.regressions)
         if _sim.check_isi_bins(isi):
@@ -708,7 +767,7 @@ class NonlinearAutoregressiveModel(object):
         Wm = (W * A[:, :, None]).reshape(self.N, self.N * self.B)
         return _sim.simulate(Wm, b.ravel(), np.asarray(self.basis, dtype=np.float64), kind, par, T, replicates=replicates, seed=seed,
                              first_replicate=first_replicate, history=history, keep_paths=keep_paths, t0=t0, on_device=self._on_gpu(gpu, "simulate"),
-                             device=self._device, lags=lags, lagged_on_device=lagged_on_device, isi=isi)
+                             device=self._device, lags=lags, lagged_on_device=lagged_on_device, isi=isi, **(dict(drive=drive) if drive else {}))
 
     def _refuse_gaussian_intervals(self, what):
         from . import simulate as _sim
@@ -752,18 +811,26 @@ class NonlinearAutoregressiveModel(object):
         S = _sim.lagged_products_device(Y, K, device=self._device) if self._on_gpu(gpu, "cross_correlogram") else _sim.lagged_products_host(Y, K)
         return _sim.correlogram(S, Y.sum(axis=0), (Y * Y).sum(axis=0), Y.shape[0])
 
-    def predictive_check(self, replicates=8, seed=0, data=0, gpu=None, lags=0, isi=0):
+    def predictive_check(self, replicates=8, seed=0, data=0, gpu=None, lags=0, isi=0, covariates=None, latents=None):
         """a posterior predictive check of data set `data` bound to this model (simulate.PredictiveCheck): call its collect() after every
         sweep to be kept -- it simulates `replicates` fresh trajectories of the data set's length from the current state --, read
         rate_quantiles(q) / fano_quantiles(q) / pvalue("rate" | "fano") at the end.  lags = K > 0 adds the lagged cross-correlogram, the
         statistic that sees the coupling: pvalue("xcorr"), xcorr_mean, xcorr_std, each (K, N, N).  isi = D >= 2 adds the statistics of the
         single train, which see refractoriness and bursting: pvalue("isi"), isi_mean, isi_std, each (N, D), and pvalue("cv"), cvs,
-        cv_quantiles(q); a Gaussian neuron is refused by name.  Changes nothing in the chain."""
+        cv_quantiles(q); a Gaussian neuron is refused by name.  Changes nothing in the chain.
+        A model with covariates needs covariates= -- 'data', the data set's own, or an array of its shape --, one with latents needs latents=
+        -- 'prior', fresh paths from the prior for every replicate: the check of the model as a generative one; or 'fitted', the data set's
+        current sampled latents, shared by the replicates: the check given the inferred drive.  Every collect() hands them to simulate()."""
         from .simulate import PredictiveCheck, check_isi_bins
-        self._refuse_covariates("predictive_check()")
+        self._refuse_covariates("predictive_check()", covariates, latents, keywords=True)
+        if latents is not None and not (isinstance(latents, str) and latents in ("prior", "fitted")):
+            raise ValueError("predictive_check(): latents=%r; 'prior' or 'fitted' is required" % (latents,))
+        if self.K:
+            data = range(len(self.data_list))[data]
+            self._drive("predictive_check()", self.data_list[data][1].shape[0], replicates, covariates, latents, data)    # (refuses a wrong shape now, not at the first collect())
         if check_isi_bins(isi):
             self._refuse_gaussian_intervals("predictive_check(isi=%d)" % isi)
-        return PredictiveCheck(self, replicates=replicates, seed=seed, data=data, gpu=gpu, lags=lags, isi=isi)
+        return PredictiveCheck(self, replicates=replicates, seed=seed, data=data, gpu=gpu, lags=lags, isi=isi, covariates=covariates, latents=latents)
 
     def _conditional_inputs(self, free, data, start, stop):
         """what the conditional law (simulate.conditional_host) takes, read from the current state and data set `data` for the checked `free`

@@ -135,7 +135,13 @@ def generate(Wm, bias, basis, T, obs, noise_scale=0.0, device=None, verbose=Fals
 #                while u1 >= c and k < NEGBIN_CAP: f = f * p * (k + xi) / (k + 1), k += 1, c = c + f.  y = k; k = NEGBIN_CAP is an error that
 #                names bin, replicate and neuron (an exploding count model)
 #   Every fp64 operation of the walks is evaluated left to right as written.
+#   offset       a model with covariates or latent common input (covariates.py, latents.py):
+#                psi_t[r, n] = ((a*W)[n, :] . x_t[r] + b[n]) + o_r[t, n] -- the offset added last, as one rounded sum --,
+#                o_r = covariates.offset_host([S_obs | X_r], beta), beta = [covariate weights | latent loadings] (N, K): from 0.0, columns
+#                ascending, a rounded product then a rounded sum (simulate_offset_host).  X_r (T, Q): given, or the prior's path of
+#                replicate r (latent_prior_host).
 PURPOSE_SIM = 2
+PURPOSE_SIM_LATENT = _lib.PGL_PURPOSE_SIM_LATENT     # the normals of the latents' prior paths: stream = replicate, element = time bin, call = factor
 KINDS = tuple(sorted(_reg.MODELS, key=lambda name: _reg.MODELS[name].sim_kind))          # KINDS[kind[n]]: the model's name
 KIND_BERNOULLI, KIND_GAUSSIAN, KIND_NEGBIN, KIND_BINOMIAL = (_reg.MODELS[name].sim_kind for name in KINDS)
 NEGBIN_CAP = 65535
@@ -276,10 +282,15 @@ class Simulation(object):
     if the caller asked for that), and lag_redos, the folds that the int8 kernel refused and the fp64 one redid.
     With isi = D > 0: isi (R, N, D) and isi_moments (R, N, 3), int64, the inter-spike-interval histogram and (M, sum d, sum d^2) of every
     replicate (isi_host states them) over the events of the T bins of THIS call only: a call that continues a `history=` does not count the
-    interval from the history's last event to its own first one."""
+    interval from the history's last event to its own first one.
+    Of a model with latent factors: latents (R, T, Q), or (1, T, Q) where the replicates share them -- kept with keep_paths=True, else None
+    --, and latent_last (R, Q), every replicate's factors at the last bin: the carry from which `history=` this Simulation continues the
+    prior's AR(1) paths.  Both None without latents."""
 
-    def __init__(self, Y, sum, sumsq, history, t0, t1, seed, first_replicate, lagged=None, lag_redos=0, isi=None, isi_moments=None):
+    def __init__(self, Y, sum, sumsq, history, t0, t1, seed, first_replicate, lagged=None, lag_redos=0, isi=None, isi_moments=None,
+                 latents=None, latent_last=None):
         self.Y, self.sum, self.sumsq, self.history = Y, sum, sumsq, history
+        self.latents, self.latent_last = latents, latent_last
         self.t0, self.t1, self.seed, self.first_replicate = int(t0), int(t1), int(seed), int(first_replicate)
         self.lagged, self.lag_redos = lagged, int(lag_redos)
         self.isi, self.isi_moments = isi, isi_moments
@@ -582,10 +593,89 @@ def _raise_cap(t, rep, n):
                    "explodes at this state (the rate grows without bound)" % (n, rep, t, NEGBIN_CAP))
 
 
-def simulate_host(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_paths, lags=0, isi=0):
+def latent_normals_sim_host(seed, reps, t0, T, Q):
+    """z (len(reps), T, Q): the standard normals of the latents' prior paths as the device draws them -- Philox4x32-10, key = seed, counter =
+    (q | PURPOSE_SIM_LATENT << 24, t0 + k, replicate lo, replicate hi); words (0, 1) of call q make u0, words (2, 3) u1,
+    z = sqrt(-2 log u0) cos(2 pi u1) (latents.latent_normals_host on another purpose and stream)"""
+    reps = np.atleast_1d(np.asarray(reps, dtype=np.int64))
+    z = np.empty((reps.size, T, Q))
+    for i, r in enumerate(reps):
+        for q in range(Q):
+            w = philox_words(seed, PURPOSE_SIM_LATENT, q, t0, int(r), T)
+            u0, u1 = _unit(w[:, 0], w[:, 1]), _unit(w[:, 2], w[:, 3])
+            z[i, :, q] = np.sqrt(-2.0 * np.log(u0)) * np.cos(2.0 * np.pi * u1)
+    return z
+
+
+def latent_recurrence_host(z, phi, carry=None):
+    """x (R, T, Q) from the normals z (R, T, Q): x[0] = z[0] without a carry -- the stationary start --, else x_t = fl(fl(phi x_{t-1}) +
+    fl(s z_t)), s = sqrt(1 - phi^2), x_{-1} = carry (R, Q).  No fused multiply-add; phi = 0 gives z itself"""
+    z = np.asarray(z, dtype=np.float64)
+    phi = np.asarray(phi, dtype=np.float64).reshape(z.shape[2])
+    s = np.sqrt(1.0 - phi * phi)
+    x = np.empty_like(z)
+    prev = None if carry is None else np.asarray(carry, dtype=np.float64).reshape(z.shape[0], z.shape[2])
+    for k in range(z.shape[1]):
+        if prev is None:
+            cur = z[:, k].copy()
+        else:
+            a, b = phi * prev, s * z[:, k]            # two rounded products, then one rounded sum
+            cur = a + b
+        x[:, k] = cur
+        prev = cur
+    return x
+
+
+def latent_prior_host(seed, reps, t0, T, phi, carry=None):
+    """THE LAW of the latents' prior paths -> X (len(reps), T, Q): per factor q a stationary AR(1) process with coefficient phi[q] and
+    marginal variance 1 (N(0, I) per bin at phi = 0), on the normals of latent_normals_sim_host.  reps: the absolute replicate indices; t0: the
+    first bin; carry (R, Q): the factors at bin t0 - 1 of a trajectory that is continued, None: bin t0 starts it.  A path depends on (seed,
+    replicate, q, the bin the trajectory started at, phi) alone"""
+    phi = np.atleast_1d(np.asarray(phi, dtype=np.float64))
+    return latent_recurrence_host(latent_normals_sim_host(seed, reps, t0, int(T), phi.size), phi, carry)
+
+
+def simulate_offset_host(S_obs, X, beta):
+    """o (R' , T, N) of THE LAW: covariates.offset_host([S_obs | X_r], beta) per replicate of X.  S_obs (T, K_obs) or None; X (R', T, Q) or None
+    (then R' = 1); beta (N, K_obs + Q)"""
+    from .covariates import offset_host
+    parts = []
+    for r in range(1 if X is None else np.shape(X)[0]):
+        cols = [v for v in (S_obs, None if X is None else np.asarray(X)[r]) if v is not None]
+        parts.append(offset_host(np.concatenate(cols, axis=1), beta))
+    return np.stack(parts)
+
+
+class Drive(object):
+    """what a model with covariates or latents adds to the activation of a simulation of T bins: beta (N, K) = [covariate weights | latent
+    loadings]; S_obs (T, K_obs) or None, row k for the k-th simulated bin; and the latents -- "prior" (with phi (Q,)) or an array (1, T, Q),
+    shared by the replicates, or (R, T, Q) -- or None where Q = 0.  What model.simulate() hands to simulate()"""
+
+    def __init__(self, beta, S_obs=None, latents=None, phi=None):
+        self.beta = np.ascontiguousarray(beta, dtype=np.float64)
+        self.S_obs = None if S_obs is None else np.ascontiguousarray(S_obs, dtype=np.float64)
+        self.K_obs = 0 if self.S_obs is None else self.S_obs.shape[1]
+        self.Q = self.beta.shape[1] - self.K_obs
+        self.prior = isinstance(latents, str) and latents == "prior"
+        self.X = None if self.prior or latents is None else np.ascontiguousarray(latents, dtype=np.float64)
+        self.phi = np.zeros(self.Q) if phi is None else np.ascontiguousarray(phi, dtype=np.float64)
+        if (self.Q > 0) != (self.prior or self.X is not None) or (self.X is not None and (self.X.ndim != 3 or self.X.shape[2] != self.Q)):
+            raise ValueError("Drive: beta has %d columns for %d observed covariates, and the latents do not have the other %d" %
+                             (self.beta.shape[1], self.K_obs, self.Q))
+
+    def host(self, seed, R, rep0, t0, T, carry):
+        """-> (offset (R or 1, T, N), X (R or 1, T, Q) or None, latent_last (R, Q) or None) by the host law"""
+        X = latent_prior_host(seed, rep0 + np.arange(R), t0, T, self.phi, carry) if self.prior else self.X
+        return simulate_offset_host(self.S_obs, X, self.beta), X, self.last(X, R)
+
+    def last(self, X, R):
+        return None if X is None else np.ascontiguousarray(np.broadcast_to(X[:, -1], (R, self.Q)))
+
+
+def simulate_host(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_paths, lags=0, isi=0, offset=None):
     """THE LAW in NumPy, vectorised over (R, N) per bin -> Simulation.  lags = K > 0: the lagged products of the T bins as well, folded block by
     block from the rolling buffer, which then keeps max(L, K - 1) rows in front.  isi = D > 0: the interval statistics, folded from the same
-    blocks with the `since` carry"""
+    blocks with the `since` carry.  offset (R or 1, T, N): added to the activation last, as one rounded sum; None: no such term"""
     Wm = np.ascontiguousarray(Wm, dtype=np.float64)
     N = Wm.shape[0]
     L, B = basis.shape
@@ -612,6 +702,8 @@ def simulate_host(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_p
             pos = H
         x = np.einsum("rlm,lb->rmb", buf[:, pos - L:pos][:, ::-1], basis)
         psi = x.reshape(R, N * B).dot(WmT) + bias
+        if offset is not None:
+            psi = psi + offset[:, t - t0]
         u1, u2 = sim_uniforms(seed, t, neurons, reps)
         y, capped = host_draw(kind, par, psi, u1, u2)
         if capped is not None:
@@ -628,7 +720,65 @@ def simulate_host(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_p
                       isi=ih, isi_moments=im)
 
 
-def simulate_device(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_paths, device=None, lags=0, lagged_on_device=False, isi=0):
+class _DriveDevice(object):
+    """a Drive on the device: S_obs and the k-major beta uploaded once; per chunk the prior's paths (pgl_latent_prior_paths, where the latents
+    are the prior's), the offset (pgl_simulate_offset_build) and the arguments of pgl_simulate_offset -- all on the one stream"""
+
+    def __init__(self, drive, dev, st, N, R, T, Tcap, seed, rep0, t0, carry, keep_paths):
+        import torch
+        self.d, self.st, self.N, self.R, self.T, self.seed, self.rep0, self.t0 = drive, st, N, R, T, seed, rep0, t0
+        Q = drive.Q
+        self.Rx = R if Q and (drive.prior or drive.X.shape[0] > 1) else 1      # replicates of the offset: 1 where they share it
+        keep = keep_paths and drive.prior
+        self.Tx = T if keep or not drive.prior else Tcap                        # rows of a replicate in the latents' buffer
+        need = 8 * self.Rx * Tcap * N + (8 * self.Rx * self.Tx * Q if Q else 0)
+        free = torch.cuda.mem_get_info(dev)[0]
+        if need > free:
+            raise PglError("simulate(covariates / latents): the offset of a chunk (%d replicates x %d bins x %d neurons) and the latents need "
+                           "%d bytes of device memory, %d are free: simulate fewer replicates per call" % (self.Rx, Tcap, N, need, free))
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.S = torch.from_numpy(drive.S_obs).to(dev) if drive.K_obs else None
+        self.beta = torch.from_numpy(np.ascontiguousarray(drive.beta.T)).to(dev)        # [K][N]
+        self.Off = torch.empty((self.Rx, Tcap, N), **f64)
+        self.ldo_r = Tcap * N if self.Rx > 1 else 0
+        self.X = self.carry = None
+        if drive.prior:
+            self.X = torch.empty((R, self.Tx, Q), **f64)
+            self.has_carry = carry is not None
+            self.carry = torch.from_numpy(np.ascontiguousarray(carry, dtype=np.float64).reshape(R, Q)).to(dev) if self.has_carry else torch.zeros((R, Q), **f64)
+            self.phi = (ctypes.c_double * Q)(*drive.phi)
+            self.s = (ctypes.c_double * Q)(*np.sqrt(1.0 - drive.phi * drive.phi))
+        elif Q:
+            self.X = torch.from_numpy(drive.X).to(dev)
+
+    def chunk(self, k0, n):
+        """queue what the launch of bins k0 .. k0 + n - 1 of the call needs -> the keywords Off, ldo_t, ldo_r of pgl_simulate_offset"""
+        d, Q = self.d, self.d.Q
+        X = None
+        if d.prior:
+            X = self.X[0, k0:] if self.Tx == self.T else self.X
+            call("pgl_latent_prior_paths", X=ptr(X), ldx_r=self.Tx * Q, R=self.R, rep0=self.rep0, t0=self.t0 + k0, Tc=n, Q=Q,
+                 phi=ctypes.cast(self.phi, ctypes.c_void_p), s=ctypes.cast(self.s, ctypes.c_void_p), carry=ptr(self.carry),
+                 has_carry=1 if self.has_carry or k0 > 0 else 0, z_override=None, seed=self.seed & (2 ** 64 - 1), hip_stream=self.st)
+        elif Q:
+            X = self.X[0, k0:]
+        call("pgl_simulate_offset_build", S=ptr(self.S[k0:]) if d.K_obs else None, lds=d.K_obs, X=ptr(X), ldx_r=self.Tx * Q if self.Rx > 1 else 0,
+             Beta=ptr(self.beta), ldn=self.N, Off=ptr(self.Off), ldo_t=self.N, ldo_r=self.ldo_r, Tc=n, N=self.N, K_obs=d.K_obs, Q=Q, R=self.Rx,
+             hip_stream=self.st)
+        return dict(Off=ptr(self.Off), ldo_t=self.N, ldo_r=self.ldo_r)
+
+    def finish(self, keep_paths):
+        """-> (latents or None, latent_last or None) of the Simulation"""
+        d = self.d
+        if not d.Q:
+            return None, None
+        if d.prior:
+            return (self.X.cpu().numpy() if keep_paths else None), self.carry.cpu().numpy()
+        return (d.X if keep_paths else None), d.last(d.X, self.R)
+
+
+def simulate_device(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_paths, device=None, lags=0, lagged_on_device=False, isi=0,
+                    drive=None, carry=None):
     """THE LAW through pgl_simulate, a chunk of bins per launch -> Simulation.  lags = K > 0: every launch writes its bins behind the K - 1 bins
     before them -- into the paths if they are kept, else into a buffer of K - 1 + chunk rows per replicate -- and pgl_lagged_products folds
     them into the running sums (_LagFold); the sums come back as a device tensor if lagged_on_device.  isi = D > 0: pgl_isi_fold folds the rows
@@ -671,14 +821,17 @@ def simulate_device(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep
         work = torch.zeros(_lib.load().pgl_simulate_work_bytes(N, B, R), dtype=torch.uint8, device=dev)
         status = torch.zeros(4, dtype=torch.int32, device=dev)
         status_h = torch.zeros(4, dtype=torch.int32).pin_memory()
+        ddev = _DriveDevice(drive, dev, st, N, R, T, min(Tc, T), seed, rep0, t0, carry, keep_paths) if drive is not None else None
+        entry = "pgl_simulate_offset" if ddev else "pgl_simulate"
         for k0 in range(0, T, Tc):
             n = min(Tc, T - k0)
             out, ldr = ((Y_d[0, k0:], T * N) if keep_paths else (buf[0, K - 1:], Tb * N) if K else (ibuf, min(Tc, T) * N) if D
                         else (None, T * N))
-            call("pgl_simulate", Wm=ptr(Wm_d), bias=ptr(bias_d), basis=ptr(basis_d), N=N, B=B, L=L, kind=ptr(kind_d), par=ptr(par_d), R=R, rep0=rep0,
+            okw = ddev.chunk(k0, n) if ddev else {}
+            call(entry, Wm=ptr(Wm_d), bias=ptr(bias_d), basis=ptr(basis_d), N=N, B=B, L=L, kind=ptr(kind_d), par=ptr(par_d), R=R, rep0=rep0,
                  seed=seed & (2 ** 64 - 1), ring=ptr(ring), Y=ptr(out), ldr=ldr, sum=ptr(sum_d), sumsq=ptr(sq_d), t0=t0 + k0, Tc=n, work=ptr(work),
-                 status=ptr(status), hip_stream=st)
-            _finish_launch("pgl_simulate", dev, status, status_h, t0 + k0, t0 + k0 + n - 1)
+                 status=ptr(status), hip_stream=st, **okw)
+            _finish_launch(entry, dev, status, status_h, t0 + k0, t0 + k0 + n - 1)
             if D:
                 ifold.fold(out, N, ldr, n)
             if K:
@@ -690,22 +843,35 @@ def simulate_device(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep
         if K and not lagged_on_device:
             lagged = lagged.cpu().numpy()
         ih, im = ifold.finish() if D else (None, None)
+        X, last = ddev.finish(keep_paths) if ddev else (None, None)
         return Simulation(Y_d.cpu().numpy() if keep_paths else None, sum_d.cpu().numpy(), sq_d.cpu().numpy(), ring.cpu().numpy()[:, rows],
-                          t0, t0 + T, seed, rep0, lagged=lagged, lag_redos=fold.redos if K else 0, isi=ih, isi_moments=im)
+                          t0, t0 + T, seed, rep0, lagged=lagged, lag_redos=fold.redos if K else 0, isi=ih, isi_moments=im, latents=X,
+                          latent_last=last)
 
 
 def simulate(Wm, bias, basis, kind, par, T, replicates=1, seed=0, first_replicate=0, history=None, keep_paths=True, t0=None, on_device=False,
-             device=None, lags=0, lagged_on_device=False, isi=0):
+             device=None, lags=0, lagged_on_device=False, isi=0, drive=None):
     """R = `replicates` trajectories of T bins of the model (Wm = a*W as (N, N*B), bias, basis (L, B), per-neuron kind / par) -> Simulation;
     on the device (pgl_simulate) or in NumPy.  What model.simulate() calls once it has read the model.  lags = K > 0 (K - 1 < T): the
     Simulation carries the lagged products of its T bins (lagged_products_host) as well; lagged_on_device leaves them on the device.
     isi = D >= 2: it carries the interval histogram and moments of its T bins (isi_host) -- of the events of these bins alone, also when the
-    call continues a history."""
+    call continues a history.
+    drive: a Drive -- the covariates and latents of THE LAW's offset; where its latents are the prior's and `history` is a Simulation, their
+    paths continue from its latent_last."""
     N = np.shape(Wm)[0]
     L = basis.shape[0]
     T, R, rep0, seed = int(T), int(replicates), int(first_replicate), int(seed)
     if T < 0 or R < 1 or rep0 < 0 or not 0 <= seed < 2 ** 64:
         raise ValueError("simulate(): T >= 0, replicates >= 1, first_replicate >= 0 and 0 <= seed < 2^64 are required")
+    carry = history.latent_last if isinstance(history, Simulation) and drive is not None and drive.prior else None
+    if carry is not None and np.shape(carry) != (R, drive.Q):
+        raise ValueError("simulate(): the Simulation to continue carries latents of shape %r; (replicates = %d, n_latents = %d) is required"
+                         % (np.shape(carry), R, drive.Q))
+    if drive is not None:
+        for name, v, want in (("covariates", drive.S_obs, (T, drive.K_obs)), ("latents", drive.X, (T, drive.Q))):
+            if v is not None and (v.shape[-2:] != want or (v.ndim == 3 and v.shape[0] not in (1, R))):
+                raise ValueError("simulate(): %s of shape %r; (T = %d, %d)%s is required" %
+                                 (name, v.shape, want[0], want[1], " or (replicates = %d, T, %d)" % (R, want[1]) if v.ndim == 3 else ""))
     hist, t0 = _initial_history(history, R, L, N, t0)
     if t0 + T >= 2 ** 31 or rep0 + R >= 2 ** 31:
         raise ValueError("simulate(): time bins and replicate indices must stay below 2^31")
@@ -714,14 +880,24 @@ def simulate(Wm, bias, basis, kind, par, T, replicates=1, seed=0, first_replicat
     D = check_isi_bins(isi)
     if T == 0:
         return Simulation(np.zeros((R, 0, N)) if keep_paths else None, np.zeros((R, N)), np.zeros((R, N)), hist, t0, t0, seed, rep0,
-                          isi=np.zeros((R, N, D), dtype=np.int64) if D else None, isi_moments=np.zeros((R, N, 3), dtype=np.int64) if D else None)
+                          isi=np.zeros((R, N, D), dtype=np.int64) if D else None, isi_moments=np.zeros((R, N, 3), dtype=np.int64) if D else None,
+                          latent_last=carry)
     run = simulate_device if on_device else simulate_host
     kw = dict(device=device) if on_device else {}
+    host_latents = None
+    if drive is not None and on_device:
+        kw.update(drive=drive, carry=carry)
+    elif drive is not None:
+        kw["offset"], X, last = drive.host(seed, R, rep0, t0, T, carry)
+        host_latents = (X if keep_paths else None), last
     if K:
         kw.update(dict(lags=K, lagged_on_device=lagged_on_device) if on_device else dict(lags=K))
     if D:
         kw["isi"] = D
-    return run(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_paths, **kw)
+    sim = run(Wm, bias, basis, kind, par, T, R, seed, rep0, hist, t0, keep_paths, **kw)
+    if host_latents is not None:
+        sim.latents, sim.latent_last = host_latents
+    return sim
 
 
 class PredictiveCheck(object):
@@ -749,8 +925,10 @@ class PredictiveCheck(object):
     and streams the density per cell by the rule of the correlogram, on the host ((N, D) is small).  pvalue("isi"), pvalue("cv"), isi_mean,
     isi_std, cvs and cv_quantiles(q) read them."""
 
-    def __init__(self, model, replicates=8, seed=0, data=0, gpu=None, lags=0, isi=0):
+    def __init__(self, model, replicates=8, seed=0, data=0, gpu=None, lags=0, isi=0, covariates=None, latents=None):
         self.model, self.R, self.seed, self.gpu = model, int(replicates), int(seed), gpu
+        # a model with covariates or latents (model.predictive_check checks them): what every collect() hands to model.simulate()
+        self._drive_kw = {} if covariates is None and latents is None else dict(covariates=covariates, latents=latents, data=data)
         self.D = check_isi_bins(isi)
         Y = np.asarray(model.data_list[data][1], dtype=np.float64)
         self.T = Y.shape[0]
@@ -768,7 +946,7 @@ class PredictiveCheck(object):
 
     def collect(self):
         sim = self.model.simulate(self.T, replicates=self.R, seed=self.seed, first_replicate=self.calls * self.R, keep_paths=False, gpu=self.gpu,
-                                  lags=self.K, lagged_on_device=True, isi=self.D)
+                                  lags=self.K, lagged_on_device=True, isi=self.D, **self._drive_kw)
         self.calls += 1
         self._rate.append(sim.rate())
         self._fano.append(sim.fano())
