@@ -286,6 +286,7 @@ int pgl_flip_apply_window(const pgl_flip_t* s, int window, void* st) {
 }
 int pgl_flip_decide(const pgl_flip_t* s, int window, void* st) {
     PGL_CHECK_ARG(s && s->M && s->perm && s->u && s->rho && s->c0 && s->a && s->d_idx && s->d_sign && s->d_cnt && s->status && s->Lws);
+    PGL_CHECK_ARG(s->G && s->batch_k && s->nb > 0 && s->ldj >= (long)s->N * s->B + 2);   // (the kernel writes G and batch_k unconditionally)
     PGL_CHECK_ARG(s->B >= 1 && s->B <= 32 && window >= 0);
     return pgl_k_flip_decide(*s, window, ST(st));
 }

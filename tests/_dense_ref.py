@@ -1,7 +1,7 @@
-"""Plain NumPy references, in np.longdouble, of the two pieces of dense linear algebra behind a sweep: the weight draw (an upper Cholesky and
-two triangular solves, pyglm/regression.py:323-340) and the sweep tableau of the collapsed flips (pgl_flips.hip, header).  No GPU, no library
-call: tests/test_dense_ref_host.py checks these functions against their own defining identities, tests/test_gpu_chol.py and
-tests/test_gpu_tableau.py hold the kernels to them.
+"""Plain NumPy references, in np.longdouble, of the pieces of dense linear algebra behind a sweep: the weight draw (an upper Cholesky and
+two triangular solves, pyglm/regression.py:323-340), the sweep tableau of the collapsed flips (pgl_flips.hip, header) and the serial loop of
+proposals on it (pyglm/regression.py:282-320).  No GPU, no library call: tests/test_dense_ref_host.py checks these functions against their own
+defining identities, tests/test_gpu_chol.py, tests/test_gpu_tableau.py and tests/test_gpu_flip_windows.py hold the kernels to them.
 
 Every bound the GPU tests use is the forward-error bound of the operation, computed from the reference's own matrix:
     8 * n * 2^-53 * kappa_2(pivot / active block),     kappa_2 from np.linalg.cond of the fp64 copy
@@ -166,6 +166,54 @@ def tableau(J, h):
     A[:n, :n] = ld(J)
     A[:n, n] = A[n, :n] = ld(h)
     return A
+
+
+# ------------------------------------------------------------------------------------------------------------ the collapsed proposals
+def block_dml(M, blk, on):
+    """change in log marginal likelihood for switching the block with rows blk ON, read off the tableau M, without the prior term c0
+    (pgl_flips.hip, header): Q = M[blk, blk] (minus it when the block is on), v = M[blk, D + 1];  (on ? +1/2 : -1/2) log|Q| + 1/2 v'Q^-1 v"""
+    Q = M[np.ix_(blk, blk)]
+    U = chol_upper(-Q if on else Q)
+    logdet = 2 * np.sum(np.log(np.diag(U)))
+    w = solve_upper_t(U, M[blk, M.shape[0] - 1])
+    return (logdet if on else -logdet) / 2 + (w @ w) / 2
+
+
+def flip_proposals(M, a, perm, u, rho, c0, B, R=None):
+    """The collapsed proposals of pyglm/regression.py:282-320 run serially on the full tableau M (symmetric, (N B + 2)-square, rows in J's
+    order, swept on {bias} U {blocks with a on}): step k proposes block m = perm[k] with the uniform u[k];
+        d = block_dml + c0[m] + log rho[m] - log(1 - rho[m]);   v = [u[k] (e0 + e1) > e0],  e0 = exp(-max(d, 0)),  e1 = exp(d - max(d, 0))
+    -- for rho exactly 0 or 1 the log-odds are NaN and v = 0 (the reference's 0 log 0 reaching sample_discrete_from_log) -- and a decision
+    that differs from a[m] sweeps the block's rows (forward when switched on).  u, rho, c0 are read as they are given (fp64 values).
+    Returns a dict: logodds, decision, threshold = 1 / (1 + exp(d)) per step (the decision is u > threshold), flips = [(k, m, +1 | -1)],
+    M and a at the end, and snaps = [(M, a) after every R steps and after the last] when R is given."""
+    M, a = ld(M).copy(), np.asarray(a).astype(bool).copy()
+    N = len(perm)
+    lo, thr, dec, flips, snaps = np.full(N, np.nan, dtype=LD), np.full(N, np.nan, dtype=LD), np.zeros(N, dtype=int), [], []
+    for k in range(N):
+        m = int(perm[k])
+        blk = np.arange(m * B, (m + 1) * B)
+        if 0 < rho[m] < 1:
+            d = block_dml(M, blk, a[m]) + LD(c0[m]) + np.log(LD(rho[m])) - np.log(1 - LD(rho[m]))
+            mx = max(d, LD(0))
+            e0, e1 = np.exp(-mx), np.exp(d - mx)
+            lo[k], thr[k], dec[k] = d, 1 / (1 + np.exp(d)), int(LD(u[k]) * (e0 + e1) > e0)
+        if dec[k] != int(a[m]):
+            s = 1 if dec[k] else -1
+            M = sweep(M, blk, s * np.ones(B))
+            a[m] = bool(dec[k])
+            flips.append((k, m, s))
+        if R and ((k + 1) % R == 0 or k == N - 1):
+            snaps.append((M.copy(), a.copy()))
+    return dict(logodds=lo, decision=dec, threshold=thr, flips=flips, M=M, a=a, snaps=snaps)
+
+
+def position_order(M, perm, B):
+    """the tableau in visit order: block perm[k] at position k, the bias and potential rows last (what pgl_flip_visit_order builds)"""
+    perm = np.asarray(perm, dtype=int)
+    D = len(perm) * B
+    rows = np.concatenate([(perm[:, None] * B + np.arange(B)[None, :]).ravel(), [D, D + 1]])
+    return M[np.ix_(rows, rows)]
 
 
 # ------------------------------------------------------------------------------------------------------------ test matrices

@@ -127,6 +127,100 @@ def test_scaling_the_tableau_by_a_power_of_two_scales_the_swept_tableau_exactly(
     assert np.array_equal(R.scale_swept(A, [], 4.0), A * 4)
 
 
+# ---------------------------------------------------------------------------------------------------------------- the collapsed proposals
+def _swept_on_active(J, h, a, B):
+    D = len(a) * B
+    S = np.array([D] + [m * B + b for m in np.nonzero(a)[0] for b in range(B)])
+    return R.sweep(R.tableau(J, h), S, np.ones(len(S)))
+
+
+def _dense_marginal(J, h, c0, a, B):
+    """-1/2 log|J_SS| + 1/2 h_S' J_SS^-1 h_S + sum of c0 over the active blocks, S = {bias} U {active blocks}, by a Cholesky of J_SS"""
+    D = len(a) * B
+    S = np.array([m * B + b for m in np.nonzero(a)[0] for b in range(B)] + [D], dtype=int)
+    U = R.chol_upper(J[np.ix_(S, S)])
+    w = R.solve_upper_t(U, h[S])
+    return -np.sum(np.log(np.diag(U))) + (w @ w) / 2 + np.sum(R.ld(c0)[np.asarray(a, dtype=bool)])
+
+
+def test_flip_logodds_telescope_to_the_dense_marginal_likelihood():
+    """N = 6, B = 3, rho = 1/2 (no prior odds): the log-odds of the steps that flip, signed by the direction, add up to the difference of the
+    marginal likelihoods of the final and the initial set -- each computed from J itself, without a tableau"""
+    N, B = 6, 3
+    seen = 0
+    for seed in (1, 2, 3):
+        rng = np.random.default_rng(seed)
+        J, h = R.wellcond_system(N * B + 1, rng)
+        a0 = rng.random(N) < 0.5
+        c0 = rng.standard_normal(N)
+        out = R.flip_proposals(_swept_on_active(J, h, a0, B), a0, rng.permutation(N), rng.random(N), np.full(N, 0.5), c0, B)
+        total = sum(s * out["logodds"][k] for k, _, s in out["flips"])
+        want = _dense_marginal(J, h, c0, out["a"], B) - _dense_marginal(J, h, c0, a0, B)
+        # (longdouble: eps 1.1e-19; the terms are of order 1 to 10, a few dozen operations each)
+        assert abs(total - want) < 1e-16 * max(1.0, abs(float(want))), (seed, float(total), float(want))
+        # the final tableau is the sweep of A on the final set
+        assert _rel(out["M"], _swept_on_active(J, h, out["a"], B)) < 1e-15
+        seen += len(out["flips"])
+    assert seen >= 4
+
+
+def test_flip_proposals_agree_with_the_fp64_oracle():
+    """one small regression problem: the oracle takes two dense Choleskys of the active sub-system per proposal (fp64 LAPACK), the reference
+    here reads a B x B block of the swept tableau -- two formulations of the same log-odds, held to the suite's own log-odds tolerance
+    (tests/test_gpu_parity.py: _check_logodds).  One rho is exactly 0 and one exactly 1: NaN log-odds and the decision 0 on both sides."""
+    from oracle import pyglm_oracle as orc
+    N, B, T = 9, 3, 300
+    rng = np.random.default_rng(21)
+    X = np.abs(rng.standard_normal((T, N, B))) * 0.4
+    y = (rng.random(T) < 0.3).astype(float)
+    om = rng.gamma(2.0, 0.12, T)
+    rho = np.full(N, 0.35)
+    perm = rng.permutation(N)
+    a0 = rng.random(N) < 0.5
+    on, off = perm[2:][a0[perm[2:]]][0], perm[2:][~a0[perm[2:]]][0]
+    rho[on], rho[off] = 1.0, 0.0
+    r = orc.Regression(N, B, rho=rho, S_w=2.0, mu_w=0.3, mu_b=-0.5, S_b=1.0)
+    r.a, r.W, r.b = a0.copy(), np.zeros((N, B)), np.zeros(1)
+    u, trace = rng.random(N), []
+    J_post, h_post = r.resample([(X, y)], [om], perm, u, rng.standard_normal(N * B + 1), trace=trace)
+    J_w, h_w, _, _ = r.natural_params()
+    c0 = np.array([0.5 * np.linalg.slogdet(J_w[m])[1] - 0.5 * r.mu_w[m] @ J_w[m] @ r.mu_w[m] for m in range(N)])
+    out = R.flip_proposals(_swept_on_active(J_post, h_post, a0, B), a0, perm, u, rho, c0, B)
+    want = np.array([t[1] for t in trace])
+    assert [t[0] for t in trace] == perm.tolist() and np.array_equal(out["decision"], [t[2] for t in trace])
+    assert np.array_equal(np.isnan(want), np.isnan(out["logodds"].astype(float))) and np.isnan(want).sum() == 2
+    ok = ~np.isnan(want)
+    np.testing.assert_allclose(out["logodds"].astype(float)[ok], want[ok], rtol=1e-10, atol=1e-9)
+    assert np.array_equal(out["a"], r.a) and len(out["flips"]) >= 2 and out["decision"][perm.tolist().index(on)] == 0
+
+
+def test_flip_proposals_do_not_depend_on_the_window_length():
+    N, B = 7, 2
+    rng = np.random.default_rng(8)
+    J, h = R.wellcond_system(N * B + 1, rng)
+    a0 = rng.random(N) < 0.5
+    args = (_swept_on_active(J, h, a0, B), a0, rng.permutation(N), rng.random(N), rng.uniform(0.2, 0.8, N), rng.standard_normal(N), B)
+    base = R.flip_proposals(*args)
+    assert base["snaps"] == [] and len(base["flips"]) >= 2
+    runs = {r: R.flip_proposals(*args, R=r) for r in (2, 3, 7, 10)}
+    for r, out in runs.items():
+        for key in ("logodds", "decision", "threshold", "M", "a"):
+            assert np.array_equal(out[key], base[key], equal_nan=True), (r, key)
+        assert out["flips"] == base["flips"] and len(out["snaps"]) == -(-N // r)
+        assert np.array_equal(out["snaps"][-1][0], base["M"]) and np.array_equal(out["snaps"][-1][1], base["a"])
+    # the boundary after six steps is the third of R = 2 and the second of R = 3
+    assert np.array_equal(runs[2]["snaps"][2][0], runs[3]["snaps"][1][0]) and np.array_equal(runs[2]["snaps"][2][1], runs[3]["snaps"][1][1])
+    assert np.array_equal(base["decision"], (R.ld(args[3]) > base["threshold"]).astype(int))      # the threshold is the decision
+
+
+def test_position_order_puts_block_perm_k_at_position_k():
+    B, perm = 2, np.array([2, 0, 1])
+    M = np.arange(64.0).reshape(8, 8)
+    P = R.position_order(M, perm, B)
+    rows = [4, 5, 0, 1, 2, 3, 6, 7]
+    assert np.array_equal(P, M[np.ix_(rows, rows)])
+
+
 def test_inv_spd_and_matrix_right_hand_sides():
     J, _ = R.spectrum_system(70, 1e6, np.random.default_rng(4))
     assert _rel(R.ld(J) @ R.inv_spd(J), np.eye(70)) < 1e-18 * 1e6

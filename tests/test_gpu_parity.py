@@ -565,8 +565,8 @@ def test_sharded_equals_unsharded(torch_dev, gram, T):
                                       (50, 5, 400, 1.0)])
 def test_edge_shapes_vs_oracle(torch_dev, N, B, T, rho):
     """edges: a single neuron, T below one 16-row K tile / not a multiple of 16, the reference's default B = 10, the
-    largest supported B (= 32: 10 blocks per proposal window), rho = 0 everywhere (deterministic: all connections off), and two all-on
-    cases whose active dimension (74, 251) ends a few rows into a 64-row Cholesky sub-panel with the padded leading dimension (80, 256)
+    largest supported B (= 32: 5 blocks per proposal window, what the LDS scratch of the proposal kernel leaves room for), rho = 0
+    everywhere (deterministic: all connections off), and two all-on cases whose active dimension (74, 251) ends a few rows into a 64-row Cholesky sub-panel with the padded leading dimension (80, 256)
     shorter than the sub-panel: a strip update must not write past a neuron's own rows"""
     from pyglm_amd.engine import make_draws
     rng = np.random.default_rng(100 + N + B)
@@ -760,12 +760,13 @@ def test_prefix_run_equals_the_same_neurons_of_a_full_sweep(torch_dev, gram):
         eng.sweep(a, W, b, *hyp, perm, u, z, seed=9, sweep=2, nrun=3, nfirst=5)          # (odd start: refused by pgl_sweep)
 
 
-def test_two_windows_per_pass_give_the_bits_of_one_pass_per_window(torch_dev):
+@pytest.mark.parametrize("N,B,T", [(200, 5, 1500), (100, 7, 900), (70, 11, 900)])
+def test_two_windows_per_pass_give_the_bits_of_one_pass_per_window(torch_dev, N, B, T):
     """pgl_k_flip_apply_pair stacks the panels of two proposal windows and passes over the trailing tableau once: every entry must see the same
-    multiply-adds in the same order as with a pass per window (pgl_sweep_t.flip_single_pass = 1).  N = 200: four windows (64, 64, 64, 8
-    blocks), one batch ragged."""
+    multiply-adds in the same order as with a pass per window (pgl_sweep_t.flip_single_pass = 1).  N = 200, B = 5: four windows (64, 64, 64, 8
+    blocks), every boundary even, one batch ragged.  N = 100, B = 7 (windows of 45, 45, 10) and N = 70, B = 11 (29, 29, 12; the run-time-B
+    proposal kernel): R B is odd, so the trailing update after the first window starts one row inside the dead window."""
     from pyglm_amd.engine import GibbsEngine, make_draws, prior_terms
-    N, B, T = 200, 5, 1500
     D = N * B
     rng = np.random.default_rng(4)
     Y = (rng.random((T, N)) < 0.1).astype(float)
