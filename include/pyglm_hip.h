@@ -87,11 +87,19 @@ int pgl_scaled_gram(const double* G0, long ldg, const double* inv_eta, double* J
 
 /* J[z][i][j] (+)= sum_t W[t][z] * X[t][i] * X[t][j], i >= j tiles only (lower triangle valid), z in [0, nz), i,j in [0, D).
  * Replaces XO = X*omega[:,None]; J += XO.T.dot(X) at pyglm/regression.py:251-252 without the T x D temporary.
- * X: Tp x ldx (Tp % 16 == 0, rows >= T zero); W: Tp x ldw weights (rows >= T zero). */
+ * X: Tp x ldx (Tp % 16 == 0, rows >= T zero); W: Tp x ldw weights (rows >= T zero).
+ * x_cols: the READABLE columns of a row of X (x_cols <= ldx), rounded down to even: the kernels load pairs of columns, a pair that starts at or
+ * past x_cols & ~1 is never loaded (a tile that reaches beyond re-reads the pair at (x_cols & ~1) - 2 into lanes whose results are not
+ * stored), and columns of W from nz on are never loaded either.  (x_cols & ~1) >= D is required and checked: with x_cols = D and D odd the
+ * last row and column of J would be computed from column D - 2. */
 int pgl_weighted_gram(const double* X, long ldx, int x_cols, const double* W, long ldw, int Tp, int D, int nz, double* J, long ldj, long strideJ,
                       int accumulate, void* hip_stream);
 /* C[r][c] (+)= sum_t A[t][r] * X[t][c]  (plain k-major contraction; the border sums X'omega, sum omega, X'kappa, sum kappa of
- * pyglm/regression.py:253-260 with A = [Omega | Kappa] and X carrying the ones column). */
+ * pyglm/regression.py:253-260 with A = [Omega | Kappa] and X carrying the ones column).  A: K x lda, B: K x ldb, K % 16 == 0, lda and ldb
+ * even, A and B 16-byte aligned.
+ * a_cols, b_cols: the READABLE columns of a row of A and of B, each rounded down to even, exactly as x_cols of pgl_weighted_gram: columns
+ * from a_cols & ~1 (b_cols & ~1) on are never loaded.  (a_cols & ~1) >= M and (b_cols & ~1) >= N are required and checked: a_cols = M with M
+ * odd would compute the last row of C from column M - 2 of A. */
 int pgl_contract_tn(const double* A, long lda, int a_cols, const double* B, long ldb, int b_cols, double* C, long ldc, int M, int N, int K,
                     double alpha, double beta, void* hip_stream);
 /* The same contraction for a batch of independent operands, C[b] = beta C[b] + alpha A[b]' B[b], b < nbatch (operands strideX doubles apart):
@@ -99,7 +107,9 @@ int pgl_contract_tn(const double* A, long lda, int a_cols, const double* B, long
  * refactors the active block per proposal) and of the blocked Cholesky of the weight draw (pyglm/regression.py:323-340).
  * tri: 0 all tiles, 1 the tiles of the lower triangle (M == N), 2 of the upper.  batch_k: optional per-batch K (multiples of 16, 0 = skip).
  * kernel: 0 generic tiles, 1 the update pipeline (256 x 128 tiles, DMA-staged, persistent) where it is the faster one, 2 always the
- * pipeline -- every choice gives the same bits (tests/test_gpu_update.py). */
+ * pipeline -- every choice gives the same bits (tests/test_gpu_update.py).
+ * a_cols, b_cols: as for pgl_contract_tn -- readable columns rounded down to even, (a_cols & ~1) >= M and (b_cols & ~1) >= N required and
+ * checked; they hold for every batch.  Rows of a batch's A and B from its batch_k on are not read. */
 int pgl_contract_tn_batched(const double* A, long lda, long strideA, int a_cols, const double* B, long ldb, long strideB, int b_cols, double* C,
                             long ldc, long strideC, int M, int N, int K, int nbatch, const int* batch_k, double alpha, double beta, int tri,
                             int kernel, void* hip_stream);

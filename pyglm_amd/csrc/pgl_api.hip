@@ -139,6 +139,7 @@ int pgl_scaled_gram(const double* G0, long ldg, const double* inv_eta, double* J
 int pgl_weighted_gram(const double* X, long ldx, int x_cols, const double* W, long ldw, int Tp, int D, int nz, double* J, long ldj, long strideJ,
                       int accumulate, void* st) {
     PGL_CHECK_ARG(X && W && J && Tp > 0 && Tp % 16 == 0 && D > 0 && nz > 0 && ldj >= D && ldw >= nz && x_cols <= ldx);
+    PGL_CHECK_ARG((x_cols & ~1) >= D);      // the readable columns, rounded down to even, cover the D that are contracted (include/pyglm_hip.h)
     PglGemmArgs a{};
     a.A = X; a.lda = ldx; a.strideA = 0;
     a.B = X; a.ldb = ldx; a.strideB = 0;
@@ -154,6 +155,7 @@ int pgl_weighted_gram(const double* X, long ldx, int x_cols, const double* W, lo
 int pgl_contract_tn(const double* A, long lda, int a_cols, const double* B, long ldb, int b_cols, double* C, long ldc, int M, int N, int K,
                     double alpha, double beta, void* st) {
     PGL_CHECK_ARG(A && B && C && M > 0 && N > 0 && K > 0 && K % 16 == 0 && ldc >= N);
+    PGL_CHECK_ARG((a_cols & ~1) >= M && (b_cols & ~1) >= N);      // readable columns, rounded down to even (include/pyglm_hip.h)
     PglGemmArgs a{};
     a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.C = C; a.ldc = ldc;
     a.M = M; a.N = N; a.K = K; a.a_cols = a_cols & ~1; a.b_cols = b_cols & ~1;
@@ -166,6 +168,7 @@ int pgl_contract_tn_batched(const double* A, long lda, long strideA, int a_cols,
                             int kernel, void* st) {
     PGL_CHECK_ARG(A && B && C && M > 0 && N > 0 && K > 0 && K % 16 == 0 && ldc >= N && nbatch > 0 && tri >= 0 && tri <= 2 && kernel >= 0 && kernel <= 2);
     PGL_CHECK_ARG(tri == 0 || M == N);
+    PGL_CHECK_ARG((a_cols & ~1) >= M && (b_cols & ~1) >= N);      // readable columns, rounded down to even (include/pyglm_hip.h)
     PglGemmArgs a{};
     a.A = A; a.lda = lda; a.strideA = strideA; a.B = B; a.ldb = ldb; a.strideB = strideB; a.C = C; a.ldc = ldc; a.strideC = strideC;
     a.M = M; a.N = N; a.K = K; a.a_cols = a_cols & ~1; a.b_cols = b_cols & ~1;
