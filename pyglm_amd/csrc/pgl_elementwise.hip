@@ -274,9 +274,19 @@ int pgl_k_colsum_partials(const double* part, int nblk, int ncol, double* out, i
 int pgl_k_basis_conv(const double* S, long lds, const double* basis, double* X, long ldx, double* Xt, long ldxt, int T, int N, int B, int R,
                      int clip, hipStream_t st) {
     if (B > 32) { pgl_set_error("basis_conv: B=%d > 32 unsupported", B); return PGL_ERR_ARG; }
+    // the basis in LDS: beyond 64 KiB (R * B > 8192) the kernel's dynamic-LDS limit is raised first, as by every launcher here that takes
+    // dynamic LDS (the launch has been seen to work without on an MI355X; HIP does not promise it), and beyond the CU's 160 KiB it is refused
+    const size_t lds_bytes = (size_t)R * B * sizeof(double);
+    if (lds_bytes > 160 * 1024) {
+        pgl_set_error("basis_conv: a basis of R=%d x B=%d doubles (%zu bytes) exceeds the 160 KiB of LDS", R, B, lds_bytes);
+        return PGL_ERR_ARG;
+    }
+    static PglPerDeviceSize lds_set;
+    if (lds_bytes > 64 * 1024)
+        if (int rc = pgl_grow_dynamic_lds(reinterpret_cast<const void*>(basis_conv_kernel), lds_bytes, lds_set)) return rc;
     ConvArgs a{S, lds, basis, X, ldx, Xt, ldxt, T, N, B, R, clip};
     const long total = (long)T * N;
-    hipLaunchKernelGGL(basis_conv_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), (size_t)R * B * sizeof(double), st, a);
+    hipLaunchKernelGGL(basis_conv_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), lds_bytes, st, a);
     PGL_CHECK_LAUNCH();
     return PGL_OK;
 }
